@@ -10,12 +10,17 @@ from pinned host memory exactly as the reference feeds its model (the PCIe copy 
   python bench.py --gpus 1 --steps 300 --warmup 30
   python bench.py --gpus N ...          (no launcher: starts its N ranks itself, one per GPU -- radnet_hip/launch.py)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+  python bench.py ... --full            (adds the secondary legs: roofline, 3x3 layer table, collectives alone, CPU baseline)
+  python bench.py ... --dump-outputs D  (writes the last timed step's outputs as D/<name>.npy, for output-by-output comparison)
+
+A plain run sets up, primes, warms up, times the steps and prints the line; everything else it can measure runs only with --full.
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "rock-art-radnet_amd")):
@@ -293,6 +298,51 @@ def collectives_leg(eng, ts, dist, world, n=20):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: everything written, at most
+DUMP_SAMPLE = 1 << 18              # elements kept of a larger array: a fixed, seeded sample (same indices on every run)
+
+
+def _dump_sample(a, seed):
+    """`a` flattened; above DUMP_SAMPLE elements, the elements at DUMP_SAMPLE sorted random indices drawn from a private
+    RandomState(seed) -- NumPy's global stream, which the step consumes, is not touched."""
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.size <= DUMP_SAMPLE:
+        return a
+    return a[np.sort(np.random.RandomState(seed).randint(0, a.size, DUMP_SAMPLE))]
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> array; each written as path/<name>.npy, float64 if it is float64, else float32."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in sorted(arrays.items()):
+        a = np.asarray(a)
+        out[name] = _dump_sample(a, zlib.crc32(name.encode())).astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def train_outputs(losses, weights):
+    """What a caller of the train step receives: the step's losses (float64 scalars) and the trainable weights it updated."""
+    out = {"loss_" + k: np.float64(v) for k, v in losses.items()}
+    for layer, parts in weights.items():
+        for part, a in parts.items():
+            out["weight_%s_%s" % (layer, part)] = a
+    return out
+
+
+def detection_outputs(dets, class_mapping):
+    """One tile's detections {class name: (boxes, probs)} as one (n, 6) float64 array of rows (class index, x1, y1, x2, y2,
+    prob), sorted by class, then prob (descending), then box."""
+    rows = [(class_mapping[name], *map(float, b), float(p)) for name, (boxes, probs) in dets.items() for b, p in zip(boxes, probs)]
+    a = np.array(rows, np.float64).reshape(-1, 6)
+    a = a[np.lexsort((a[:, 4], a[:, 3], a[:, 2], a[:, 1], -a[:, 5], a[:, 0]))]
+    return {"detections": a}
+
+
 def _host_cores():
     try:
         return len(os.sched_getaffinity(0))
@@ -337,6 +387,8 @@ def bench_predict(args):
     dets = net._detect_all(seq(args.steps))
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, detection_outputs(dets[-1], C.class_mapping))
     n_det = sum(len(v[0]) for d in dets[:len(tiles)] for v in d.values())
     # ---- roofline leg: the same tiles one at a time on ONE lane, GEMM launches timed from their own dispatch
     roof = None
@@ -405,8 +457,15 @@ def main():
     ap.add_argument("--per-gpu-batch", type=int, default=1)
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--width", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--roofline-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary measurements: the roofline leg (--roofline-steps), the "
+                         "3x3 layer table, the collectives alone (multi-GPU) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, a fixed seeded sample of "
+                         "a large array, at most 64 MB in all): train workloads the losses and the trainable weights, predict "
+                         "the last tile's detections")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--roofline-steps", type=int, default=3, help="--full: steps of the roofline leg (0: none)")
     ap.add_argument("--trainable", choices=("train", "cont"), default="train",
                     help="train: train.py trainability, whole base frozen (the BASELINE metric); cont: cont_train.py, stages 3-4 "
                          "unfrozen in both models (secondary measurement, single GPU)")
@@ -421,6 +480,9 @@ def main():
                     help="start the ranks, form the process group over gloo (no GPU), all-reduce the ranks, print one JSON line: "
                          "exercises the self-launch path on a machine without GPUs (tests/test_bench_launch.py)")
     args = ap.parse_args()
+    if not args.full:                # a plain run: only what the headline figure needs
+        args.roofline_steps = 0
+        args.no_cpu_baseline = True
 
     if args.workload == "cont":
         args.trainable = "cont"
@@ -583,6 +645,8 @@ def main():
             dist.destroy_process_group()
         raise SystemExit("invalid run: %d classifier-head steps were skipped inside the timed region" % skipped)
     losses = ts.losses()
+    if args.dump_outputs and rank == 0:       # before the roofline leg, whose steps update the weights further
+        dump_outputs(args.dump_outputs, train_outputs(losses, eng.get_weights()))
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=eng.dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -643,7 +707,7 @@ def main():
                 roof["layers_3x3"] = layers_3x3_table(eng, bp0, eng._plan_rpn(bp0["fh"], bp0["fw"], bp0["F"], nb0))
             except Exception as e:                       # a secondary table must never cost the bench line
                 roof["layers_3x3_error"] = repr(e)
-    coll = collectives_leg(eng, ts, dist, world) if (dist is not None and not cont) else None
+    coll = collectives_leg(eng, ts, dist, world) if (args.full and dist is not None and not cont) else None
     if dist is not None:
         dist.barrier()
 

@@ -69,7 +69,7 @@ def test_predict_tile_composed_equals_model_calls():
     assert np.array_equal(pc, pc_ref[0]) and np.array_equal(pr, pr_ref[0])
 
 
-def test_train_step_composed_equals_scheduler_one_lane():
+def test_train_step_composed_equals_scheduler_one_lane(tmp_path):
     """Three iterations through radnet_train_step == three TrainStep.step calls (one lane): losses, RNG consumption, RoI
     selection, and every trainable weight."""
     from radnet_hip import native
@@ -85,7 +85,7 @@ def test_train_step_composed_equals_scheduler_one_lane():
         la.append(ts.losses())
     rng_a = int(np.random.randint(0, 2 ** 31 - 1))
     wa = eng_a.get_weights()
-    tune = "/tmp/radnet_native_tune.txt"
+    tune = str(tmp_path / "tune.txt")
     eng_a.save_tuning(tune)
     C2, P2, eng_b = make()
     eng_b.load_tuning(tune)                          # same launch shapes -> same summation order

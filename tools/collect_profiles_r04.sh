@@ -4,10 +4,11 @@ TAG=${TAG:-r04}
 mkdir -p gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 T=gpurun_out/$TAG/tune.txt
+D=$(dirname $T)        # this run's output folder
 rm -f $T
 # the bench line with the shipped tables (what the driver runs), 300-step and driver form
-python bench.py > gpurun_out/$TAG/bench.json 2> gpurun_out/$TAG/bench.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/$TAG/bench_20_steps_driver_form.json 2> gpurun_out/$TAG/bench20.err
+python bench.py --full > $D/bench.json 2> $D/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $D/bench_20_steps_driver_form.json 2> $D/bench20.err
 python bench.py --tune-cache $T --no-cpu-baseline --roofline-steps 0 --steps 40 --warmup 10 > /dev/null 2>&1      # table of this box for the traced runs
 # pipelined run under the tracer (lane timeline)
 rocprofv3 --kernel-trace --stats -d gpurun_out/$TAG/pipe -o pipe --output-format csv -- python3 bench.py --tune-cache $T --no-cpu-baseline --roofline-steps 0 --steps 40 --warmup 20 > gpurun_out/$TAG/pipe.log 2>&1
@@ -30,11 +31,11 @@ bash tools/rpn_gemm_traffic.sh gpurun_out/$TAG/rpn_traffic > gpurun_out/$TAG/rpn
 rm -rf gpurun_out/$TAG/rpn_traffic
 head -14 gpurun_out/$TAG/trace_summary.txt; head -16 gpurun_out/$TAG/pmc_summary.txt | cut -c1-220; cat gpurun_out/$TAG/rpn_gemm_traffic.txt
 # the other bench lines (BASELINE cfg 3 / cfg 5 / cont_train.py mode / cfg 4 on one GPU / the data-parallel schedule rehearsed with 1-rank communicators)
-for w in predict vgg16 cont; do python bench.py --workload $w > gpurun_out/$TAG/bench_$w.json 2> gpurun_out/$TAG/bench_$w.err; done
-python bench.py --per-gpu-batch 2 --no-cpu-baseline > gpurun_out/$TAG/bench_per_gpu_batch2_ordered.json 2>/dev/null
-RADNET_DETERMINISTIC=0 python bench.py --per-gpu-batch 2 --no-cpu-baseline > gpurun_out/$TAG/bench_per_gpu_batch2_atomics.json 2>/dev/null
-RADNET_BENCH_REHEARSAL=nccl1 python bench.py --no-cpu-baseline > gpurun_out/$TAG/bench_dp_rehearsal_native_exchange.json 2>/dev/null
-python bench.py --no-cpu-baseline > gpurun_out/$TAG/bench_same_box_as_dp_rehearsal.json 2>/dev/null
+for w in predict vgg16 cont; do python bench.py --full --workload $w > $D/bench_$w.json 2> $D/bench_$w.err; done
+python bench.py --full --per-gpu-batch 2 --no-cpu-baseline > $D/bench_per_gpu_batch2_ordered.json 2>/dev/null
+RADNET_DETERMINISTIC=0 python bench.py --full --per-gpu-batch 2 --no-cpu-baseline > $D/bench_per_gpu_batch2_atomics.json 2>/dev/null
+RADNET_BENCH_REHEARSAL=nccl1 python bench.py --full --no-cpu-baseline > $D/bench_dp_rehearsal_native_exchange.json 2>/dev/null
+python bench.py --full --no-cpu-baseline > $D/bench_same_box_as_dp_rehearsal.json 2>/dev/null
 python - <<PY
 import json, glob
 for f in sorted(glob.glob("gpurun_out/$TAG/bench*.json")):
