@@ -183,6 +183,22 @@ int radnet_conv_fwd_pair(radnet_ctx* ctx, const radnet_conv_desc* d1, const radn
  * do write db->y -- for every other geometry, forced configs, autotuning off, RADNET_NO_BNECK_FUSE=1. */
 int radnet_conv_bottleneck(radnet_ctx* ctx, const radnet_conv_desc* db, const radnet_conv_desc* dc, const radnet_conv_desc* da);
 
+/* ---- inference convolution on bf16 matrix cores (csrc/conv_bf16.hip) -----------------------------
+ * The forward semantics of radnet_conv_fwd (resnet50.py:41-147,183-186; rpn.py:41-64) with bf16 operands and fp32 accumulation,
+ * for frozen weights only (RADNet.predict, RADNet.py:520-600; the reference runs the same graph in fp32):
+ *   y[m][n] = act( (sum_k bf16(im2col(x))[m][k] * bf16(w)[k][n]) * scale[n] + shift[n] + addend[m][n] ),  act / act_cols as above.
+ * bf16() rounds to nearest, ties to even (v_cvt_pk_bf16_f32); subnormals are kept.  Activations stay fp32 in memory: the gather
+ * rounds x on its way to the matrix cores, the epilogue and y are fp32.  No atomics, no split K: two runs give the same bits.
+ *
+ * radnet_weights_to_bf16: wt[j][i] = bf16(w[i][j]) for i < k, j < n; 0 for k <= i < ldk (w [k][ldw] fp32, wt [n][ldk] bf16 bits).
+ *   Made once per weight load.  ldk >= k rounded up to 32 (the kernel's K tile), a multiple of 8.
+ * radnet_conv_fwd_bf16: d->w and d->ldw are ignored; wt / ldk are the output of radnet_weights_to_bf16 for this layer's weights
+ *   (k = kh*kw*c).  Needs c % 8 == 0 (8 consecutive k are 8 channels of one tap: the 4-channel stem stays on radnet_conv_fwd;
+ *   RADNET_ERR_UNSUPPORTED otherwise), 16-byte aligned x and wt.  Any kernel size, stride and padding radnet_conv_fwd takes.
+ *   The launch shape (128x128, 128x64 or 64x64 output tiles) is a fixed rule of (M, N): no autotuning, no tuning-table entry. */
+int radnet_weights_to_bf16(radnet_ctx* ctx, const float* w, int32_t k, int32_t n, int32_t ldw, uint16_t* wt, int32_t ldk);
+int radnet_conv_fwd_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wt, int32_t ldk);
+
 /* out[n] (+)= sum_m g[m][n] * gscale[n]   (bias gradients) */
 int radnet_colsum(radnet_ctx* ctx, const float* g, int32_t m, int32_t n, int32_t ld, const float* gscale,
                   float* out, int32_t accumulate);
@@ -372,12 +388,13 @@ int radnet_relu_mask(radnet_ctx* ctx, float* g, const float* act, int64_t n);
  *   FILL0        p: dst                      i: bytes (low 32 bits), bytes (high 32 bits)
  *   RELU_MASK    p: g, act                   i: n (low), n (high)
  *   ROI_BWD      p: dy, rois, dfmap          i: h, w, c, r, ps
- *   CHAIN        p: radnet_chain*             (radnet_chain_run: a run of CONV_FWD / WINO ops as one persistent launch) */
+ *   CHAIN        p: radnet_chain*             (radnet_chain_run: a run of CONV_FWD / WINO ops as one persistent launch)
+ *   CONV_FWD_BF16 conv, p[0] = wt (bf16 weights), i[0] = ldk   (radnet_conv_fwd_bf16: predict programs in bf16 mode) */
 enum {
   RADNET_OP_CONV_FWD = 1, RADNET_OP_CONV_DGRAD = 2, RADNET_OP_CONV_WGRAD = 3, RADNET_OP_MAXPOOL = 4, RADNET_OP_COLSUM = 5,
   RADNET_OP_WINO = 6, RADNET_OP_WINO_REUSE = 7, RADNET_OP_WINO_WGRAD = 8, RADNET_OP_SCATTER = 9, RADNET_OP_FILL0 = 10,
   RADNET_OP_RELU_MASK = 11, RADNET_OP_ROI_BWD = 12, RADNET_OP_CONV_BWD = 13, RADNET_OP_CHAIN = 14, RADNET_OP_CONV_FWD_PAIR = 15,
-  RADNET_OP_CONV_BNECK = 16,
+  RADNET_OP_CONV_BNECK = 16, RADNET_OP_CONV_FWD_BF16 = 17,
   RADNET_OP_NOP = 0
 };
 typedef struct radnet_op {

@@ -374,8 +374,11 @@ class _ConfigUnpickler(pickle.Unpickler):
                                      % (module, name))
 
 
-def load_radnet(config_path, device_index=0):
-    """RADNet.py:721-775: unpickle the Config, build the RPN (3 outputs) and detector models, load C.weights_path."""
+def load_radnet(config_path, device_index=0, precision="fp32"):
+    """RADNet.py:721-775: unpickle the Config, build the RPN (3 outputs) and detector models, load C.weights_path.
+    precision="bf16": the convolutions run on bf16 matrix cores with fp32 accumulation (ResNet50, inference only)."""
+    if precision not in ("fp32", "bf16"):
+        raise ValueError("precision must be 'fp32' or 'bf16', not %r" % (precision,))
     from . import models
     with open(config_path, 'rb') as f:
         C = _ConfigUnpickler(f).load()
@@ -386,6 +389,6 @@ def load_radnet(config_path, device_index=0):
     else:
         print('Not a valid base model!')
         sys.exit(1)
-    _, _, model_all, model_rpn, model_detector = models.build_models(C, device_index=device_index, workload="predict")      # loads no train-step launch-shape table
+    _, _, model_all, model_rpn, model_detector = models.build_models(C, device_index=device_index, workload="predict", precision=precision)      # loads no train-step launch-shape table
     model_all.load_weights(str(C.weights_path).replace('\\', '/'), by_name=True)
     return RADNet(C, model_rpn, model_detector, base_model.preprocess)

@@ -24,11 +24,12 @@ class Adam:
 
 
 class _Shared:
-    def __init__(self, C, device_index=0, weights=None, lr=5e-5, bce_mode=0, workload=None):
+    def __init__(self, C, device_index=0, weights=None, lr=5e-5, bce_mode=0, workload=None, precision="fp32"):
         from radnet_hip import synth
         from radnet_hip import make_engine
         self.C = C
-        self.eng = make_engine(C, device_index=device_index, bce_mode=bce_mode, lr=lr, workload=workload)
+        kw = {} if precision == "fp32" else dict(precision=precision)
+        self.eng = make_engine(C, device_index=device_index, bce_mode=bce_mode, lr=lr, workload=workload, **kw)
         if weights is None:
             gen = synth.synthetic_weights_vgg16 if C.network == "vgg16" else synth.synthetic_weights
             weights = gen(seed=3, n_anchors=self.eng.A, n_classes=self.eng.nc)
@@ -175,6 +176,7 @@ class RPNModel(_ModelBase):
 
     def train_on_batch(self, X, Y):
         eng = self._s.eng
+        eng.check_trainable("model_rpn.train_on_batch")
         self._use_lr()
         bp, rp = self._forward(X)
         y_cls, y_regr = self._targets(Y, rp)
@@ -186,6 +188,7 @@ class RPNModel(_ModelBase):
 
     def test_on_batch(self, X, Y):
         eng = self._s.eng
+        eng.check_trainable("model_rpn.test_on_batch")
         bp, rp = self._forward(X)
         y_cls, y_regr = self._targets(Y, rp)
         eng.ctx.call("radnet_rpn_loss", rp["pred"], 64, y_cls, y_regr, rp["M"], eng.A, eng.bce_mode, rp["dz"], 64, eng.rpn_losses, eng.loss_scratch)
@@ -220,6 +223,7 @@ class ClassifierModel(_ModelBase):
 
     def train_on_batch(self, inputs, targets):
         eng = self._s.eng
+        eng.check_trainable("model_classifier.train_on_batch")
         self._use_lr()
         hp = self._prepare(inputs, targets, training=True)
         eng.set_accumulate(hp["bwd"], False)
@@ -230,6 +234,7 @@ class ClassifierModel(_ModelBase):
 
     def test_on_batch(self, inputs, targets):
         eng = self._s.eng
+        eng.check_trainable("model_classifier.test_on_batch")
         hp = self._prepare(inputs, targets)
         eng.ctx.call("radnet_det_loss", hp["pcls"], hp["pregr"], hp["y1"], hp["y2"], hp["R"], eng.nc, eng.nreg, hp["dz"], eng.det_losses)
         return self._losses()
@@ -278,9 +283,15 @@ class AllModel(_ModelBase):
     """Model([img, rois], rpn[:2] + classifier) (train.py:211): exists to save / load every weight."""
 
 
-def build_models(C, device_index=0, weights=None, lr=5e-5, bce_mode=None, workload=None):
+def build_models(C, device_index=0, weights=None, lr=5e-5, bce_mode=None, workload=None, precision="fp32"):
     """The four model objects of train.py:199-211 / RADNet.py:748-770 over one shared engine.
-    Returns (model_rpn [2 outputs], model_classifier, model_all, model_rpn_predict [3 outputs], model_detector)."""
+    Returns (model_rpn [2 outputs], model_classifier, model_all, model_rpn_predict [3 outputs], model_detector).
+    precision="bf16": inference-only models whose convolutions run on bf16 matrix cores with fp32 accumulation (ResNet50 only;
+    the training calls raise RuntimeError)."""
     from . import losses
-    s = _Shared(C, device_index, weights, lr, losses.BCE_MODE if bce_mode is None else bce_mode, workload)
+    if precision not in ("fp32", "bf16"):
+        raise ValueError("precision must be 'fp32' or 'bf16', not %r" % (precision,))
+    if precision == "bf16" and C.network != "resnet50":
+        raise NotImplementedError("precision='bf16' is implemented for the ResNet50 network only (not %r)" % (C.network,))
+    s = _Shared(C, device_index, weights, lr, losses.BCE_MODE if bce_mode is None else bce_mode, workload, precision)
     return RPNModel(s), ClassifierModel(s), AllModel(s), RPNModel(s, with_features=True), DetectorModel(s)

@@ -132,7 +132,15 @@ class FasterRCNNEngine:
     supports_batched = True      # per-GPU mini-batch as one layer program (upload_images / _plan_rpn(nb) / _plan_head(groups))
     feat_len = staticmethod(feat_len)
 
-    def __init__(self, C_cfg, device_index=0, n_classes=None, bce_mode=0, lr=5e-5, autotune=True, workload=None):
+    def __init__(self, C_cfg, device_index=0, n_classes=None, bce_mode=0, lr=5e-5, autotune=True, workload=None, precision="fp32"):
+        # "bf16": inference only -- every conv with a multiple of 8 input channels runs on bf16 matrix cores (fp32 accumulation,
+        # csrc/conv_bf16.hip) on bf16 copies of the weights; training entry points refuse such an engine
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("precision must be 'fp32' or 'bf16', not %r" % (precision,))
+        if precision == "bf16" and (self.NETWORK != "resnet50" or C_cfg.network != "resnet50"):
+            raise NotImplementedError("precision='bf16' is implemented for the ResNet50 network only (not %r)" % (C_cfg.network,))
+        self.precision = precision
+        self._bf16_w = {}              # fp32 weight pointer -> (bf16 copy [N][ldk], ldk, conv layer, N)
         self.workload = workload or self.WORKLOAD
         self.TUNED_PREFIX = "%s_%s_" % (self.workload, self.NETWORK)
         if C_cfg.network != self.NETWORK:
@@ -177,6 +185,8 @@ class FasterRCNNEngine:
         # 256 by default: the chain's static deal needs every workgroup of every concurrently running chain resident, and the
         # pipelined step runs two of them (prefetch lanes) beside the RPN and classifier lanes' launches (1 024 slots on the chip)
         self.chain_wgs = int(os.environ.get("RADNET_CHAIN_WGS", "256"))
+        if precision == "bf16":        # the paired, bottleneck and chain launches are fp32 kernels: bf16 programs hold plain ops
+            self.use_chain = self.fwd_pair = self.bneck_fuse = self.head_train_wino = False
         self._chain_plans = []     # plans whose base forward is a chain launch: check_chains() reads their sticky error words
         self.wino_wgrad = os.environ.get("RADNET_NO_WINOGRAD_WGRAD", "0") != "1"
         # ... and their weight gradients in the Winograd domain, on the transformed input the forward pass left (the rpn_conv1 path)
@@ -325,6 +335,7 @@ class FasterRCNNEngine:
         """Winograd filter transforms of the classifier's 3x3 convs (inference plans only) after the head weights changed."""
         if getattr(self, "_inference_filters_stale", False):
             self._inference_filters_stale = False
+            self._refresh_bf16()
             self._refresh_winograd([n for n in self.INFERENCE_WINOGRAD_LAYERS if getattr(self.convs.get(n), "wino_u", None) is not None])
 
     def refresh_head_shift(self):
@@ -386,6 +397,7 @@ class FasterRCNNEngine:
         self.dense_w.copy_(t(k)); self.dense_b.copy_(t(b))
         self.refresh_head_shift()
         self._refresh_winograd()
+        self._refresh_bf16()
         torch.cuda.synchronize(self.dev)
 
     def get_weights(self, names=None):
@@ -435,6 +447,8 @@ class FasterRCNNEngine:
     INFERENCE_WINOGRAD_LAYERS = tuple("res5%s_branch2b" % b for b in "abc")
 
     def _uses_winograd(self, c, inference=False):
+        if getattr(self, "precision", "fp32") == "bf16":
+            return False               # bf16 mode: every 3x3 conv in the direct form (the F(4x4) transforms amplify the rounding)
         listed = c.name in self.WINOGRAD_LAYERS or ((inference or getattr(self, "head_train_wino", False)) and c.name in self.INFERENCE_WINOGRAD_LAYERS
                                                     and os.environ.get("RADNET_NO_INFERENCE_WINOGRAD", "0") != "1")
         return self.use_winograd and listed and c.kh == 3 and c.stride == 1 and c.pad == 1 and c.cin % 32 == 0
@@ -461,6 +475,45 @@ class FasterRCNNEngine:
                 c.wino_m = 4 if name in self.INFERENCE_WINOGRAD_LAYERS else self._wino_form(c)
                 c.wino_u = torch.empty((c.wino_m + 2) ** 2, c.cin, c.cout, dtype=torch.float32, device=self.dev)
             self.ctx.call("radnet_winograd4_filter" if c.wino_m == 4 else "radnet_winograd_filter", c.weight, c.cin, c.cout, c.ldw, c.wino_u)
+
+    # ------------------------------------------------------------------------------------------ bf16 inference mode
+    def check_trainable(self, what):
+        """Training entry points call this: a bf16 engine is an inference engine."""
+        if getattr(self, "precision", "fp32") != "fp32":
+            raise RuntimeError("%s: this engine was built with precision=%r, which is inference only; build an fp32 engine to train"
+                               % (what, self.precision))
+
+    def _bf16_weights(self, c):
+        """bf16 copy [N][ldk] of conv `c`'s weights (N = the descriptor's output columns, ldk = K rounded up to 32), made on first
+        use; _refresh_bf16 rewrites it in place whenever the weights change, so compiled programs and hipGraphs keep their pointers."""
+        ent = self._bf16_w.get(c.weight.data_ptr())
+        if ent is None:
+            k = c.kh * c.kh * c.cin
+            n = c.ldw if c.name == "rpn_heads" else c.cout
+            ldk = (k + 31) // 32 * 32
+            wt = torch.empty(n, ldk, dtype=torch.int16, device=self.dev)
+            ent = (wt, ldk, c, n)
+            self._bf16_w[c.weight.data_ptr()] = ent
+            self.ctx.call("radnet_weights_to_bf16", c.weight, k, n, c.ldw, wt, ldk)
+        return ent
+
+    def _refresh_bf16(self):
+        for wt, ldk, c, n in self._bf16_w.values():
+            self.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, n, c.ldw, wt, ldk)
+
+    def _bf16_ops(self, ops):
+        """bf16 mode: every direct forward conv whose input has a multiple of 8 channels -> ("conv_bf16", desc); the 4-channel stem
+        stays fp32.  fp32 mode: `ops` unchanged."""
+        if getattr(self, "precision", "fp32") != "bf16":
+            return ops
+        by_ptr = {c.weight.data_ptr(): c for c in self.convs.values()}
+        out = []
+        for kind, p in ops:
+            if kind == "conv" and p.c % 8 == 0:
+                self._bf16_weights(by_ptr[p.w])
+                kind = "conv_bf16"
+            out.append((kind, p))
+        return out
 
     def _fwd_op(self, c, x, nb, h, w, y, keep, relu=True, inference=False):
         """Forward op of conv `c` on x -> y: the direct implicit GEMM, or the Winograd form for the layers listed above."""
@@ -530,6 +583,7 @@ class FasterRCNNEngine:
                 cur, h, w = out, oh, ow
         if self.bneck_fuse and not self.use_chain and self.FROZEN_BASE_FUSION:
             ops = self._fuse_bottlenecks(ops)
+        ops = self._bf16_ops(ops)
         plan = dict(ops=ops, x=x, F=cur, fh=h, fw=w, keep=keep, nb=nb)
         if self.use_chain:
             self._chain_ops(plan, first=2)               # conv1 (4-channel stem) and the max-pool stay launches of their own
@@ -763,6 +817,11 @@ class FasterRCNNEngine:
             elif kind in ("bneck_second", "bneck_third"):
                 o.kind = L.OP_NOP
                 o.conv = p
+            elif kind == "conv_bf16":              # bf16 inference mode: the layer's bf16 weight copy rides in p[0] / i[0]
+                wt, ldk, _, _ = self._bf16_w[p.w]
+                o.kind = L.OP_CONV_FWD_BF16
+                o.conv = p
+                o.p[0], o.i[0] = wt.data_ptr(), ldk
             elif kind in ("conv", "dgrad", "wgrad"):
                 o.kind = {"conv": L.OP_CONV_FWD, "dgrad": L.OP_CONV_DGRAD, "wgrad": L.OP_CONV_WGRAD}[kind]
                 o.conv = p
@@ -988,8 +1047,8 @@ class FasterRCNNEngine:
         bwd = self._fuse_bias_grads(bwd)
         ws_bytes = int(self.lib.radnet_proposals_ws_bytes(M1 * self.A))
         # the re-prediction after Adam #1 (train.py:291) sees the same feature map: its input transform is already in V
-        refwd = [("wino_reuse", op1[1]) if op1[0] == "wino" else op1, ("conv", d2)]
-        plan = dict(fwd=[op1, ("conv", d2)], refwd=refwd, bwd=bwd, b1=b1, h=hbuf, pred=pred, dz=dz, dh=dh, M=M1, nb=nb, fh=fh, fw=fw,
+        refwd = self._bf16_ops([("wino_reuse", op1[1]) if op1[0] == "wino" else op1, ("conv", d2)])
+        plan = dict(fwd=self._bf16_ops([op1, ("conv", d2)]), refwd=refwd, bwd=bwd, b1=b1, h=hbuf, pred=pred, dz=dz, dh=dh, M=M1, nb=nb, fh=fh, fw=fw,
                     wino_keep=wino_keep,
                     prop_ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev),
                     R=torch.zeros(1024, 4, dtype=torch.int64, device=dev), Rp=torch.zeros(1024, dtype=torch.float32, device=dev),
@@ -1049,6 +1108,7 @@ class FasterRCNNEngine:
     def adam(self, arena, grad_scale=1.0, zero_grad=True):
         """One Keras-2 Adam step over the arena.  zero_grad: the gradient arena is cleared in the same pass, so the
         next step's backward accumulates into zeros without a memset (arenas start zeroed, Arena.finalize)."""
+        self.check_trainable("adam")
         arena.t += 1
         is_head = arena is getattr(self, "head_arena", None)
         fused = (is_head and getattr(self, "head_bias_len", 0) > 0 and self.head_bias_off % 4 == 0
@@ -1140,6 +1200,8 @@ class FasterRCNNEngine:
         key = ("head" if training else "head_inf", R, fh, fw, F.data_ptr(), groups)
         if key in self._plans:
             return self._plans[key]
+        if training:
+            self.check_trainable("classifier training plan")
         if R % groups:
             raise L.RadnetError("head plan: %d RoIs do not split into %d groups" % (R, groups))
         dev = self.dev
@@ -1190,6 +1252,7 @@ class FasterRCNNEngine:
         tail_scratch = torch.zeros(int(self.lib.radnet_head_tail_scratch_bytes(R)), dtype=torch.uint8, device=dev)
         keep.append(tail_scratch)
         if not training:
+            fwd = self._bf16_ops(fwd)
             plan = dict(R=R, rois=rois, pooled=pooled, fwd=fwd, blocks=blocks, y5=cur, hw=h * w, M=M, feat=feat, pcls=pcls, pregr=pregr,
                         F=F, fh=fh, fw=fw, keep=keep, groups=groups, tail_scratch=tail_scratch)
             self._plans[key] = plan

@@ -42,6 +42,7 @@ class ConvDesc(C.Structure):
 # ---- layer programs and composed entry points (include/radnet_hip.h, csrc/program.hip) --------------------------------
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_MAXPOOL, OP_COLSUM, OP_WINO, OP_WINO_REUSE, OP_WINO_WGRAD, OP_SCATTER, OP_FILL0, \
     OP_RELU_MASK, OP_ROI_BWD, OP_CONV_BWD, OP_CHAIN, OP_CONV_FWD_PAIR, OP_CONV_BNECK = range(1, 17)
+OP_CONV_FWD_BF16 = 17
 OP_NOP = 0
 
 
@@ -158,6 +159,8 @@ def load_library():
         "radnet_timing_read": (C.c_int, [vp, C.c_int, C.POINTER(f64), C.POINTER(i64), C.POINTER(f64)]),
         "radnet_timing_reset": (C.c_int, [vp]),
         "radnet_conv_fwd": (C.c_int, [vp, C.POINTER(ConvDesc)]),
+        "radnet_conv_fwd_bf16": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32]),
+        "radnet_weights_to_bf16": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
         "radnet_conv_dgrad": (C.c_int, [vp, C.POINTER(ConvDesc)]),
         "radnet_gemm_batched": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32]),
         "radnet_winograd_filter": (C.c_int, [vp, vp, i32, i32, i32, vp]),

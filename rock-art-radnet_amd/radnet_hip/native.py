@@ -70,6 +70,8 @@ class NativeTrainStep:
     engine.select_samples)."""
 
     def __init__(self, eng, world=1):
+        if getattr(eng, "precision", "fp32") != "fp32":
+            eng.check_trainable("NativeTrainStep")
         self.eng = eng
         self.world = world
         self.skipped_head_steps = 0

@@ -77,6 +77,8 @@ class TrainStep:
         its own optimizer), so the update order the reference defines is unchanged while the exchange hides under
         the next image's anchor labelling, base forward and RPN phases.  Call flush() after the last
         step."""
+        if getattr(eng, "precision", "fp32") != "fp32":
+            eng.check_trainable("TrainStep")
         self.eng = eng
         self.world = world_size
         self.group = dist_group
