@@ -198,6 +198,15 @@ int radnet_conv_bottleneck(radnet_ctx* ctx, const radnet_conv_desc* db, const ra
  *   The launch shape (128x128, 128x64 or 64x64 output tiles) is a fixed rule of (M, N): no autotuning, no tuning-table entry. */
 int radnet_weights_to_bf16(radnet_ctx* ctx, const float* w, int32_t k, int32_t n, int32_t ldw, uint16_t* wt, int32_t ldk);
 int radnet_conv_fwd_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wt, int32_t ldk);
+/* radnet_conv_fwd_bf16 with its K tiles dealt over `ksplit` slices of one launch (bf16-mixed training: small M, deep K).  Ordered:
+ * every slice writes its partial tile to the context's workspace (radnet_set_workspace), the last to arrive sums the slices in
+ * slice order and runs the epilogue -- no float atomics, the bits do not depend on arrival order or timing.  ksplit <= 1 is
+ * radnet_conv_fwd_bf16 bit for bit; at most 64 and the number of 32-deep K tiles.  The split changes the summation order, so
+ * results differ from ksplit = 1 within the rounding of an fp32 sum.
+ * radnet_conv_bf16_pick_split: the split the bf16-mixed engine uses, a fixed function of (M = nb*oh*ow, N, K = kh*kw*c): the
+ * smallest power of two (at most 16) that gives >= 256 workgroups, doubled only while every slice keeps >= 8 K tiles. */
+int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wt, int32_t ldk, int32_t ksplit);
+int32_t radnet_conv_bf16_pick_split(int64_t m, int32_t n, int32_t k);
 
 /* out[n] (+)= sum_m g[m][n] * gscale[n]   (bias gradients) */
 int radnet_colsum(radnet_ctx* ctx, const float* g, int32_t m, int32_t n, int32_t ld, const float* gscale,
@@ -278,6 +287,21 @@ typedef struct radnet_adam_wino {
 int radnet_adam_step_fused(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1, float beta2,
                            float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len, const float* scale,
                            const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers);
+/* bf16-mixed training: radnet_adam_step_affine (shift may be 0: no bias re-fold) that ALSO rewrites the bf16 images of up to sixteen
+ * conv kernels that live in the arena -- [k][ldw] fp32 at float offset `off` -- from the weights it has just updated:
+ * wt[j][i] = bf16(p[off + i*ldw + j]) for i < k, j < n; 0 for k <= i < ldk (radnet_weights_to_bf16's layout and rounding).
+ * Bit-identical to radnet_adam_step_affine / radnet_adam_step followed by radnet_weights_to_bf16 for each listed layer.
+ * Needs ldw >= n, ldk >= k, ldw and off multiples of 4, ldk a multiple of 8, wt 16-byte aligned; layers inside the arena, not
+ * overlapping each other or the bias range; at most 16 layers.  Otherwise a negative code and nothing is launched. */
+typedef struct radnet_adam_bf16 {
+  int64_t off;           /* float offset of the kernel [k][ldw] in the arena */
+  int32_t k, n, ldw;     /* reduction length kh*kw*c, output columns of the image, row pitch of the fp32 kernel */
+  uint16_t* wt;          /* bf16 image [n][ldk] */
+  int32_t ldk;           /* >= k, a multiple of 8 */
+} radnet_adam_bf16;
+int radnet_adam_step_bf16(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1, float beta2,
+                          float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len, const float* scale,
+                          const float* t0, float* shift, const radnet_adam_bf16* layers, int32_t n_layers);
 
 /* ---- proposal decode + greedy NMS (rpn.py:68-172, 299-344, 380-455), fp64 ---------------------
  * pred: fused head output [rows*cols][ld_pred] (scores in [0,A), regression in [A,5A)).
@@ -389,7 +413,8 @@ int radnet_relu_mask(radnet_ctx* ctx, float* g, const float* act, int64_t n);
  *   RELU_MASK    p: g, act                   i: n (low), n (high)
  *   ROI_BWD      p: dy, rois, dfmap          i: h, w, c, r, ps
  *   CHAIN        p: radnet_chain*             (radnet_chain_run: a run of CONV_FWD / WINO ops as one persistent launch)
- *   CONV_FWD_BF16 conv, p[0] = wt (bf16 weights), i[0] = ldk   (radnet_conv_fwd_bf16: predict programs in bf16 mode) */
+ *   CONV_FWD_BF16 conv, p[0] = wt (bf16 weights), i[0] = ldk, i[1] = ksplit (0 or 1: one pass; radnet_conv_fwd_bf16_split)
+ *                (bf16 predict programs: ksplit 0; bf16-mixed training programs: radnet_conv_bf16_pick_split of the layer) */
 enum {
   RADNET_OP_CONV_FWD = 1, RADNET_OP_CONV_DGRAD = 2, RADNET_OP_CONV_WGRAD = 3, RADNET_OP_MAXPOOL = 4, RADNET_OP_COLSUM = 5,
   RADNET_OP_WINO = 6, RADNET_OP_WINO_REUSE = 7, RADNET_OP_WINO_WGRAD = 8, RADNET_OP_SCATTER = 9, RADNET_OP_FILL0 = 10,

@@ -16,7 +16,12 @@
 //     operands are row-major [row][32 k + 8 pad] bf16 in LDS (80-byte rows), read as one ds_read_b128 per fragment.  Two
 //     LDS buffers, the global loads of tile t+1 in registers while tile t is multiplied: one barrier per K tile.
 //   * Fused epilogue as in conv_mfma.hip: per-column scale / shift, residual addend, ReLU or sigmoid on [0, act_cols).
-//   * No split K and no atomics: each output element is one workgroup's fixed-order sum, so two runs give the same bits.
+//   * Ordered K split (bf16-mixed training: small M, deep K -- radnet_conv_bf16_pick_split): blockIdx.z = slice of the K
+//     tiles.  conv_mfma.hip's in-launch protocol: every slice writes its partial tile as a write-through (sc1) slab, drains
+//     it, takes a ticket from the tile's arrival counter; the last arrival sums ALL slabs in slice order (its own read back
+//     too, with sc1 loads), so the result does not depend on arrival order, then runs the epilogue and leaves the counter
+//     at zero.  Slabs live in the context's workspace, counters in its aux block: each lane has its own.  No float atomics:
+//     two runs give the same bits.  ksplit <= 1 is the single-pass launch, unchanged.
 #include "radnet_internal.h"
 #include <hip/hip_ext.h>
 
@@ -39,6 +44,9 @@ struct Bf16Args {
   const float* scale;        // per-column scale or null
   const float* shift;        // per-column shift or null
   const float* addend;       // residual [M][ld_add] or null
+  float* partial;            // K split: slabs [tile][slice][BM*BN] (context workspace)
+  unsigned* counters;        // K split: arrival counter per output tile (context aux block, zero outside a launch)
+  int ksplit;
   int H, W, C, OW, KW, stride, pad_t, pad_l;
   int M, N, K, nkt, ldk, ldy, ld_add, act, act_cols;
   int OHOW;
@@ -64,6 +72,13 @@ __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned of
 __device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
 }
+// sc1 (aux 16): write-through store / L1-bypassing agent-coherent load, for the slabs handed to the last slice in-launch
+__device__ __forceinline__ f32x4 buf_load4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 16));
+}
+__device__ __forceinline__ void buf_store4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off, const f32x4& v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, 16);
+}
 
 // fp32 -> bf16, round to nearest, ties to even (v_cvt_pk_bf16_f32 on gfx950)
 __device__ __forceinline__ uint16_t to_bf16_bits(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
@@ -81,7 +96,7 @@ __global__ void __launch_bounds__(256) weights_to_bf16_kernel(const float* __res
   wt[i] = k < K ? to_bf16_bits(w[(long long)k * ldw + n]) : (uint16_t)0;
 }
 
-template <int BM, int BN>
+template <int BM, int BN, bool SPLIT>
 __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
   constexpr int TM = BM / 64, TN = BN / 64;          // 32x32 accumulator tiles per wave (2x2 waves)
   constexpr int AL = BM / 64, BL = BN / 64;          // 8-k chunks each thread stages per K tile (4 chunks per row)
@@ -151,12 +166,15 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  gload(0);
+  // K tiles [kt0, kt1) of this slice (ksplit <= nkt: none is empty)
+  const int kt0 = SPLIT ? (int)(((long long)g.nkt * blockIdx.z) / g.ksplit) : 0;
+  const int kt1 = SPLIT ? (int)(((long long)g.nkt * (blockIdx.z + 1)) / g.ksplit) : g.nkt;
+  gload(kt0);
   lstore(0);
   __syncthreads();
-  for (int kt = 0; kt < g.nkt; ++kt) {
-    const int cur = kt & 1;
-    gload(kt + 1 < g.nkt ? kt + 1 : kt);             // the last iteration re-loads its own tile (never stored): no branch
+  for (int kt = kt0; kt < kt1; ++kt) {
+    const int cur = (kt - kt0) & 1;
+    gload(kt + 1 < kt1 ? kt + 1 : kt);               // the last iteration re-loads its own tile (never stored): no branch
 #pragma unroll
     for (int s = 0; s < BK / 16; ++s) {
       bf16x8 af[TM], bfr[TN];
@@ -173,6 +191,55 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
     }
     lstore(cur ^ 1);
     __syncthreads();
+  }
+
+  if constexpr (SPLIT) {
+    // slab layout private to this kernel: the 16 registers of a lane's 32x32 accumulator contiguous (four 16-byte accesses)
+    __shared__ int s_last;
+    const unsigned tile_id = blockIdx.x + gridDim.x * blockIdx.y;
+    const unsigned lane_off = (unsigned)((wave * TM * TN * 64 + lane) * 16) * 4u;
+    const __amdgpu_buffer_rsrc_t rslab = make_rsrc(g.partial + ((size_t)tile_id * g.ksplit + blockIdx.z) * (BM * BN), BM * BN * 4u);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+          buf_store4_sc1(rslab, lane_off + (unsigned)(((i * TN + j) * 64 * 16 + q * 4) * 4), v);
+        }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      const unsigned ticket = __hip_atomic_fetch_add(g.counters + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int last = ticket == (unsigned)(g.ksplit - 1);
+      if (last) __hip_atomic_store(g.counters + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+      s_last = last;
+    }
+    __syncthreads();
+    if (s_last == 0) return;                         // uniform for the workgroup
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // compiler-only: keeps the slab loads below the ticket
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int s = 0; s < g.ksplit; ++s) {             // slices ADDED in slice (= k) order
+      const __amdgpu_buffer_rsrc_t rs = make_rsrc(g.partial + ((size_t)tile_id * g.ksplit + s) * (BM * BN), BM * BN * 4u);
+      f32x4 v[TM * TN * 4];
+#pragma unroll
+      for (int t = 0; t < TM * TN * 4; ++t) v[t] = buf_load4_sc1(rs, lane_off + (unsigned)(((t >> 2) * 64 * 16 + (t & 3) * 4) * 4));
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 w = v[(i * TN + j) * 4 + q];
+            acc[i][j][4 * q] += w.x; acc[i][j][4 * q + 1] += w.y; acc[i][j][4 * q + 2] += w.z; acc[i][j][4 * q + 3] += w.w;
+          }
+    }
   }
 
   // epilogue: D[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -206,11 +273,22 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
 }
 
 template <int BM, int BN>
-int launch_bf16(radnet_ctx* ctx, const Bf16Args& g) {
-  const dim3 grid(radnet_cdiv(g.M, BM), radnet_cdiv(g.N, BN));
+int launch_bf16(radnet_ctx* ctx, Bf16Args g) {
+  const dim3 grid(radnet_cdiv(g.M, BM), radnet_cdiv(g.N, BN), g.ksplit > 1 ? g.ksplit : 1);
+  if (g.ksplit > 1) {
+    const unsigned long long tiles = (unsigned long long)grid.x * grid.y;
+    if (tiles > kAuxBf16SplitCounterCount)
+      RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_fwd_bf16: %llu output tiles exceed the %zu split counters", tiles, kAuxBf16SplitCounterCount);
+    const unsigned long long need = tiles * (unsigned long long)g.ksplit * BM * BN * 4ull;
+    if (!ctx->ws || ctx->ws_bytes < need)
+      RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: K split %d needs %llu bytes of workspace (radnet_set_workspace: %llu)", g.ksplit, need,
+                  (unsigned long long)ctx->ws_bytes);
+    g.partial = (float*)ctx->ws;
+    g.counters = reinterpret_cast<unsigned*>(ctx->aux + kAuxBf16SplitCounters);
+  }
   const bool timed = ctx->timing != 0;
   if (timed) radnet_timing_arm(ctx);
-  auto kernel = conv_bf16_fwd_kernel<BM, BN>;
+  auto kernel = g.ksplit > 1 ? conv_bf16_fwd_kernel<BM, BN, true> : conv_bf16_fwd_kernel<BM, BN, false>;
   if (ctx->arm0) hipExtLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, ctx->arm0, ctx->arm1, 0, g);
   else hipLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, g);
   RADNET_CHECK_LAUNCH(ctx, "conv_bf16_fwd_kernel");
@@ -230,7 +308,30 @@ extern "C" int radnet_weights_to_bf16(radnet_ctx* ctx, const float* w, int32_t k
   return RADNET_OK;
 }
 
+// output tile of the launch: a fixed rule of (M, N) -- the largest tile that still gives every CU a workgroup (0: 128x128, 1: 128x64, 2: 64x64)
+static int bf16_tile_shape(long long M, int N, long long* tiles) {
+  const long long t128 = (long long)radnet_cdiv(M, 128) * radnet_cdiv(N, 128), t128x64 = (long long)radnet_cdiv(M, 128) * radnet_cdiv(N, 64);
+  if (N > 64 && t128 >= 256) { *tiles = t128; return 0; }
+  if (t128x64 >= 256) { *tiles = t128x64; return 1; }
+  *tiles = (long long)radnet_cdiv(M, 64) * radnet_cdiv(N, 64);
+  return 2;
+}
+
+extern "C" int32_t radnet_conv_bf16_pick_split(int64_t M, int32_t N, int32_t K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 1;
+  long long tiles = 0;
+  bf16_tile_shape(M, N, &tiles);
+  const long long nkt = (K + BK - 1) / BK;
+  int s = 1;
+  while (tiles * s < 256 && nkt >= 16ll * s && s < 16) s *= 2;      // double while short of 256 workgroups and slices keep >= 8 K tiles
+  return s;
+}
+
 extern "C" int radnet_conv_fwd_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wt, int32_t ldk) {
+  return radnet_conv_fwd_bf16_split(ctx, d, wt, ldk, 1);
+}
+
+extern "C" int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wt, int32_t ldk, int32_t ksplit) {
   if (!ctx || !d) return RADNET_ERR_ARG;
   if (!d->x || !wt || !d->y) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: null tensor");
   if (d->c % 8 != 0) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_fwd_bf16: %d input channels (needs a multiple of 8)", d->c);
@@ -257,9 +358,12 @@ extern "C" int radnet_conv_fwd_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, 
   g.magic_ohow = radnet_div_magic((uint32_t)g.OHOW); g.magic_ow = radnet_div_magic((uint32_t)d->ow);
   g.magic_c = radnet_div_magic((uint32_t)d->c); g.magic_kw = radnet_div_magic((uint32_t)d->kw);
   g.x_bytes = (unsigned)x_bytes; g.w_bytes = (unsigned)w_bytes; g.y_bytes = (unsigned)y_bytes; g.add_bytes = (unsigned)add_bytes;
-  // launch shape: a fixed rule of (M, N) -- the largest tile that still gives every CU a workgroup
-  const long long t128 = (long long)radnet_cdiv(M, 128) * radnet_cdiv(d->n, 128), t128x64 = (long long)radnet_cdiv(M, 128) * radnet_cdiv(d->n, 64);
-  if (d->n > 64 && t128 >= 256) return launch_bf16<128, 128>(ctx, g);
-  if (t128x64 >= 256) return launch_bf16<128, 64>(ctx, g);
+  if (ksplit > 64 || ksplit > g.nkt)
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: K split %d (at most 64 and the %d K tiles)", ksplit, g.nkt);
+  g.ksplit = ksplit > 1 ? ksplit : 1;
+  long long tiles = 0;
+  const int shape = bf16_tile_shape(M, d->n, &tiles);
+  if (shape == 0) return launch_bf16<128, 128>(ctx, g);
+  if (shape == 1) return launch_bf16<128, 64>(ctx, g);
   return launch_bf16<64, 64>(ctx, g);
 }

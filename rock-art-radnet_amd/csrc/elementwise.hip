@@ -441,6 +441,100 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float*
   }
 }
 
+// bf16-mixed training (radnet_adam_step_bf16): the Adam step of adam_kernel (folded shifts optional) that ALSO rewrites the bf16
+// [n][ldk] images of up to kAdamBf16Max conv kernels [k][ldw] living in the arena -- the operands the bf16 forward convs read
+// (conv_bf16.hip).  The listed kernels leave the flat sweep and go to workgroups of their own behind it (radnet_adam_step_fused's
+// layout): a workgroup owns a 64 k x 64 n tile; phase 1, every thread: the Adam update of four float4 chunks of its rows,
+// coalesced along n, new weights into LDS (zeros for rows k..ldk); phase 2: the tile transposed out of LDS, eight consecutive k
+// of one output column per thread, rounded as weights_to_bf16_kernel rounds (to nearest, ties to even) and written as one
+// 16-byte store -- coalesced along k.  Same adam_one, same conversion: bit-identical to Adam followed by radnet_weights_to_bf16.
+constexpr int kAdamBf16Max = 16;
+constexpr int kAdamBf16Tile = 64;
+struct AdamBf16 {
+  long long off4[kAdamBf16Max];   // first float4 of the layer's kernel in the arena
+  int k[kAdamBf16Max], n[kAdamBf16Max], ldw4[kAdamBf16Max], ldk[kAdamBf16Max];
+  int ntn[kAdamBf16Max];          // n tiles per k tile row: cdiv(ldw, 64)
+  int unit0[kAdamBf16Max + 1];    // first workgroup (relative to the first tile workgroup) of each layer; [n] = their total
+  uint16_t* wt[kAdamBf16Max];
+  int nl;
+  unsigned sweep_blocks;          // workgroups of the flat sweep (the tile workgroups follow)
+  // the flat sweep runs over the arena WITHOUT the listed kernels: its index j lies in gap g when pref[g] <= j < pref[g + 1] and
+  // stands for float4 gap0[g] + j - pref[g] (a sweep over the whole arena that skips the kernels spends its time skipping them)
+  long long gap0[kAdamBf16Max + 1], pref[kAdamBf16Max + 2];
+  int ngap;
+};
+__global__ void __launch_bounds__(256) adam_bf16_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long long n4, float lr_t, float b1, float b2, float eps,
+                                                        float gs, int zero_grad, long long aff_off4, long long aff_n4,
+                                                        const float* __restrict__ aff_scale, const float* __restrict__ aff_t0,
+                                                        float* __restrict__ aff_shift, AdamBf16 lz) {
+  float4* p4 = reinterpret_cast<float4*>(p);
+  float4* g4 = reinterpret_cast<float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  if (blockIdx.x >= lz.sweep_blocks) {
+    __shared__ float tile[kAdamBf16Tile][kAdamBf16Tile + 1];     // [k][n], odd pitch: the transposed reads hit 64 different banks
+    const int unit = (int)(blockIdx.x - lz.sweep_blocks);
+    int layer = 0;
+    for (int l = 1; l < lz.nl; ++l)
+      if (unit >= lz.unit0[l]) layer = l;
+    const int u = unit - lz.unit0[layer];
+    const int k0 = (u / lz.ntn[layer]) * kAdamBf16Tile, n0 = (u % lz.ntn[layer]) * kAdamBf16Tile;
+    const int K = lz.k[layer], ldw4 = lz.ldw4[layer];
+    const int c4 = threadIdx.x & 15;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int r = (threadIdx.x >> 4) + 16 * it;
+      const int kk = k0 + r, j4 = n0 / 4 + c4;
+      float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (kk < K && j4 < ldw4) {
+        const long long i = lz.off4[layer] + (long long)kk * ldw4 + j4;
+        float4 mm = m4[i], vv = v4[i];
+        pp = p4[i];
+        adam_one(pp, g4[i], mm, vv, lr_t, b1, b2, eps, gs);
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+        if (zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      tile[r][4 * c4] = pp.x; tile[r][4 * c4 + 1] = pp.y; tile[r][4 * c4 + 2] = pp.z; tile[r][4 * c4 + 3] = pp.w;
+    }
+    __syncthreads();
+    const int N = lz.n[layer], ldk = lz.ldk[layer];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int q = threadIdx.x + 256 * it;           // 64 columns x 8 chunks of 8 k
+      const int c = q >> 3, kc = (q & 7) * 8;
+      const int col = n0 + c, kk = k0 + kc;
+      if (col >= N || kk >= ldk) continue;            // ldk % 8 == 0: a chunk lies wholly inside [0, ldk) or wholly outside
+      uint16_t h[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) h[e] = kk + e < K ? __builtin_bit_cast(uint16_t, (__bf16)tile[kc + e][c]) : (uint16_t)0;
+      uint4 o;
+      o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
+      o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
+      *reinterpret_cast<uint4*>(lz.wt[layer] + (long long)col * ldk + kk) = o;
+    }
+    return;
+  }
+  const long long rest = lz.pref[lz.ngap];
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < rest; j += (long long)lz.sweep_blocks * blockDim.x) {
+    int gp = 0;
+    for (int q = 1; q < lz.ngap; ++q)
+      if (j >= lz.pref[q]) gp = q;
+    const long long i = lz.gap0[gp] + (j - lz.pref[gp]);
+    float4 pp = p4[i], mm = m4[i], vv = v4[i];
+    adam_one(pp, g4[i], mm, vv, lr_t, b1, b2, eps, gs);
+    p4[i] = pp;
+    m4[i] = mm;
+    v4[i] = vv;
+    if (zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (aff_shift != nullptr && i >= aff_off4 && i < aff_off4 + aff_n4) {
+      const long long j = i - aff_off4;
+      const float4 a = reinterpret_cast<const float4*>(aff_scale)[j], c = reinterpret_cast<const float4*>(aff_t0)[j];
+      reinterpret_cast<float4*>(aff_shift)[j] = make_float4(a.x * pp.x + c.x, a.y * pp.y + c.y, a.z * pp.z + c.z, a.w * pp.w + c.w);
+    }
+  }
+}
+
 // ---- RPN losses (losses.py:16-66) ------------------------------------------------------------------------------
 // scratch (double): [0] sum valid, [1] sum valid*ce, [2] sum mask, [3] sum mask*smoothL1
 __device__ __forceinline__ float bce_swapped_logit(float t) {
@@ -817,6 +911,62 @@ extern "C" int radnet_adam_step_fused(radnet_ctx* ctx, float* p, float* g, float
   hipLaunchKernelGGL(adam_kernel, dim3(sweep + (unsigned)wz.unit0[n_layers]), dim3(256), 0, ctx->stream, p, g, m, v, (long long)(n / 4), (float)lr_t,
                      beta1, beta2, eps, grad_scale, (int)zero_grad, (long long)(bias_off / 4), (long long)(shift ? bias_len / 4 : 0), scale, t0, shift, wz);
   RADNET_CHECK_LAUNCH(ctx, "adam_fused");
+  return RADNET_OK;
+}
+
+extern "C" int radnet_adam_step_bf16(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,
+                                     float beta2, float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len,
+                                     const float* scale, const float* t0, float* shift, const radnet_adam_bf16* layers, int32_t n_layers) {
+  if (!ctx) return RADNET_ERR_ARG;
+  if (!p || !g || !m || !v || n_layers < 0 || (n_layers > 0 && !layers)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: null tensor");
+  if (n_layers > kAdamBf16Max) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: %d layers (at most %d)", n_layers, kAdamBf16Max);
+  if (shift != nullptr && (!scale || !t0)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: shift without scale / t0");
+  if ((n % 4) || (bias_off % 4) || (bias_len % 4) || bias_off < 0 || bias_len < 0 || bias_off + bias_len > n)
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: arena length %lld, bias range [%lld, +%lld) must be multiples of 4 inside the arena", (long long)n,
+                (long long)bias_off, (long long)bias_len);
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: arenas must be 16-byte aligned");
+  if (shift && (((uintptr_t)scale | (uintptr_t)t0 | (uintptr_t)shift) & 15)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: scale / t0 / shift must be 16-byte aligned");
+  if (t < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam: step counter starts at 1");
+  AdamBf16 lz{};
+  lz.nl = n_layers;
+  long long in_layers = 0;
+  for (int l = 0; l < n_layers; ++l) {
+    const radnet_adam_bf16& d = layers[l];
+    if (!d.wt || d.k <= 0 || d.n <= 0 || d.ldw < d.n || (d.ldw & 3) || (d.off & 3) || d.ldk < d.k || (d.ldk & 7) || ((uintptr_t)d.wt & 15) ||
+        d.k >= (1 << 24) || d.ldk >= (1 << 24) || d.ldw >= (1 << 20))
+      RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layer %d (k %d, n %d, ldw %d, ldk %d): needs ldw >= n, ldk >= k, ldw %% 4 == 0, ldk %% 8 == 0, "
+                  "offset %% 4 == 0, a 16-byte aligned image", l, d.k, d.n, d.ldw, d.ldk);
+    const int64_t len = (int64_t)d.k * d.ldw;
+    if (d.off < 0 || d.off + len > n) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layer %d [%lld, +%lld) lies outside the arena", l, (long long)d.off, (long long)len);
+    if (shift && bias_len > 0 && d.off < bias_off + bias_len && bias_off < d.off + len) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layer %d overlaps the bias range", l);
+    for (int k = 0; k < l; ++k)
+      if (d.off < layers[k].off + (int64_t)layers[k].k * layers[k].ldw && layers[k].off < d.off + len) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layers %d and %d overlap", k, l);
+    lz.off4[l] = d.off / 4;
+    lz.k[l] = d.k; lz.n[l] = d.n; lz.ldw4[l] = d.ldw / 4; lz.ldk[l] = d.ldk; lz.wt[l] = d.wt;
+    lz.ntn[l] = radnet_cdiv(d.ldw, kAdamBf16Tile);
+    const int units = radnet_cdiv(std::max(d.k, d.ldk), kAdamBf16Tile) * lz.ntn[l];
+    lz.unit0[l + 1] = lz.unit0[l] + units;
+    in_layers += len / 4;
+  }
+  // gaps between the listed kernels, in arena order
+  int order[kAdamBf16Max];
+  for (int l = 0; l < n_layers; ++l) order[l] = l;
+  std::sort(order, order + n_layers, [&](int a, int b) { return layers[a].off < layers[b].off; });
+  long long at4 = 0;
+  for (int q = 0; q <= n_layers; ++q) {
+    const long long end4 = q < n_layers ? layers[order[q]].off / 4 : n / 4;
+    lz.gap0[lz.ngap] = at4;
+    lz.pref[lz.ngap + 1] = lz.pref[lz.ngap] + (end4 - at4);
+    ++lz.ngap;
+    if (q < n_layers) at4 = end4 + (long long)layers[order[q]].k * layers[order[q]].ldw / 4;
+  }
+  const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t));
+  const unsigned sweep = (unsigned)grid_for(std::max<long long>(n / 4 - in_layers, 1), 256, 8192);
+  lz.sweep_blocks = sweep;
+  hipLaunchKernelGGL(adam_bf16_kernel, dim3(sweep + (unsigned)lz.unit0[n_layers]), dim3(256), 0, ctx->stream, p, g, m, v, (long long)(n / 4),
+                     (float)lr_t, beta1, beta2, eps, grad_scale, (int)zero_grad, (long long)(bias_off / 4), (long long)(shift ? bias_len / 4 : 0), scale,
+                     t0, shift, lz);
+  RADNET_CHECK_LAUNCH(ctx, "adam_bf16");
   return RADNET_OK;
 }
 

@@ -115,7 +115,9 @@ constexpr size_t kAuxLossBlocks = 1024;
 constexpr size_t kAuxColsumScratch = kAuxLossPartials + kAuxLossBlocks * 4 * 8;           // kAuxColsumRows x 65536 floats
 constexpr size_t kAuxColsumRows = 32;
 constexpr size_t kAuxColsumCols = 65536;
-constexpr size_t kAuxBytes = kAuxColsumScratch + kAuxColsumRows * kAuxColsumCols * 4;
+constexpr size_t kAuxBf16SplitCounters = kAuxColsumScratch + kAuxColsumRows * kAuxColsumCols * 4;   // 8192 x u32: one per output tile of a
+constexpr size_t kAuxBf16SplitCounterCount = 8192;                                                  // K-split bf16 forward launch
+constexpr size_t kAuxBytes = kAuxBf16SplitCounters + kAuxBf16SplitCounterCount * 4;
 
 #define RADNET_FAIL(ctx, code, ...)                         \
   do {                                                      \

@@ -287,11 +287,16 @@ def build_models(C, device_index=0, weights=None, lr=5e-5, bce_mode=None, worklo
     """The four model objects of train.py:199-211 / RADNet.py:748-770 over one shared engine.
     Returns (model_rpn [2 outputs], model_classifier, model_all, model_rpn_predict [3 outputs], model_detector).
     precision="bf16": inference-only models whose convolutions run on bf16 matrix cores with fp32 accumulation (ResNet50 only;
-    the training calls raise RuntimeError)."""
+    the training calls raise RuntimeError).
+    precision="bf16-mixed": trainable models whose forward convolutions run on bf16 matrix cores with fp32 accumulation; the
+    backward and Adam stay fp32 on fp32 master weights, which save_weights / load_weights read and write (ResNet50 only, not the
+    cont_train.py workload)."""
     from . import losses
-    if precision not in ("fp32", "bf16"):
-        raise ValueError("precision must be 'fp32' or 'bf16', not %r" % (precision,))
-    if precision == "bf16" and C.network != "resnet50":
-        raise NotImplementedError("precision='bf16' is implemented for the ResNet50 network only (not %r)" % (C.network,))
+    if precision not in ("fp32", "bf16", "bf16-mixed"):
+        raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-mixed', not %r" % (precision,))
+    if precision != "fp32" and C.network != "resnet50":
+        raise NotImplementedError("precision=%r is implemented for the ResNet50 network only (not %r)" % (precision, C.network))
+    if precision == "bf16-mixed" and workload == "cont":
+        raise NotImplementedError("precision='bf16-mixed' is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)")
     s = _Shared(C, device_index, weights, lr, losses.BCE_MODE if bce_mode is None else bce_mode, workload, precision)
     return RPNModel(s), ClassifierModel(s), AllModel(s), RPNModel(s, with_features=True), DetectorModel(s)

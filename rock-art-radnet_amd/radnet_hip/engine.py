@@ -25,6 +25,7 @@ from . import lib as L
 BN_EPS = 1e-3        # FixedBatchNormalization.py:8
 RES_STAGES = ((2, "abc", (64, 64, 256), 1), (3, "abcd", (128, 128, 512), 2), (4, "abcdef", (256, 256, 1024), 2))
 HEAD_STAGE = (5, "abc", (512, 512, 2048), 2)
+PRECISIONS = ("fp32", "bf16", "bf16-mixed")     # FasterRCNNEngine(precision=...): see __init__
 RPN_LD = 64          # fused RPN head GEMM width (A + 4A = 60 for 12 anchors, padded)
 
 
@@ -134,13 +135,19 @@ class FasterRCNNEngine:
 
     def __init__(self, C_cfg, device_index=0, n_classes=None, bce_mode=0, lr=5e-5, autotune=True, workload=None, precision="fp32"):
         # "bf16": inference only -- every conv with a multiple of 8 input channels runs on bf16 matrix cores (fp32 accumulation,
-        # csrc/conv_bf16.hip) on bf16 copies of the weights; training entry points refuse such an engine
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision must be 'fp32' or 'bf16', not %r" % (precision,))
-        if precision == "bf16" and (self.NETWORK != "resnet50" or C_cfg.network != "resnet50"):
-            raise NotImplementedError("precision='bf16' is implemented for the ResNet50 network only (not %r)" % (C_cfg.network,))
+        # csrc/conv_bf16.hip) on bf16 copies of the weights; training entry points refuse such an engine.
+        # "bf16-mixed": trainable -- the same forward convs in every training, validation and predict program, with the K split of
+        # radnet_conv_bf16_pick_split; backward and Adam stay fp32 on the fp32 master weights, and Adam rewrites the bf16 images of
+        # the trainable convs in its own launch (radnet_adam_step_bf16)
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-mixed', not %r" % (precision,))
+        if precision != "fp32" and (self.NETWORK != "resnet50" or C_cfg.network != "resnet50"):
+            raise NotImplementedError("precision=%r is implemented for the ResNet50 network only (not %r)" % (precision, C_cfg.network))
+        if precision == "bf16-mixed" and (workload or self.WORKLOAD) == "cont":
+            raise NotImplementedError("precision='bf16-mixed' is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)")
         self.precision = precision
         self._bf16_w = {}              # fp32 weight pointer -> (bf16 copy [N][ldk], ldk, conv layer, N)
+        self._bf16_arena_layers = {}   # id(arena) -> (radnet_adam_bf16[], n): the bf16 images Adam rewrites for that arena
         self.workload = workload or self.WORKLOAD
         self.TUNED_PREFIX = "%s_%s_" % (self.workload, self.NETWORK)
         if C_cfg.network != self.NETWORK:
@@ -185,7 +192,7 @@ class FasterRCNNEngine:
         # 256 by default: the chain's static deal needs every workgroup of every concurrently running chain resident, and the
         # pipelined step runs two of them (prefetch lanes) beside the RPN and classifier lanes' launches (1 024 slots on the chip)
         self.chain_wgs = int(os.environ.get("RADNET_CHAIN_WGS", "256"))
-        if precision == "bf16":        # the paired, bottleneck and chain launches are fp32 kernels: bf16 programs hold plain ops
+        if precision != "fp32":        # the paired, bottleneck and chain launches are fp32 kernels: bf16 programs hold plain ops
             self.use_chain = self.fwd_pair = self.bneck_fuse = self.head_train_wino = False
         self._chain_plans = []     # plans whose base forward is a chain launch: check_chains() reads their sticky error words
         self.wino_wgrad = os.environ.get("RADNET_NO_WINOGRAD_WGRAD", "0") != "1"
@@ -447,7 +454,7 @@ class FasterRCNNEngine:
     INFERENCE_WINOGRAD_LAYERS = tuple("res5%s_branch2b" % b for b in "abc")
 
     def _uses_winograd(self, c, inference=False):
-        if getattr(self, "precision", "fp32") == "bf16":
+        if getattr(self, "precision", "fp32") != "fp32":
             return False               # bf16 mode: every 3x3 conv in the direct form (the F(4x4) transforms amplify the rounding)
         listed = c.name in self.WINOGRAD_LAYERS or ((inference or getattr(self, "head_train_wino", False)) and c.name in self.INFERENCE_WINOGRAD_LAYERS
                                                     and os.environ.get("RADNET_NO_INFERENCE_WINOGRAD", "0") != "1")
@@ -476,10 +483,10 @@ class FasterRCNNEngine:
                 c.wino_u = torch.empty((c.wino_m + 2) ** 2, c.cin, c.cout, dtype=torch.float32, device=self.dev)
             self.ctx.call("radnet_winograd4_filter" if c.wino_m == 4 else "radnet_winograd_filter", c.weight, c.cin, c.cout, c.ldw, c.wino_u)
 
-    # ------------------------------------------------------------------------------------------ bf16 inference mode
+    # ------------------------------------------------------------------------------------------ bf16 inference / bf16-mixed modes
     def check_trainable(self, what):
-        """Training entry points call this: a bf16 engine is an inference engine."""
-        if getattr(self, "precision", "fp32") != "fp32":
+        """Training entry points call this: a bf16 engine is an inference engine (fp32 and bf16-mixed engines train)."""
+        if getattr(self, "precision", "fp32") == "bf16":
             raise RuntimeError("%s: this engine was built with precision=%r, which is inference only; build an fp32 engine to train"
                                % (what, self.precision))
 
@@ -501,10 +508,36 @@ class FasterRCNNEngine:
         for wt, ldk, c, n in self._bf16_w.values():
             self.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, n, c.ldw, wt, ldk)
 
+    def _adam_bf16_layers(self, arena):
+        """bf16-mixed: (radnet_adam_bf16[], n) -- the registry of the bf16 images whose fp32 masters live in `arena` (rpn_conv1 and
+        rpn_heads in the RPN arena, the ten stage-5 convs in the head arena), made on first use together with any image not made yet.
+        Adam #1 and the RPN forwards run on the main lane, Adam #2 and the classifier forward on the head lane: each image is written
+        and read on one lane.  The frozen base's images are written once per weight load (set_weights)."""
+        ent = self._bf16_arena_layers.get(id(arena))
+        if ent is None:
+            lo, hi = arena.p.data_ptr(), arena.p.data_ptr() + 4 * arena.n
+            rows = []
+            for c in self.convs.values():
+                if c.weight is not None and c.cin % 8 == 0 and lo <= c.weight.data_ptr() < hi:
+                    wt, ldk, _, n = self._bf16_weights(c)
+                    rows.append(((c.weight.data_ptr() - lo) // 4, c.kh * c.kh * c.cin, n, c.ldw, wt.data_ptr(), ldk))
+            arr = (L.AdamBf16 * max(len(rows), 1))()
+            for k, (off, kk, n, ldw, wt, ldk) in enumerate(rows):
+                arr[k].off, arr[k].k, arr[k].n, arr[k].ldw, arr[k].wt, arr[k].ldk = off, kk, n, ldw, wt, ldk
+            ent = (arr, len(rows))
+            self._bf16_arena_layers[id(arena)] = ent
+        return ent
+
+    def _bf16_split(self, d):
+        """K slices of a bf16 forward launch: radnet_conv_bf16_pick_split in bf16-mixed engines, one pass in bf16 inference engines."""
+        if getattr(self, "precision", "fp32") != "bf16-mixed":
+            return 0
+        return int(self.lib.radnet_conv_bf16_pick_split(d.nb * d.oh * d.ow, d.n, d.kh * d.kw * d.c))
+
     def _bf16_ops(self, ops):
-        """bf16 mode: every direct forward conv whose input has a multiple of 8 channels -> ("conv_bf16", desc); the 4-channel stem
-        stays fp32.  fp32 mode: `ops` unchanged."""
-        if getattr(self, "precision", "fp32") != "bf16":
+        """bf16 / bf16-mixed modes: every direct forward conv whose input has a multiple of 8 channels -> ("conv_bf16", desc); the
+        4-channel stem stays fp32.  fp32 mode: `ops` unchanged."""
+        if getattr(self, "precision", "fp32") == "fp32":
             return ops
         by_ptr = {c.weight.data_ptr(): c for c in self.convs.values()}
         out = []
@@ -817,11 +850,11 @@ class FasterRCNNEngine:
             elif kind in ("bneck_second", "bneck_third"):
                 o.kind = L.OP_NOP
                 o.conv = p
-            elif kind == "conv_bf16":              # bf16 inference mode: the layer's bf16 weight copy rides in p[0] / i[0]
+            elif kind == "conv_bf16":              # bf16 modes: the layer's bf16 weight copy rides in p[0] / i[0], the K split in i[1]
                 wt, ldk, _, _ = self._bf16_w[p.w]
                 o.kind = L.OP_CONV_FWD_BF16
                 o.conv = p
-                o.p[0], o.i[0] = wt.data_ptr(), ldk
+                o.p[0], o.i[0], o.i[1] = wt.data_ptr(), ldk, self._bf16_split(p)
             elif kind in ("conv", "dgrad", "wgrad"):
                 o.kind = {"conv": L.OP_CONV_FWD, "dgrad": L.OP_CONV_DGRAD, "wgrad": L.OP_CONV_WGRAD}[kind]
                 o.conv = p
@@ -1114,6 +1147,18 @@ class FasterRCNNEngine:
         fused = (is_head and getattr(self, "head_bias_len", 0) > 0 and self.head_bias_off % 4 == 0
                  and self.head_bias_len % 4 == 0 and os.environ.get("RADNET_NO_ADAM_AFFINE", "0") != "1")
         wino = self._head_adam_wino() if is_head and getattr(self, "head_train_wino", False) else None
+        if getattr(self, "precision", "fp32") == "bf16-mixed":
+            # Adam (+ the folded shifts on the head arena) and the bf16 images of the arena's convs, one launch
+            arr, n_l = self._adam_bf16_layers(arena)
+            self.ctx.check(self.lib.radnet_adam_step_bf16(
+                self.ctx.h, arena.p.data_ptr(), arena.g.data_ptr(), arena.m.data_ptr(), arena.v.data_ptr(), C.c_int64(arena.n), arena.t, C.c_float(self.lr),
+                C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1 if zero_grad else 0,
+                C.c_int64(self.head_bias_off if fused else 0), C.c_int64(self.head_bias_len if fused else 0),
+                self.head_scale.data_ptr() if fused else None, self.head_t0.data_ptr() if fused else None, self.head_shift.data_ptr() if fused else None,
+                arr, n_l), "radnet_adam_step_bf16")
+            if fused:
+                self._head_shift_fresh = True
+            return
         if wino is not None:      # Adam #2 + folded shifts + the Winograd filters of the classifier's 3x3 convs, one launch
             arr, n_l = wino
             self.ctx.check(self.lib.radnet_adam_step_fused(
@@ -1251,8 +1296,8 @@ class FasterRCNNEngine:
         y1, y2 = buf(R, self.nc), buf(R, 2 * self.nreg)
         tail_scratch = torch.zeros(int(self.lib.radnet_head_tail_scratch_bytes(R)), dtype=torch.uint8, device=dev)
         keep.append(tail_scratch)
+        fwd = self._bf16_ops(fwd)
         if not training:
-            fwd = self._bf16_ops(fwd)
             plan = dict(R=R, rois=rois, pooled=pooled, fwd=fwd, blocks=blocks, y5=cur, hw=h * w, M=M, feat=feat, pcls=pcls, pregr=pregr,
                         F=F, fh=fh, fw=fw, keep=keep, groups=groups, tail_scratch=tail_scratch)
             self._plans[key] = plan

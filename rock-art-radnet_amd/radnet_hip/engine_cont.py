@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .engine import RES_STAGES, Arena, FasterRCNNEngine
+from .engine import PRECISIONS, RES_STAGES, Arena, FasterRCNNEngine
 
 
 class ContEngine(FasterRCNNEngine):
@@ -35,7 +35,12 @@ class ContEngine(FasterRCNNEngine):
     # launches + a column sum + the unpaired data gradient against one paired launch per layer -- off unless RADNET_CONT_WINO_WGRAD=1
     S34_WINO_WGRAD = os.environ.get("RADNET_CONT_WINO_WGRAD", "0") == "1"
 
-    def __init__(self, C_cfg, device_index=0, n_classes=None, bce_mode=0, lr=2e-5, autotune=True):
+    def __init__(self, C_cfg, device_index=0, n_classes=None, bce_mode=0, lr=2e-5, autotune=True, precision="fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-mixed', not %r" % (precision,))
+        if precision != "fp32":
+            raise NotImplementedError("precision=%r is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)"
+                                      % (precision,))
         super().__init__(C_cfg, device_index, n_classes, bce_mode, lr, autotune)
 
     # ------------------------------------------------------------------------------------------ layers

@@ -89,6 +89,11 @@ class AdamWino(C.Structure):
     _fields_ = [("off", C.c_int64), ("c", C.c_int32), ("n", C.c_int32), ("u", C.c_void_p)]
 
 
+class AdamBf16(C.Structure):
+    """Mirror of `radnet_adam_bf16`: a conv kernel [k][ldw] inside an optimizer arena and its bf16 image [n][ldk] (bf16-mixed training)."""
+    _fields_ = [("off", C.c_int64), ("k", C.c_int32), ("n", C.c_int32), ("ldw", C.c_int32), ("wt", C.c_void_p), ("ldk", C.c_int32)]
+
+
 class TrainDesc(C.Structure):
     """Mirror of `radnet_train_desc` (field order is the header's)."""
     _d, _i, _vp = C.c_double, C.c_int32, C.c_void_p
@@ -160,6 +165,8 @@ def load_library():
         "radnet_timing_reset": (C.c_int, [vp]),
         "radnet_conv_fwd": (C.c_int, [vp, C.POINTER(ConvDesc)]),
         "radnet_conv_fwd_bf16": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32]),
+        "radnet_conv_fwd_bf16_split": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32, i32]),
+        "radnet_conv_bf16_pick_split": (i32, [C.c_int64, i32, i32]),
         "radnet_weights_to_bf16": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
         "radnet_conv_dgrad": (C.c_int, [vp, C.POINTER(ConvDesc)]),
         "radnet_gemm_batched": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32]),
@@ -176,6 +183,8 @@ def load_library():
         "radnet_winograd4_filter_grad": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
         "radnet_adam_step_fused": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32,
                                             C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(AdamWino), i32]),
+        "radnet_adam_step_bf16": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32,
+                                           C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(AdamBf16), i32]),
         "radnet_conv_wgrad": (C.c_int, [vp, C.POINTER(ConvDesc)]),
         "radnet_conv_bwd": (C.c_int, [vp, C.POINTER(ConvDesc)]),
         "radnet_conv_fwd_pair": (C.c_int, [vp, C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),

@@ -70,6 +70,9 @@ class NativeTrainStep:
     engine.select_samples)."""
 
     def __init__(self, eng, world=1):
+        if getattr(eng, "precision", "fp32") == "bf16-mixed":
+            raise NotImplementedError("NativeTrainStep: precision='bf16-mixed' is not implemented for radnet_train_step "
+                                      "(radnet_train_desc has no bf16 images); use TrainStep")
         if getattr(eng, "precision", "fp32") != "fp32":
             eng.check_trainable("NativeTrainStep")
         self.eng = eng
