@@ -208,6 +208,50 @@ int radnet_conv_fwd_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint1
 int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wt, int32_t ldk, int32_t ksplit);
 int32_t radnet_conv_bf16_pick_split(int64_t m, int32_t n, int32_t k);
 
+/* ---- convolution backward on bf16 matrix cores (csrc/conv_bf16_bwd.hip; engine precision "bf16-train") ---------------
+ * The backward semantics of radnet_conv_dgrad / radnet_conv_wgrad with bf16 operands and fp32 accumulation.  With
+ * g[m][n] = dy[m][n] * gscale[n] computed as ONE fp32 multiply (g = dy when gscale is 0) and bf16() as above:
+ *   dgrad :  dx[p][c] = mask( (sum_{kh,kw,n} bf16(g)[q(p,kh,kw)][n] * bf16(w)[(kh,kw,c)][n]) + dx_add[p][c] ), stride 1 only;
+ *            dx_add and the dx_mask > 0 test are fp32, in the epilogue
+ *   wgrad :  dw[k][n] (+)= sum_m bf16(im2col(x))[m][k] * bf16(g)[m][n], any stride / padding / kernel size radnet_conv_wgrad takes;
+ *            dw_accumulate 0 overwrites, 1 and 2 add the sum ONCE to what dw holds (2: the zeros the caller wrote);
+ *            d->db set: the bias gradient is radnet_colsum of the UNROUNDED dy * gscale (exact fp32, added in index order)
+ * Activations and gradients stay fp32 in memory and are rounded on their way to the matrix cores.  bf16 has fp32's exponent
+ * range: there is no loss scaling (dy * 2^-40 gives dw * 2^-40 and dx * 2^-40 bit for bit while nothing is subnormal).
+ * No float atomics: a split of the reduction is radnet_conv_fwd_bf16_split's ordered in-launch protocol (slabs in the context
+ * workspace, arrival counters in the context's aux block, the last arrival adds ALL slices in slice order), so two runs and
+ * two contexts give the same bits.  A split whose slabs (output size x slices, rounded up to whole tiles) do not fit the
+ * workspace, or whose output has more than 8192 tiles, is halved until it does -- by that rule, never by a timer; the launch shape
+ * is radnet_conv_fwd_bf16's fixed rule on (output rows, output columns).  split <= 1: one pass.
+ *
+ * radnet_weights_to_bf16_dgrad: the dgrad image of a conv kernel w [taps*c][ldw] (taps = kh*kw):
+ *   wd[i][t*n8 + j] = bf16(w[t*c + i][j]) for i < c, t < taps, j < n;  0 for every other element of wd [c][ldkd];
+ *   n8 = n rounded up to 8, ldkd >= taps*n8 rounded up to 32, a multiple of 8; wd 16-byte aligned.  8 consecutive n of one
+ *   (tap, c) are 16 contiguous bytes: the B fragment of the dgrad's MFMA.  Same rounding as radnet_weights_to_bf16.
+ * radnet_weights_to_bf16_dgrad_arena: the same for up to 16 kernels that live in one optimizer arena p [n_arena] -- ONE launch
+ *   over the registry, issued after the arena's Adam step (radnet_adam_step_bf16 keeps its signature and its 16-layer cap).
+ * radnet_conv_dgrad_bf16: d->w / d->ldw are ignored; wd / ldkd are the layer's dgrad image.  Needs stride 1, n and ld_dy multiples
+ *   of 4 with ld_dy >= n rounded up to 8 (columns >= n of dy are read but contribute zero: rpn_heads has 60 live columns in a
+ *   pitch of 64), 16-byte aligned dy / gscale / wd; RADNET_ERR_UNSUPPORTED otherwise, nothing launched.
+ * radnet_conv_wgrad_bf16: needs c and n multiples of 8, ld_dy a multiple of 4, 16-byte aligned x / dy / gscale;
+ *   RADNET_ERR_UNSUPPORTED otherwise, nothing launched.  msplit slices of the M = nb*oh*ow pixels.
+ * radnet_dgrad_bf16_pick_split(P = nb*h*w, c, kd = kh*kw*n8) / radnet_wgrad_bf16_pick_split(M, n, K = kh*kw*c): the splits the
+ *   bf16-train engine uses -- radnet_conv_bf16_pick_split's rule on (output rows, output columns, reduction length): the smallest
+ *   power of two (at most 16) that gives >= 256 workgroups, doubled only while every slice keeps >= 8 reduction tiles of 32. */
+typedef struct radnet_bf16_dgrad_image {
+  int64_t off;           /* float offset of the kernel [taps*c][ldw] in the arena */
+  int32_t taps, c, n, ldw;
+  uint16_t* wd;          /* dgrad image [c][ldkd] */
+  int32_t ldkd;
+} radnet_bf16_dgrad_image;
+int radnet_weights_to_bf16_dgrad(radnet_ctx* ctx, const float* w, int32_t taps, int32_t c, int32_t n, int32_t ldw, uint16_t* wd, int32_t ldkd);
+int radnet_weights_to_bf16_dgrad_arena(radnet_ctx* ctx, const float* p, int64_t n_arena, const radnet_bf16_dgrad_image* layers, int32_t n_layers);
+int radnet_conv_dgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wd, int32_t ldkd);
+int radnet_conv_dgrad_bf16_split(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wd, int32_t ldkd, int32_t ksplit);
+int radnet_conv_wgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, int32_t msplit);
+int32_t radnet_dgrad_bf16_pick_split(int64_t p, int32_t c, int32_t kd);
+int32_t radnet_wgrad_bf16_pick_split(int64_t m, int32_t n, int32_t k);
+
 /* out[n] (+)= sum_m g[m][n] * gscale[n]   (bias gradients) */
 int radnet_colsum(radnet_ctx* ctx, const float* g, int32_t m, int32_t n, int32_t ld, const float* gscale,
                   float* out, int32_t accumulate);
@@ -414,12 +458,15 @@ int radnet_relu_mask(radnet_ctx* ctx, float* g, const float* act, int64_t n);
  *   ROI_BWD      p: dy, rois, dfmap          i: h, w, c, r, ps
  *   CHAIN        p: radnet_chain*             (radnet_chain_run: a run of CONV_FWD / WINO ops as one persistent launch)
  *   CONV_FWD_BF16 conv, p[0] = wt (bf16 weights), i[0] = ldk, i[1] = ksplit (0 or 1: one pass; radnet_conv_fwd_bf16_split)
- *                (bf16 predict programs: ksplit 0; bf16-mixed training programs: radnet_conv_bf16_pick_split of the layer) */
+ *                (bf16 predict programs: ksplit 0; bf16-mixed training programs: radnet_conv_bf16_pick_split of the layer)
+ *   CONV_DGRAD_BF16 conv, p[0] = wd (the layer's dgrad image), i[0] = ldkd, i[1] = ksplit (radnet_conv_dgrad_bf16_split)
+ *   CONV_WGRAD_BF16 conv, i[1] = msplit (radnet_conv_wgrad_bf16)
+ *                (bf16-train training programs: radnet_dgrad_bf16_pick_split / radnet_wgrad_bf16_pick_split of the layer) */
 enum {
   RADNET_OP_CONV_FWD = 1, RADNET_OP_CONV_DGRAD = 2, RADNET_OP_CONV_WGRAD = 3, RADNET_OP_MAXPOOL = 4, RADNET_OP_COLSUM = 5,
   RADNET_OP_WINO = 6, RADNET_OP_WINO_REUSE = 7, RADNET_OP_WINO_WGRAD = 8, RADNET_OP_SCATTER = 9, RADNET_OP_FILL0 = 10,
   RADNET_OP_RELU_MASK = 11, RADNET_OP_ROI_BWD = 12, RADNET_OP_CONV_BWD = 13, RADNET_OP_CHAIN = 14, RADNET_OP_CONV_FWD_PAIR = 15,
-  RADNET_OP_CONV_BNECK = 16, RADNET_OP_CONV_FWD_BF16 = 17,
+  RADNET_OP_CONV_BNECK = 16, RADNET_OP_CONV_FWD_BF16 = 17, RADNET_OP_CONV_DGRAD_BF16 = 18, RADNET_OP_CONV_WGRAD_BF16 = 19,
   RADNET_OP_NOP = 0
 };
 typedef struct radnet_op {

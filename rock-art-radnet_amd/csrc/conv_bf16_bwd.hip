@@ -1,0 +1,549 @@
+// Convolution backward on the gfx950 bf16 matrix cores (v_mfma_f32_32x32x16_bf16), fp32 accumulation: the data gradient and the
+// weight gradient of the layers conv_bf16.hip runs forward (engine precision "bf16-train").
+//
+// With g[m][n] = dy[m][n] * gscale[n] as ONE fp32 multiply (g = dy without gscale) and bf16() = round to nearest, ties to even:
+//   dgrad  dx[p][c] = mask( (sum_{ky,kx,n} bf16(g)[q(p,ky,kx)][n] * bf16(w)[(ky,kx,c)][n]) + dx_add[p][c] )      stride 1
+//   wgrad  dw[k][n] (+)= sum_m bf16(im2col(x))[m][k] * bf16(g)[m][n]
+// Both are ONE kernel template: an output tile of rows x cols, a reduction in 32-deep tiles, conv_bf16.hip's 2x2 waves, its two
+// LDS buffers of [row][32 + 8] bf16 and its ordered in-launch split of the reduction.  They differ in what a row, a column and
+// the reduction are, i.e. in the gather and the epilogue:
+//   * dgrad: rows = input pixels p, columns = input channels c, reduction = (tap, n), n innermost.  The A tile is gathered from
+//     dy like the forward gathers x (8 consecutive n of one tap as two 16-byte buffer loads, out-of-range offset for taps that
+//     fall off the output grid, ragged rows and the reduction's padding), multiplied by gscale and rounded on its way to LDS.
+//     The B tile comes from a second bf16 image of the weights in the dgrad layout wd[c][ldkd] (radnet_weights_to_bf16_dgrad):
+//     element tap * n8 + j of row c is bf16(w[(tap, c)][j]), n8 = n rounded up to 8, zero for j >= n and past taps * n8 -- 8
+//     consecutive n of one (tap, c) are one 16-byte load.  Columns j >= n of dy are zeroed in the gather (rpn_heads: 60 of 64).
+//   * wgrad: rows = k = (tap, c), columns = n, reduction = output pixels m -- the dimension that is contiguous in NEITHER operand
+//     (x is [pixel][c], dy is [m][n]).  Both tiles are transposed ON THE LDS WRITE: a thread loads 8 consecutive channels of one
+//     pixel (two 16-byte loads), rounds them and writes them as eight 2-byte stores into eight LDS rows at column m; the MFMA
+//     fragments are then the same 16-byte row reads as everywhere else.  Lanes of a wave hold 32 consecutive m of two channel
+//     groups, so the eight stores of a wave spread over 32 banks.  im2col (3x3 padding, stride 2) is the forward's
+//     out-of-range-offset gather with the tap fixed per thread and the pixel moving.
+//   * Split of the reduction (blockIdx.z): conv_bf16.hip's protocol -- sc1 slabs in the context workspace, one arrival counter per
+//     output tile in the aux block (the forward's counters: launches of one context are ordered), the last arrival sums ALL slabs
+//     in slice order and leaves the counter at zero.  No float atomics.
+#include "radnet_internal.h"
+#include <hip/hip_ext.h>
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int BK = 32;          // reduction depth per LDS tile (two MFMA steps of 16)
+constexpr int LDSROW = BK + 8;  // bf16 per LDS row: 80 bytes
+constexpr int NTHREADS = 256;
+constexpr unsigned kOOB = 0x80000000u;   // every descriptor covers < 2 GiB (checked by the launchers)
+constexpr int MODE_DGRAD = 0, MODE_WGRAD = 1;
+
+struct BwdArgs {
+  const float* x;            // wgrad: forward input NHWC
+  const float* dy;           // [M][ld_dy]
+  const float* gscale;       // per-output-channel factor on dy or null
+  const uint16_t* wd;        // dgrad: bf16 weights in the dgrad layout [C][ldk]
+  float* out;                // dgrad: dx [P][ld_out]; wgrad: dw [K][ld_out]
+  const float* add;          // dgrad: dx_add or null; wgrad: dw itself when accumulating, else null
+  const float* mask;         // dgrad: dx_mask or null
+  float* partial;            // split: slabs [tile][slice][BM*BN] (context workspace)
+  unsigned* counters;        // split: arrival counter per output tile (context aux block, zero outside a launch)
+  int split;
+  int H, W, C, OH, OW, KW, stride, pad_t, pad_l;      // the FORWARD convolution's geometry
+  int rows, cols, nrt;       // output tile grid extents, number of 32-deep reduction tiles
+  int N, n8, red, ldk;       // forward output channels; dgrad: n rounded up to 8, taps * n8, pitch of wd
+  int M;                     // forward output pixels nb*oh*ow
+  int ld_dy, ld_out, ld_add, ld_mask;
+  int HW, OHOW;
+  unsigned long long magic_hw, magic_w, magic_ohow, magic_ow, magic_c, magic_kw, magic_n8;
+  unsigned x_bytes, dy_bytes, w_bytes, out_bytes, add_bytes, mask_bytes;
+};
+
+__device__ __forceinline__ int div_magic(int m, unsigned long long magic) {
+  return (int)(((unsigned long long)(unsigned)m * magic) >> 40);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+}
+__device__ __forceinline__ u32x4 buf_load4u(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+}
+__device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
+}
+__device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
+}
+// sc1 (aux 16): write-through store / L1-bypassing agent-coherent load, for the slabs handed to the last slice in-launch
+__device__ __forceinline__ f32x4 buf_load4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 16));
+}
+__device__ __forceinline__ void buf_store4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off, const f32x4& v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, 16);
+}
+
+// fp32 -> bf16, round to nearest, ties to even (v_cvt_pk_bf16_f32 on gfx950)
+__device__ __forceinline__ uint16_t to_bf16_bits(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
+__device__ __forceinline__ u32x4 pack8_bf16(const f32x4& lo, const f32x4& hi) {
+  const bf16x8 b = {(__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w, (__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w};
+  return __builtin_bit_cast(u32x4, b);
+}
+
+// ---- dgrad images of the weights -------------------------------------------------------------------------------------------
+struct DgradImage {
+  const float* w;            // [taps*c][ldw] fp32
+  uint16_t* wd;              // [c][ldkd] bf16 bits
+  int taps, c, n, ldw, ldkd, n8;
+};
+struct DgradImages {
+  DgradImage l[16];
+};
+
+// wd[cc][tap * n8 + j] = bf16(w[(tap, cc)][j]) for tap < taps, j < n; 0 elsewhere.  blockIdx.y = layer of the registry.
+__global__ void __launch_bounds__(256) weights_to_bf16_dgrad_kernel(DgradImages L) {
+  const DgradImage g = L.l[blockIdx.y];
+  const long long total = (long long)g.c * g.ldkd;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int cc = (int)(i / g.ldkd), kd = (int)(i - (long long)cc * g.ldkd);
+    const int tap = kd / g.n8, j = kd - tap * g.n8;
+    g.wd[i] = (tap < g.taps && j < g.n) ? to_bf16_bits(g.w[((long long)tap * g.c + cc) * g.ldw + j]) : (uint16_t)0;
+  }
+}
+
+// ---- the kernel ------------------------------------------------------------------------------------------------------------
+template <int BM, int BN, int MODE, bool SPLIT>
+__global__ void __launch_bounds__(NTHREADS) conv_bf16_bwd_kernel(BwdArgs g) {
+  constexpr int TM = BM / 64, TN = BN / 64;          // 32x32 accumulator tiles per wave (2x2 waves)
+  constexpr int AL = BM / 64, BL = BN / 64;          // 8-element chunks each thread stages per reduction tile and operand
+  __shared__ __attribute__((aligned(16))) uint16_t sa[2][BM * LDSROW];
+  __shared__ __attribute__((aligned(16))) uint16_t sb[2][BN * LDSROW];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+  const __amdgpu_buffer_rsrc_t rx = make_rsrc(g.x, g.x_bytes);
+  const __amdgpu_buffer_rsrc_t rdy = make_rsrc(g.dy, g.dy_bytes);
+  const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.wd, g.w_bytes);
+  const __amdgpu_buffer_rsrc_t rgs = make_rsrc(g.gscale, g.gscale ? (unsigned)g.N * 4u : 0u);
+  const bool has_gs = g.gscale != nullptr;
+
+  // dgrad staging: thread tid owns rows (tid >> 2) + 64 j of both tiles and the 8-element chunk (tid & 3) of each reduction tile
+  // wgrad staging: thread tid owns reduction element (pixel) tid & 31 of each tile and the rows 8 (tid >> 5) + 64 j .. + 7 of both tiles
+  const int ch = tid & 3;
+  const int mrow = tid & 31, grp = tid >> 5;
+  int pix[AL], qh0[AL], qw0[AL];                     // dgrad: per staged row
+  unsigned woff[BL];
+  int aky[AL], akx[AL], ac[AL];                      // wgrad: tap and channel of the thread's 8 k rows (ac < 0: past K)
+  int bn[BL];                                        // wgrad: first of the thread's 8 columns (< 0: past N)
+  float gsb[BL][8];                                  // wgrad: gscale of those columns
+  if constexpr (MODE == MODE_DGRAD) {
+#pragma unroll
+    for (int j = 0; j < AL; ++j) {
+      const int p = m0 + (tid >> 2) + 64 * j;
+      const int img = div_magic(p, g.magic_hw);
+      const int r = p - img * g.HW;
+      const int ih = div_magic(r, g.magic_w), iw = r - ih * g.W;
+      // a row past the end gets an output row that no tap can reach: every load of it is out of range
+      qh0[j] = p < g.rows ? ih + g.pad_t : -(1 << 20);
+      qw0[j] = iw + g.pad_l;
+      pix[j] = img * g.OH;
+    }
+#pragma unroll
+    for (int j = 0; j < BL; ++j) {
+      const int c = n0 + (tid >> 2) + 64 * j;
+      woff[j] = c < g.cols ? ((unsigned)c * (unsigned)g.ldk + 8u * ch) * 2u : kOOB;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < AL; ++j) {
+      const int k0 = m0 + 64 * j + 8 * grp;          // 8 consecutive channels of one tap (C % 8 == 0)
+      const int tap = div_magic(k0, g.magic_c);
+      aky[j] = div_magic(tap, g.magic_kw);
+      akx[j] = tap - aky[j] * g.KW;
+      ac[j] = k0 < g.rows ? k0 - tap * g.C : -1;
+    }
+#pragma unroll
+    for (int j = 0; j < BL; ++j) {
+      const int n = n0 + 64 * j + 8 * grp;           // N % 8 == 0: a chunk is inside or outside as a whole
+      bn[j] = n < g.cols ? n : -1;
+      const unsigned off = n < g.cols ? (unsigned)n * 4u : kOOB;
+      const f32x4 a = buf_load4(rgs, off), b = buf_load4(rgs, off + 16u);
+      const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) gsb[j][i] = has_gs ? v[i] : 1.f;
+    }
+  }
+
+  f32x4 ra[AL][2];                                   // A chunk in flight (fp32)
+  u32x4 rb[BL];                                      // dgrad: B chunk in flight (bf16)
+  f32x4 rbf[BL][2];                                  // wgrad: B chunk in flight (fp32)
+  f32x4 rg[2];                                       // dgrad: gscale of the A chunk's 8 columns
+  int rnn = 0;                                       // dgrad: first column of the A chunk
+  auto gload = [&](int t) {
+    if constexpr (MODE == MODE_DGRAD) {
+      const int k0 = t * BK + 8 * ch;                // 8 consecutive n of one tap (n8 % 8 == 0)
+      const int tap = div_magic(k0, g.magic_n8);
+      const int nn = k0 - tap * g.n8;
+      const int ky = div_magic(tap, g.magic_kw), kx = tap - ky * g.KW;
+      const bool kok = k0 < g.red;
+      rnn = nn;
+      rg[0] = buf_load4(rgs, (unsigned)nn * 4u);
+      rg[1] = buf_load4(rgs, (unsigned)nn * 4u + 16u);
+#pragma unroll
+      for (int j = 0; j < AL; ++j) {
+        const int qh = qh0[j] - ky, qw = qw0[j] - kx;
+        const bool ok = kok & ((unsigned)qh < (unsigned)g.OH) & ((unsigned)qw < (unsigned)g.OW);
+        const unsigned off = ok ? ((unsigned)((pix[j] + qh) * g.OW + qw) * (unsigned)g.ld_dy + (unsigned)nn) * 4u : kOOB;
+        ra[j][0] = buf_load4(rdy, off);
+        ra[j][1] = buf_load4(rdy, off + 16u);
+      }
+#pragma unroll
+      for (int j = 0; j < BL; ++j) rb[j] = buf_load4u(rw, woff[j] + (unsigned)t * (BK * 2u));
+    } else {
+      const int m = t * BK + mrow;
+      const bool mok = m < g.M;
+      const int img = div_magic(m, g.magic_ohow);
+      const int r = m - img * g.OHOW;
+      const int oh = div_magic(r, g.magic_ow), ow = r - oh * g.OW;
+      const int ihb = oh * g.stride - g.pad_t, iwb = ow * g.stride - g.pad_l, pb = img * g.H;
+#pragma unroll
+      for (int j = 0; j < AL; ++j) {
+        const int ih = ihb + aky[j], iw = iwb + akx[j];
+        const bool ok = mok & (ac[j] >= 0) & ((unsigned)ih < (unsigned)g.H) & ((unsigned)iw < (unsigned)g.W);
+        const unsigned off = ok ? ((unsigned)((pb + ih) * g.W + iw) * (unsigned)g.C + (unsigned)ac[j]) * 4u : kOOB;
+        ra[j][0] = buf_load4(rx, off);
+        ra[j][1] = buf_load4(rx, off + 16u);
+      }
+#pragma unroll
+      for (int j = 0; j < BL; ++j) {
+        const unsigned off = (mok & (bn[j] >= 0)) ? ((unsigned)m * (unsigned)g.ld_dy + (unsigned)bn[j]) * 4u : kOOB;
+        rbf[j][0] = buf_load4(rdy, off);
+        rbf[j][1] = buf_load4(rdy, off + 16u);
+      }
+    }
+  };
+  auto lstore = [&](int buf) {
+    if constexpr (MODE == MODE_DGRAD) {
+      // g = dy * gscale (one fp32 multiply), columns >= N zeroed, then rounded
+      float s[8] = {rg[0].x, rg[0].y, rg[0].z, rg[0].w, rg[1].x, rg[1].y, rg[1].z, rg[1].w};
+      bool live[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        live[i] = rnn + i < g.N;
+        s[i] = has_gs ? s[i] : 1.f;
+      }
+#pragma unroll
+      for (int j = 0; j < AL; ++j) {
+        const float v[8] = {ra[j][0].x, ra[j][0].y, ra[j][0].z, ra[j][0].w, ra[j][1].x, ra[j][1].y, ra[j][1].z, ra[j][1].w};
+        float q[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) q[i] = live[i] ? v[i] * s[i] : 0.f;
+        const f32x4 lo = {q[0], q[1], q[2], q[3]}, hi4 = {q[4], q[5], q[6], q[7]};
+        *reinterpret_cast<u32x4*>(&sa[buf][((tid >> 2) + 64 * j) * LDSROW + 8 * ch]) = pack8_bf16(lo, hi4);
+      }
+#pragma unroll
+      for (int j = 0; j < BL; ++j) *reinterpret_cast<u32x4*>(&sb[buf][((tid >> 2) + 64 * j) * LDSROW + 8 * ch]) = rb[j];
+    } else {
+      // transposed on the write: the thread's 8 channels of pixel `mrow` go to 8 LDS rows, column mrow
+#pragma unroll
+      for (int j = 0; j < AL; ++j) {
+        const float v[8] = {ra[j][0].x, ra[j][0].y, ra[j][0].z, ra[j][0].w, ra[j][1].x, ra[j][1].y, ra[j][1].z, ra[j][1].w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sa[buf][(64 * j + 8 * grp + i) * LDSROW + mrow] = to_bf16_bits(v[i]);
+      }
+#pragma unroll
+      for (int j = 0; j < BL; ++j) {
+        const float v[8] = {rbf[j][0].x, rbf[j][0].y, rbf[j][0].z, rbf[j][0].w, rbf[j][1].x, rbf[j][1].y, rbf[j][1].z, rbf[j][1].w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sb[buf][(64 * j + 8 * grp + i) * LDSROW + mrow] = to_bf16_bits(v[i] * gsb[j][i]);
+      }
+    }
+  };
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // reduction tiles [t0, t1) of this slice (split <= nrt: none is empty)
+  const int t0 = SPLIT ? (int)(((long long)g.nrt * blockIdx.z) / g.split) : 0;
+  const int t1 = SPLIT ? (int)(((long long)g.nrt * (blockIdx.z + 1)) / g.split) : g.nrt;
+  gload(t0);
+  lstore(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int cur = (t - t0) & 1;
+    gload(t + 1 < t1 ? t + 1 : t);                   // the last iteration re-loads its own tile (never stored): no branch
+#pragma unroll
+    for (int s = 0; s < BK / 16; ++s) {
+      bf16x8 af[TM], bfr[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+        af[i] = *reinterpret_cast<const bf16x8*>(&sa[cur][(wm * (BM / 2) + i * 32 + l31) * LDSROW + 16 * s + 8 * hi]);
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        bfr[j] = *reinterpret_cast<const bf16x8*>(&sb[cur][(wn * (BN / 2) + j * 32 + l31) * LDSROW + 16 * s + 8 * hi]);
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    }
+    lstore(cur ^ 1);
+    __syncthreads();
+  }
+
+  if constexpr (SPLIT) {
+    // slab layout private to this kernel: the 16 registers of a lane's 32x32 accumulator contiguous (four 16-byte accesses)
+    __shared__ int s_last;
+    const unsigned tile_id = blockIdx.x + gridDim.x * blockIdx.y;
+    const unsigned lane_off = (unsigned)((wave * TM * TN * 64 + lane) * 16) * 4u;
+    const __amdgpu_buffer_rsrc_t rslab = make_rsrc(g.partial + ((size_t)tile_id * g.split + blockIdx.z) * (BM * BN), BM * BN * 4u);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+          buf_store4_sc1(rslab, lane_off + (unsigned)(((i * TN + j) * 64 * 16 + q * 4) * 4), v);
+        }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      const unsigned ticket = __hip_atomic_fetch_add(g.counters + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int last = ticket == (unsigned)(g.split - 1);
+      if (last) __hip_atomic_store(g.counters + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+      s_last = last;
+    }
+    __syncthreads();
+    if (s_last == 0) return;                         // uniform for the workgroup
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // compiler-only: keeps the slab loads below the ticket
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int s = 0; s < g.split; ++s) {              // slices ADDED in slice order
+      const __amdgpu_buffer_rsrc_t rs = make_rsrc(g.partial + ((size_t)tile_id * g.split + s) * (BM * BN), BM * BN * 4u);
+      f32x4 v[TM * TN * 4];
+#pragma unroll
+      for (int t = 0; t < TM * TN * 4; ++t) v[t] = buf_load4_sc1(rs, lane_off + (unsigned)(((t >> 2) * 64 * 16 + (t & 3) * 4) * 4));
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 w = v[(i * TN + j) * 4 + q];
+            acc[i][j][4 * q] += w.x; acc[i][j][4 * q + 1] += w.y; acc[i][j][4 * q + 2] += w.z; acc[i][j][4 * q + 3] += w.w;
+          }
+    }
+  }
+
+  // epilogue: D[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  //   dgrad: dx = mask > 0 ? acc + dx_add : 0;   wgrad: dw = acc (+ dw)
+  const __amdgpu_buffer_rsrc_t ro = make_rsrc(g.out, g.out_bytes);
+  const __amdgpu_buffer_rsrc_t radd = make_rsrc(g.add, g.add ? g.add_bytes : 0u);       // null -> every load returns 0
+  const __amdgpu_buffer_rsrc_t rmask = make_rsrc(g.mask, g.mask ? g.mask_bytes : 0u);
+  const bool has_mask = (MODE == MODE_DGRAD) && g.mask != nullptr;
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int n = n0 + wn * (BN / 2) + j * 32 + l31;
+    const bool nv = n < g.cols;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int mb = m0 + wm * (BM / 2) + i * 32 + 4 * hi;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = mb + (r & 3) + 8 * (r >> 2);
+        const bool ok = nv & (m < g.rows);
+        const float ad = buf_load1(radd, ok ? ((unsigned)m * (unsigned)g.ld_add + (unsigned)n) * 4u : kOOB);
+        float v = acc[i][j][r] + ad;
+        if constexpr (MODE == MODE_DGRAD) {
+          const float mk = buf_load1(rmask, ok ? ((unsigned)m * (unsigned)g.ld_mask + (unsigned)n) * 4u : kOOB);
+          v = (!has_mask || mk > 0.f) ? v : 0.f;
+        }
+        buf_store1(ro, ok ? ((unsigned)m * (unsigned)g.ld_out + (unsigned)n) * 4u : kOOB, v);
+      }
+    }
+  }
+}
+
+// output tile of the launch: conv_bf16.hip's fixed rule on (rows, cols) -- 0: 128x128, 1: 128x64, 2: 64x64
+int tile_shape(long long rows, int cols, long long* tiles) {
+  const long long t128 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 128), t128x64 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 64);
+  if (cols > 64 && t128 >= 256) { *tiles = t128; return 0; }
+  if (t128x64 >= 256) { *tiles = t128x64; return 1; }
+  *tiles = (long long)radnet_cdiv(rows, 64) * radnet_cdiv(cols, 64);
+  return 2;
+}
+
+template <int BM, int BN, int MODE>
+int launch_bwd(radnet_ctx* ctx, BwdArgs g, double flops) {
+  const char* what = MODE == MODE_DGRAD ? "conv_dgrad_bf16" : "conv_wgrad_bf16";
+  const dim3 grid0(radnet_cdiv(g.rows, BM), radnet_cdiv(g.cols, BN), 1);
+  const unsigned long long tiles = (unsigned long long)grid0.x * grid0.y;
+  // by rule, never by timing: halve the split until its counters and slabs fit the context (one pass needs neither)
+  while (g.split > 1 && (tiles > kAuxBf16SplitCounterCount || !ctx->ws || tiles * (unsigned long long)g.split * BM * BN * 4ull > ctx->ws_bytes)) g.split /= 2;
+  if (g.split > 1) {
+    g.partial = (float*)ctx->ws;
+    g.counters = reinterpret_cast<unsigned*>(ctx->aux + kAuxBf16SplitCounters);
+  }
+  const dim3 grid(grid0.x, grid0.y, g.split > 1 ? g.split : 1);
+  const bool timed = ctx->timing != 0;
+  if (timed) radnet_timing_arm(ctx);
+  auto kernel = g.split > 1 ? conv_bf16_bwd_kernel<BM, BN, MODE, true> : conv_bf16_bwd_kernel<BM, BN, MODE, false>;
+  if (ctx->arm0) hipExtLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, ctx->arm0, ctx->arm1, 0, g);
+  else hipLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, g);
+  RADNET_CHECK_LAUNCH(ctx, what);
+  if (timed) radnet_timing_end_armed(ctx, MODE == MODE_DGRAD ? 1 : 2, flops);
+  return RADNET_OK;
+}
+
+template <int MODE>
+int launch_by_shape(radnet_ctx* ctx, const BwdArgs& g, double flops) {
+  long long tiles = 0;
+  const int shape = tile_shape(g.rows, g.cols, &tiles);
+  if (shape == 0) return launch_bwd<128, 128, MODE>(ctx, g, flops);
+  if (shape == 1) return launch_bwd<128, 64, MODE>(ctx, g, flops);
+  return launch_bwd<64, 64, MODE>(ctx, g, flops);
+}
+
+int cast_images(radnet_ctx* ctx, const DgradImages& L, int n_layers) {
+  hipLaunchKernelGGL(weights_to_bf16_dgrad_kernel, dim3(512, (unsigned)n_layers), dim3(256), 0, ctx->stream, L);
+  RADNET_CHECK_LAUNCH(ctx, "weights_to_bf16_dgrad_kernel");
+  return RADNET_OK;
+}
+
+// 0, or the complaint about one image
+const char* image_problem(const float* w, int taps, int c, int n, int ldw, const uint16_t* wd, int ldkd) {
+  if (!w || !wd) return "null tensor";
+  if (taps <= 0 || c <= 0 || n <= 0 || ldw < n) return "bad geometry";
+  const long long kd = (long long)taps * ((n + 7) / 8 * 8), kdp = (kd + BK - 1) / BK * BK;
+  if (ldkd < kdp || ldkd % 8 != 0 || ((uintptr_t)wd & 15)) return "ldkd must be >= taps * roundup(n, 8) rounded up to 32, a multiple of 8, wd 16-byte aligned";
+  if ((long long)c * ldkd * 2 >= (1ll << 31)) return "image too large";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" int radnet_weights_to_bf16_dgrad(radnet_ctx* ctx, const float* w, int32_t taps, int32_t c, int32_t n, int32_t ldw, uint16_t* wd,
+                                            int32_t ldkd) {
+  if (!ctx) return RADNET_ERR_ARG;
+  if (const char* why = image_problem(w, taps, c, n, ldw, wd, ldkd)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "weights_to_bf16_dgrad: %s (taps=%d c=%d n=%d ldw=%d ldkd=%d)", why, taps, c, n, ldw, ldkd);
+  DgradImages L{};
+  L.l[0] = DgradImage{w, wd, taps, c, n, ldw, ldkd, (n + 7) / 8 * 8};
+  return cast_images(ctx, L, 1);
+}
+
+extern "C" int radnet_weights_to_bf16_dgrad_arena(radnet_ctx* ctx, const float* p, int64_t n_arena, const radnet_bf16_dgrad_image* layers,
+                                                  int32_t n_layers) {
+  if (!ctx) return RADNET_ERR_ARG;
+  if (!p || n_arena <= 0 || n_layers < 0 || (n_layers > 0 && !layers)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "weights_to_bf16_dgrad_arena: null arena or registry");
+  if (n_layers > 16) RADNET_FAIL(ctx, RADNET_ERR_ARG, "weights_to_bf16_dgrad_arena: %d layers (at most 16)", n_layers);
+  if (n_layers == 0) return RADNET_OK;
+  DgradImages L{};
+  for (int k = 0; k < n_layers; ++k) {
+    const radnet_bf16_dgrad_image& s = layers[k];
+    if (s.off < 0 || s.taps <= 0 || s.c <= 0 || s.ldw <= 0 || s.off + (int64_t)s.taps * s.c * s.ldw > n_arena)
+      RADNET_FAIL(ctx, RADNET_ERR_ARG, "weights_to_bf16_dgrad_arena: layer %d lies outside the arena", k);
+    if (const char* why = image_problem(p + s.off, s.taps, s.c, s.n, s.ldw, s.wd, s.ldkd)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "weights_to_bf16_dgrad_arena: layer %d: %s", k, why);
+    L.l[k] = DgradImage{p + s.off, s.wd, s.taps, s.c, s.n, s.ldw, s.ldkd, (s.n + 7) / 8 * 8};
+  }
+  return cast_images(ctx, L, n_layers);
+}
+
+extern "C" int32_t radnet_dgrad_bf16_pick_split(int64_t p, int32_t c, int32_t kd) { return radnet_conv_bf16_pick_split(p, c, kd); }
+// rows of the weight gradient are K, its reduction the M output pixels
+extern "C" int32_t radnet_wgrad_bf16_pick_split(int64_t m, int32_t n, int32_t k) {
+  if (m <= 0 || n <= 0 || k <= 0) return 1;
+  return radnet_conv_bf16_pick_split(k, n, (int32_t)std::min<int64_t>(m, 1 << 30));
+}
+
+static int check_geometry(radnet_ctx* ctx, const radnet_conv_desc* d, const char* what) {
+  if (d->nb <= 0 || d->h <= 0 || d->w_ <= 0 || d->oh <= 0 || d->ow <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->n <= 0 || d->c <= 0)
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: bad geometry", what);
+  if ((d->oh - 1) * d->stride - d->pad_t >= d->h || (d->ow - 1) * d->stride - d->pad_l >= d->w_)
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: output %dx%d inconsistent with input %dx%d", what, d->oh, d->ow, d->h, d->w_);
+  return RADNET_OK;
+}
+
+extern "C" int radnet_conv_dgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wd, int32_t ldkd) {
+  return radnet_conv_dgrad_bf16_split(ctx, d, wd, ldkd, 1);
+}
+
+extern "C" int radnet_conv_dgrad_bf16_split(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wd, int32_t ldkd, int32_t ksplit) {
+  if (!ctx || !d) return RADNET_ERR_ARG;
+  if (!d->dy || !wd || !d->dx) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_dgrad_bf16: null tensor");
+  if (d->stride != 1) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_dgrad_bf16: stride %d (stride 1 only, as radnet_conv_dgrad)", d->stride);
+  if (int rc = check_geometry(ctx, d, "conv_dgrad_bf16")) return rc;
+  const int n8 = (d->n + 7) / 8 * 8;
+  if (d->n % 4 != 0 || d->ld_dy % 4 != 0 || d->ld_dy < n8)
+    RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_dgrad_bf16: n=%d ld_dy=%d (n and ld_dy multiples of 4, ld_dy >= n rounded up to 8)", d->n, d->ld_dy);
+  if (((uintptr_t)d->dy & 15) || ((uintptr_t)wd & 15) || (d->gscale && ((uintptr_t)d->gscale & 15)))
+    RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_dgrad_bf16: dy, gscale and wd must be 16-byte aligned");
+  const long long kd = (long long)d->kh * d->kw * n8, kdp = (kd + BK - 1) / BK * BK;
+  if (ldkd < kdp || ldkd % 8 != 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_dgrad_bf16: ldkd=%d (needs >= %lld, a multiple of 8)", ldkd, kdp);
+  if (d->ld_dx < d->c || (d->dx_add && d->ld_dx_add < d->c) || (d->dx_mask && d->ld_dx_mask < d->c))
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_dgrad_bf16: ld_dx=%d ld_dx_add=%d ld_dx_mask=%d for %d channels", d->ld_dx, d->ld_dx_add, d->ld_dx_mask, d->c);
+  const long long P = (long long)d->nb * d->h * d->w_, M = (long long)d->nb * d->oh * d->ow;
+  const long long dy_bytes = M * d->ld_dy * 4, w_bytes = (long long)d->c * ldkd * 2, out_bytes = ((P - 1) * d->ld_dx + d->c) * 4;
+  const long long add_bytes = d->dx_add ? ((P - 1) * d->ld_dx_add + d->c) * 4 : 0, mask_bytes = d->dx_mask ? ((P - 1) * d->ld_dx_mask + d->c) * 4 : 0;
+  const long long lim = 1ll << 31;
+  if (dy_bytes >= lim || w_bytes >= lim || out_bytes >= lim || add_bytes >= lim || mask_bytes >= lim || P >= (1 << 20) || M >= (1 << 20) || kdp >= (1 << 20))
+    RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_dgrad_bf16: problem too large (P=%lld kd=%lld)", P, kd);
+  BwdArgs g{};
+  g.dy = d->dy; g.gscale = d->gscale; g.wd = wd; g.out = d->dx; g.add = d->dx_add; g.mask = d->dx_mask;
+  g.H = d->h; g.W = d->w_; g.C = d->c; g.OH = d->oh; g.OW = d->ow; g.KW = d->kw; g.stride = 1; g.pad_t = d->pad_t; g.pad_l = d->pad_l;
+  g.rows = (int)P; g.cols = d->c; g.nrt = (int)(kdp / BK); g.N = d->n; g.n8 = n8; g.red = (int)kd; g.ldk = ldkd; g.M = (int)M;
+  g.ld_dy = d->ld_dy; g.ld_out = d->ld_dx; g.ld_add = d->ld_dx_add; g.ld_mask = d->ld_dx_mask;
+  g.HW = d->h * d->w_; g.OHOW = d->oh * d->ow;
+  g.magic_hw = radnet_div_magic((uint32_t)g.HW); g.magic_w = radnet_div_magic((uint32_t)d->w_);
+  g.magic_kw = radnet_div_magic((uint32_t)d->kw); g.magic_n8 = radnet_div_magic((uint32_t)n8);
+  g.dy_bytes = (unsigned)dy_bytes; g.w_bytes = (unsigned)w_bytes; g.out_bytes = (unsigned)out_bytes; g.add_bytes = (unsigned)add_bytes;
+  g.mask_bytes = (unsigned)mask_bytes;
+  if (ksplit > 64 || ksplit > g.nrt) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_dgrad_bf16: split %d (at most 64 and the %d reduction tiles)", ksplit, g.nrt);
+  g.split = ksplit > 1 ? ksplit : 1;
+  return launch_by_shape<MODE_DGRAD>(ctx, g, 2.0 * P * (double)d->c * d->kh * d->kw * d->n);
+}
+
+extern "C" int radnet_conv_wgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, int32_t msplit) {
+  if (!ctx || !d) return RADNET_ERR_ARG;
+  if (!d->x || !d->dy || !d->dw) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_bf16: null tensor");
+  if (int rc = check_geometry(ctx, d, "conv_wgrad_bf16")) return rc;
+  if (d->c % 8 != 0 || d->n % 8 != 0 || d->ld_dy % 4 != 0)
+    RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_bf16: c=%d n=%d ld_dy=%d (channel counts multiples of 8, ld_dy of 4)", d->c, d->n, d->ld_dy);
+  if (((uintptr_t)d->x & 15) || ((uintptr_t)d->dy & 15) || (d->gscale && ((uintptr_t)d->gscale & 15)))
+    RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_bf16: x, dy and gscale must be 16-byte aligned");
+  if (d->ldw < d->n || d->ld_dy < d->n || d->dw_accumulate < 0 || d->dw_accumulate > 2)
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_bf16: ldw=%d ld_dy=%d dw_accumulate=%d for %d columns", d->ldw, d->ld_dy, d->dw_accumulate, d->n);
+  const long long M = (long long)d->nb * d->oh * d->ow, K = (long long)d->kh * d->kw * d->c;
+  const long long x_bytes = (long long)d->nb * d->h * d->w_ * d->c * 4, dy_bytes = ((M - 1) * d->ld_dy + d->n) * 4, out_bytes = ((K - 1) * d->ldw + d->n) * 4;
+  const long long lim = 1ll << 31;
+  if (x_bytes >= lim || dy_bytes >= lim || out_bytes >= lim || M >= (1 << 20) || K >= (1 << 20))
+    RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_bf16: problem too large (M=%lld K=%lld)", M, K);
+  BwdArgs g{};
+  g.x = d->x; g.dy = d->dy; g.gscale = d->gscale; g.out = d->dw;
+  g.add = d->dw_accumulate != 0 ? d->dw : nullptr;      // 1: add to what is there; 2: the caller zeroed it -- the same add
+  g.H = d->h; g.W = d->w_; g.C = d->c; g.OH = d->oh; g.OW = d->ow; g.KW = d->kw; g.stride = d->stride; g.pad_t = d->pad_t; g.pad_l = d->pad_l;
+  g.rows = (int)K; g.cols = d->n; g.nrt = radnet_cdiv(M, BK); g.N = d->n; g.M = (int)M;
+  g.ld_dy = d->ld_dy; g.ld_out = d->ldw; g.ld_add = d->ldw;
+  g.HW = d->h * d->w_; g.OHOW = d->oh * d->ow;
+  g.magic_ohow = radnet_div_magic((uint32_t)g.OHOW); g.magic_ow = radnet_div_magic((uint32_t)d->ow);
+  g.magic_c = radnet_div_magic((uint32_t)d->c); g.magic_kw = radnet_div_magic((uint32_t)d->kw);
+  g.x_bytes = (unsigned)x_bytes; g.dy_bytes = (unsigned)dy_bytes; g.out_bytes = (unsigned)out_bytes; g.add_bytes = (unsigned)out_bytes;
+  if (msplit > 64 || msplit > g.nrt) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_bf16: split %d (at most 64 and the %d reduction tiles)", msplit, g.nrt);
+  g.split = msplit > 1 ? msplit : 1;
+  int rc = launch_by_shape<MODE_WGRAD>(ctx, g, 2.0 * M * (double)d->n * K);
+  // bias gradient: the exact fp32 column sum of the UNROUNDED dy * gscale, added in index order
+  if (rc == RADNET_OK && d->db) rc = radnet_colsum(ctx, d->dy, (int32_t)M, d->n, d->ld_dy, d->gscale, d->db, d->dw_accumulate != 0 ? 1 : 0);
+  return rc;
+}

@@ -94,6 +94,8 @@ extern "C" int radnet_program_run(radnet_ctx* ctx, const radnet_op* ops, int32_t
         break;
       }
       case RADNET_OP_CONV_FWD_BF16: rc = radnet_conv_fwd_bf16_split(ctx, &o.conv, (const uint16_t*)o.p[0], o.i[0], o.i[1]); break;
+      case RADNET_OP_CONV_DGRAD_BF16: rc = radnet_conv_dgrad_bf16_split(ctx, &o.conv, (const uint16_t*)o.p[0], o.i[0], o.i[1]); break;
+      case RADNET_OP_CONV_WGRAD_BF16: rc = radnet_conv_wgrad_bf16(ctx, &o.conv, o.i[1]); break;
       case RADNET_OP_NOP: rc = RADNET_OK; break;
       case RADNET_OP_MAXPOOL:
         rc = radnet_maxpool_fwd(ctx, (const float*)o.p[0], (float*)o.p[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5]);

@@ -292,11 +292,11 @@ def build_models(C, device_index=0, weights=None, lr=5e-5, bce_mode=None, worklo
     backward and Adam stay fp32 on fp32 master weights, which save_weights / load_weights read and write (ResNet50 only, not the
     cont_train.py workload)."""
     from . import losses
-    if precision not in ("fp32", "bf16", "bf16-mixed"):
-        raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-mixed', not %r" % (precision,))
+    if precision not in ("fp32", "bf16", "bf16-mixed", "bf16-train"):
+        raise ValueError("precision must be 'fp32', 'bf16', 'bf16-mixed' or 'bf16-train', not %r" % (precision,))
     if precision != "fp32" and C.network != "resnet50":
         raise NotImplementedError("precision=%r is implemented for the ResNet50 network only (not %r)" % (precision, C.network))
-    if precision == "bf16-mixed" and workload == "cont":
-        raise NotImplementedError("precision='bf16-mixed' is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)")
+    if precision in ("bf16-mixed", "bf16-train") and workload == "cont":
+        raise NotImplementedError("precision='bf16-mixed' / 'bf16-train' is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)")
     s = _Shared(C, device_index, weights, lr, losses.BCE_MODE if bce_mode is None else bce_mode, workload, precision)
     return RPNModel(s), ClassifierModel(s), AllModel(s), RPNModel(s, with_features=True), DetectorModel(s)

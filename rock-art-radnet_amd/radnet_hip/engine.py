@@ -25,7 +25,8 @@ from . import lib as L
 BN_EPS = 1e-3        # FixedBatchNormalization.py:8
 RES_STAGES = ((2, "abc", (64, 64, 256), 1), (3, "abcd", (128, 128, 512), 2), (4, "abcdef", (256, 256, 1024), 2))
 HEAD_STAGE = (5, "abc", (512, 512, 2048), 2)
-PRECISIONS = ("fp32", "bf16", "bf16-mixed")     # FasterRCNNEngine(precision=...): see __init__
+PRECISIONS = ("fp32", "bf16", "bf16-mixed", "bf16-train")     # FasterRCNNEngine(precision=...): see __init__
+MIXED_PRECISIONS = ("bf16-mixed", "bf16-train")      # trainable bf16 modes: bf16 forward convs, fp32 masters and Adam
 RPN_LD = 64          # fused RPN head GEMM width (A + 4A = 60 for 12 anchors, padded)
 
 
@@ -139,15 +140,20 @@ class FasterRCNNEngine:
         # "bf16-mixed": trainable -- the same forward convs in every training, validation and predict program, with the K split of
         # radnet_conv_bf16_pick_split; backward and Adam stay fp32 on the fp32 master weights, and Adam rewrites the bf16 images of
         # the trainable convs in its own launch (radnet_adam_step_bf16)
+        # "bf16-train": bf16-mixed whose conv data gradients and weight gradients run on the bf16 matrix cores too (fp32 accumulation,
+        # csrc/conv_bf16_bwd.hip); bias gradients, dense heads, losses and Adam stay fp32.  The layers with a data gradient keep a second
+        # bf16 image in the dgrad layout, rewritten by one cast launch after each Adam of their arena
         if precision not in PRECISIONS:
-            raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-mixed', not %r" % (precision,))
+            raise ValueError("precision must be 'fp32', 'bf16', 'bf16-mixed' or 'bf16-train', not %r" % (precision,))
         if precision != "fp32" and (self.NETWORK != "resnet50" or C_cfg.network != "resnet50"):
             raise NotImplementedError("precision=%r is implemented for the ResNet50 network only (not %r)" % (precision, C_cfg.network))
-        if precision == "bf16-mixed" and (workload or self.WORKLOAD) == "cont":
-            raise NotImplementedError("precision='bf16-mixed' is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)")
+        if precision in MIXED_PRECISIONS and (workload or self.WORKLOAD) == "cont":
+            raise NotImplementedError("precision='bf16-mixed' / 'bf16-train' is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)")
         self.precision = precision
         self._bf16_w = {}              # fp32 weight pointer -> (bf16 copy [N][ldk], ldk, conv layer, N)
         self._bf16_arena_layers = {}   # id(arena) -> (radnet_adam_bf16[], n): the bf16 images Adam rewrites for that arena
+        self._bf16_wd = {}             # bf16-train: fp32 weight pointer -> (dgrad image [cin][ldkd], ldkd, conv layer, N)
+        self._bf16_wd_arena = {}       # id(arena) -> [radnet_bf16_dgrad_image[], n made so far]: the dgrad images of that arena's layers
         self.workload = workload or self.WORKLOAD
         self.TUNED_PREFIX = "%s_%s_" % (self.workload, self.NETWORK)
         if C_cfg.network != self.NETWORK:
@@ -507,6 +513,52 @@ class FasterRCNNEngine:
     def _refresh_bf16(self):
         for wt, ldk, c, n in self._bf16_w.values():
             self.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, n, c.ldw, wt, ldk)
+        for wd, ldkd, c, n in getattr(self, "_bf16_wd", {}).values():
+            self.ctx.call("radnet_weights_to_bf16_dgrad", c.weight, c.kh * c.kh, c.cin, n, c.ldw, wd, ldkd)
+
+    def _bf16_dgrad_weights(self, c):
+        """bf16-train: the dgrad image [cin][ldkd] of conv `c` (radnet_weights_to_bf16_dgrad: element tap * n8 + j of row i is
+        bf16(w[(tap, i)][j]), n8 = N rounded up to 8, ldkd = taps * n8 rounded up to 32), made on first use and entered into its
+        arena's registry; _refresh_bf16 and adam() rewrite it in place, so compiled programs and hipGraphs keep their pointers."""
+        ent = self._bf16_wd.get(c.weight.data_ptr())
+        if ent is None:
+            taps = c.kh * c.kh
+            n = c.ldw if c.name == "rpn_heads" else c.cout
+            ldkd = (taps * ((n + 7) // 8 * 8) + 31) // 32 * 32
+            wd = torch.empty(c.cin, ldkd, dtype=torch.int16, device=self.dev)
+            ent = (wd, ldkd, c, n)
+            self._bf16_wd[c.weight.data_ptr()] = ent
+            self.ctx.call("radnet_weights_to_bf16_dgrad", c.weight, taps, c.cin, n, c.ldw, wd, ldkd)
+            for arena in (self.rpn_arena, self.head_arena):
+                lo = arena.p.data_ptr()
+                if lo <= c.weight.data_ptr() < lo + 4 * arena.n:
+                    reg = self._bf16_wd_arena.setdefault(id(arena), [(L.Bf16DgradImage * 16)(), 0])
+                    if reg[1] >= 16:
+                        raise L.RadnetError("engine: more than 16 dgrad images in one optimizer arena")
+                    r = reg[0][reg[1]]
+                    r.off, r.taps, r.c, r.n, r.ldw, r.wd, r.ldkd = (c.weight.data_ptr() - lo) // 4, taps, c.cin, n, c.ldw, wd.data_ptr(), ldkd
+                    reg[1] += 1
+        return ent
+
+    def _bf16_bwd_ops(self, ops):
+        """bf16-train: every ("dgrad", d) / ("wgrad", d) of a backward program whose reduction operand qualifies -> ("dgrad_bf16", d) /
+        ("wgrad_bf16", d) (radnet_conv_dgrad_bf16_split / radnet_conv_wgrad_bf16 with the splits of radnet_*_bf16_pick_split).
+        dgrad: stride 1, n and ld_dy multiples of 4; wgrad: c and n multiples of 8, ld_dy of 4.  Every other mode: `ops` unchanged.
+        Runs BEFORE _fuse_bias_grads and the wgrad + dgrad pairing of _compile, which both look for the fp32 kinds only: a bf16 weight
+        gradient keeps its bias-gradient column sum as the launch of its own behind it (exact fp32 sums of the unrounded dy) and
+        is never folded into radnet_conv_bwd."""
+        if getattr(self, "precision", "fp32") != "bf16-train":
+            return ops
+        by_ptr = {c.weight.data_ptr(): c for c in self.convs.values() if c.weight is not None}
+        out = []
+        for kind, p in ops:
+            if kind == "dgrad" and p.stride == 1 and p.n % 4 == 0 and p.ld_dy % 4 == 0 and p.ld_dy >= (p.n + 7) // 8 * 8:
+                self._bf16_dgrad_weights(by_ptr[p.w])
+                kind = "dgrad_bf16"
+            elif kind == "wgrad" and p.c % 8 == 0 and p.n % 8 == 0 and p.ld_dy % 4 == 0:
+                kind = "wgrad_bf16"
+            out.append((kind, p))
+        return out
 
     def _adam_bf16_layers(self, arena):
         """bf16-mixed: (radnet_adam_bf16[], n) -- the registry of the bf16 images whose fp32 masters live in `arena` (rpn_conv1 and
@@ -530,7 +582,7 @@ class FasterRCNNEngine:
 
     def _bf16_split(self, d):
         """K slices of a bf16 forward launch: radnet_conv_bf16_pick_split in bf16-mixed engines, one pass in bf16 inference engines."""
-        if getattr(self, "precision", "fp32") != "bf16-mixed":
+        if getattr(self, "precision", "fp32") not in MIXED_PRECISIONS:
             return 0
         return int(self.lib.radnet_conv_bf16_pick_split(d.nb * d.oh * d.ow, d.n, d.kh * d.kw * d.c))
 
@@ -790,7 +842,8 @@ class FasterRCNNEngine:
         hipGraph and replayed: ~20 us of host time per launch (ctypes + hipLaunchKernel) become one graph launch, and
         the host thread stays ahead of the GPU (tools/host_timeline.py).  Keyed by the program and the gradient
         write modes of its wgrad descriptors (set_accumulate edits them in place)."""
-        key = (id(ops), id(self.ctx), tuple(p.dw_accumulate if kind == "wgrad" else p[-1] for kind, p in ops if kind in ("wgrad", "wino_wgrad")))
+        key = (id(ops), id(self.ctx), tuple(p.dw_accumulate if kind in ("wgrad", "wgrad_bf16") else p[-1] for kind, p in ops
+                                            if kind in ("wgrad", "wgrad_bf16", "wino_wgrad")))
         ent = self._graphs.get(key)
         if ent is None:
             # first run of this program: every new GEMM shape is measured here, so launches run one at a time
@@ -823,8 +876,8 @@ class FasterRCNNEngine:
         """The launch list as a radnet_op array (include/radnet_hip.h): what radnet_program_run executes and what the composed
         entry points (radnet_rpn_forward / radnet_predict_tile / radnet_train_step) take.  Cached per list and gradient write
         mode (set_accumulate edits the Python descriptors in place; the array holds copies)."""
-        key = (id(ops), tuple(p.dw_accumulate if kind == "wgrad" else (p[-1] if kind == "wino_wgrad" else p[6]) for kind, p in ops
-                              if kind in ("wgrad", "wino_wgrad", "colsum")))
+        key = (id(ops), tuple(p.dw_accumulate if kind in ("wgrad", "wgrad_bf16") else (p[-1] if kind == "wino_wgrad" else p[6]) for kind, p in ops
+                              if kind in ("wgrad", "wgrad_bf16", "wino_wgrad", "colsum")))
         ent = self._compiled.get(key)
         if ent is not None:
             return ent[0]
@@ -855,6 +908,16 @@ class FasterRCNNEngine:
                 o.kind = L.OP_CONV_FWD_BF16
                 o.conv = p
                 o.p[0], o.i[0], o.i[1] = wt.data_ptr(), ldk, self._bf16_split(p)
+            elif kind == "dgrad_bf16":             # bf16-train: the layer's dgrad image rides in p[0] / i[0], the split of (tap, n) in i[1]
+                wd, ldkd, _, _ = self._bf16_wd[p.w]
+                o.kind = L.OP_CONV_DGRAD_BF16
+                o.conv = p
+                o.p[0], o.i[0] = wd.data_ptr(), ldkd
+                o.i[1] = int(self.lib.radnet_dgrad_bf16_pick_split(p.nb * p.h * p.w_, p.c, p.kh * p.kw * ((p.n + 7) // 8 * 8)))
+            elif kind == "wgrad_bf16":             # bf16-train: the split of the pixels in i[1]
+                o.kind = L.OP_CONV_WGRAD_BF16
+                o.conv = p
+                o.i[1] = int(self.lib.radnet_wgrad_bf16_pick_split(p.nb * p.oh * p.ow, p.n, p.kh * p.kw * p.c))
             elif kind in ("conv", "dgrad", "wgrad"):
                 o.kind = {"conv": L.OP_CONV_FWD, "dgrad": L.OP_CONV_DGRAD, "wgrad": L.OP_CONV_WGRAD}[kind]
                 o.conv = p
@@ -945,7 +1008,7 @@ class FasterRCNNEngine:
         arena with ONE memset, so the ~25 per-layer memsets disappear (dw_accumulate = 2)."""
         v = 1 if flag else (2 if prezeroed else 0)
         for kind, p in ops:
-            if kind == "wgrad":
+            if kind in ("wgrad", "wgrad_bf16"):
                 p.dw_accumulate = v
             elif kind == "wino_wgrad":
                 p[-1] = v
@@ -1077,7 +1140,7 @@ class FasterRCNNEngine:
             wg1 = ("wgrad", b1)
         bwd = [("wgrad", b2), ("colsum", [dz.data_ptr(), M, RPN_LD, RPN_LD, None, ch.dbias.data_ptr(), 1]),
                ("dgrad", b2), wg1, ("colsum", [dh.data_ptr(), M, 512, 512, None, c1.dbias.data_ptr(), 1])]      # M = all nb images
-        bwd = self._fuse_bias_grads(bwd)
+        bwd = self._fuse_bias_grads(self._bf16_bwd_ops(bwd))
         ws_bytes = int(self.lib.radnet_proposals_ws_bytes(M1 * self.A))
         # the re-prediction after Adam #1 (train.py:291) sees the same feature map: its input transform is already in V
         refwd = self._bf16_ops([("wino_reuse", op1[1]) if op1[0] == "wino" else op1, ("conv", d2)])
@@ -1147,7 +1210,7 @@ class FasterRCNNEngine:
         fused = (is_head and getattr(self, "head_bias_len", 0) > 0 and self.head_bias_off % 4 == 0
                  and self.head_bias_len % 4 == 0 and os.environ.get("RADNET_NO_ADAM_AFFINE", "0") != "1")
         wino = self._head_adam_wino() if is_head and getattr(self, "head_train_wino", False) else None
-        if getattr(self, "precision", "fp32") == "bf16-mixed":
+        if getattr(self, "precision", "fp32") in MIXED_PRECISIONS:
             # Adam (+ the folded shifts on the head arena) and the bf16 images of the arena's convs, one launch
             arr, n_l = self._adam_bf16_layers(arena)
             self.ctx.check(self.lib.radnet_adam_step_bf16(
@@ -1158,6 +1221,12 @@ class FasterRCNNEngine:
                 arr, n_l), "radnet_adam_step_bf16")
             if fused:
                 self._head_shift_fresh = True
+            reg = self._bf16_wd_arena.get(id(arena))
+            if reg is not None and reg[1]:
+                # bf16-train: the dgrad images of this arena's layers, ONE cast launch over the registry behind Adam on the same lane
+                # (the lane whose backward programs read them); radnet_adam_step_bf16 keeps its signature and its 16-layer cap
+                self.ctx.check(self.lib.radnet_weights_to_bf16_dgrad_arena(self.ctx.h, arena.p.data_ptr(), C.c_int64(arena.n), reg[0], reg[1]),
+                               "radnet_weights_to_bf16_dgrad_arena")
             return
         if wino is not None:      # Adam #2 + folded shifts + the Winograd filters of the classifier's 3x3 convs, one launch
             arr, n_l = wino
@@ -1348,7 +1417,7 @@ class FasterRCNNEngine:
             # gradient slice of this block's kernels: contiguous in the arena (kernels are laid out in forward order)
             k0 = self.head_arena.offsets[B["names"][0] + "/kernel"][0]
             kl, sl = self.head_arena.offsets[B["names"][3 if B["first"] else 2] + "/kernel"]
-            bwd_parts.append((self._fuse_bias_grads(bwd[part_from:]), (k0, kl + _pad4(sl))))
+            bwd_parts.append((self._fuse_bias_grads(self._bf16_bwd_ops(bwd[part_from:])), (k0, kl + _pad4(sl))))
         bwd = [op for part, _ in bwd_parts for op in part]
         cover = sorted(sl for _, sl in bwd_parts)
         if cover[0][0] != 0 or cover[-1][1] != self.head_bias_off or any(a[1] != b[0] for a, b in zip(cover, cover[1:])):

@@ -37,7 +37,7 @@ class ContEngine(FasterRCNNEngine):
 
     def __init__(self, C_cfg, device_index=0, n_classes=None, bce_mode=0, lr=2e-5, autotune=True, precision="fp32"):
         if precision not in PRECISIONS:
-            raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-mixed', not %r" % (precision,))
+            raise ValueError("precision must be 'fp32', 'bf16', 'bf16-mixed' or 'bf16-train', not %r" % (precision,))
         if precision != "fp32":
             raise NotImplementedError("precision=%r is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)"
                                       % (precision,))

@@ -43,6 +43,7 @@ class ConvDesc(C.Structure):
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_MAXPOOL, OP_COLSUM, OP_WINO, OP_WINO_REUSE, OP_WINO_WGRAD, OP_SCATTER, OP_FILL0, \
     OP_RELU_MASK, OP_ROI_BWD, OP_CONV_BWD, OP_CHAIN, OP_CONV_FWD_PAIR, OP_CONV_BNECK = range(1, 17)
 OP_CONV_FWD_BF16 = 17
+OP_CONV_DGRAD_BF16, OP_CONV_WGRAD_BF16 = 18, 19
 OP_NOP = 0
 
 
@@ -92,6 +93,11 @@ class AdamWino(C.Structure):
 class AdamBf16(C.Structure):
     """Mirror of `radnet_adam_bf16`: a conv kernel [k][ldw] inside an optimizer arena and its bf16 image [n][ldk] (bf16-mixed training)."""
     _fields_ = [("off", C.c_int64), ("k", C.c_int32), ("n", C.c_int32), ("ldw", C.c_int32), ("wt", C.c_void_p), ("ldk", C.c_int32)]
+
+
+class Bf16DgradImage(C.Structure):
+    """Mirror of `radnet_bf16_dgrad_image`: a conv kernel [taps*c][ldw] inside an optimizer arena and its dgrad image [c][ldkd] (bf16-train)."""
+    _fields_ = [("off", C.c_int64), ("taps", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("ldw", C.c_int32), ("wd", C.c_void_p), ("ldkd", C.c_int32)]
 
 
 class TrainDesc(C.Structure):
@@ -168,6 +174,13 @@ def load_library():
         "radnet_conv_fwd_bf16_split": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32, i32]),
         "radnet_conv_bf16_pick_split": (i32, [C.c_int64, i32, i32]),
         "radnet_weights_to_bf16": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
+        "radnet_weights_to_bf16_dgrad": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32]),
+        "radnet_weights_to_bf16_dgrad_arena": (C.c_int, [vp, vp, i64, C.POINTER(Bf16DgradImage), i32]),
+        "radnet_conv_dgrad_bf16": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32]),
+        "radnet_conv_dgrad_bf16_split": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32, i32]),
+        "radnet_conv_wgrad_bf16": (C.c_int, [vp, C.POINTER(ConvDesc), i32]),
+        "radnet_dgrad_bf16_pick_split": (i32, [C.c_int64, i32, i32]),
+        "radnet_wgrad_bf16_pick_split": (i32, [C.c_int64, i32, i32]),
         "radnet_conv_dgrad": (C.c_int, [vp, C.POINTER(ConvDesc)]),
         "radnet_gemm_batched": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32]),
         "radnet_winograd_filter": (C.c_int, [vp, vp, i32, i32, i32, vp]),

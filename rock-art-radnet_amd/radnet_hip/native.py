@@ -70,8 +70,8 @@ class NativeTrainStep:
     engine.select_samples)."""
 
     def __init__(self, eng, world=1):
-        if getattr(eng, "precision", "fp32") == "bf16-mixed":
-            raise NotImplementedError("NativeTrainStep: precision='bf16-mixed' is not implemented for radnet_train_step "
+        if getattr(eng, "precision", "fp32") in ("bf16-mixed", "bf16-train"):
+            raise NotImplementedError("NativeTrainStep: precision='bf16-mixed' / 'bf16-train' is not implemented for radnet_train_step "
                                       "(radnet_train_desc has no bf16 images); use TrainStep")
         if getattr(eng, "precision", "fp32") != "fp32":
             eng.check_trainable("NativeTrainStep")

@@ -1,0 +1,599 @@
+"""bf16-train mode (FasterRCNNEngine(precision="bf16-train")): bf16-mixed whose conv data gradients and weight gradients run on the
+bf16 matrix cores too (csrc/conv_bf16_bwd.hip), fp32 accumulation, fp32 masters and Adam.
+
+  1. radnet_weights_to_bf16_dgrad (+ _arena): the dgrad image equals a NumPy bf16(w) in the stated layout bit for bit, padding zero,
+     ragged n (60 of 64);
+  2. kernel parity on EVERY backward shape of the 600x1000 training plans (batch 1 and the batch-2 M): within the forward kernel's
+     bound of the fp64 sum over bf16-rounded operands, outside it against the unrounded operands;
+  3. two runs and two lanes give identical bits, split 1 == the unsplit launch;  4. dy * 2^-40 scales dw and dx bit for bit;
+  5. one training step against the oracle and the bf16-train emulation;  6. pipelined == call by call, images follow the masters;
+  7. fit / validate / save / load and isolation of the other precisions."""
+import copy
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+
+
+def _cfg(img_size=600):
+    from faster_rcnn.config import Config
+    C_ = Config()
+    C_.img_size = img_size
+    return C_
+
+
+def _bf16_bits(a):
+    """NumPy round to nearest, ties to even, fp32 -> bf16 bit patterns (uint16); finite inputs."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def _bf16_round(a):
+    return (_bf16_bits(a).astype(np.uint32) << 16).view(np.float32).astype(np.float64).reshape(np.shape(a))
+
+
+def _sample(H, W, k=0):
+    from radnet_hip import synth
+    meta = synth.synthetic_gt(2 + k, n=5, src_w=2 * W, src_h=2 * H, smin=50, smax=min(H, W))
+    return dict(img=synth.synthetic_panel(1 + k, H, W), bboxes=meta["bboxes"], width=2 * W, height=2 * H)
+
+
+def _engine(img_size=600, precision="bf16-train", **kw):
+    from radnet_hip import synth
+    from radnet_hip.engine import FasterRCNNEngine
+    eng = FasterRCNNEngine(_cfg(img_size), precision=precision, **kw)
+    eng.set_weights(synth.synthetic_weights(seed=3))
+    return eng
+
+
+@pytest.fixture(scope="module")
+def lanes():
+    """Two contexts with their own streams and 256 MB workspaces."""
+    from radnet_hip import lib as L
+    out = []
+    for _ in range(2):
+        st = torch.cuda.Stream()
+        cx = L.Context(0, stream_handle=st.cuda_stream)
+        ws = torch.empty(256 << 20, dtype=torch.uint8, device="cuda")
+        cx.check(cx.lib.radnet_set_workspace(cx.h, ws.data_ptr(), ws.numel()), "set_workspace")
+        out.append((cx, st, ws))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ 1. cast
+def _dgrad_image_ref(w, taps, c, n, ldkd):
+    """wd[i][t*n8 + j] = bf16(w[t*c + i][j]); zero elsewhere."""
+    n8 = (n + 7) // 8 * 8
+    ref = np.zeros((c, ldkd), np.uint16)
+    b = _bf16_bits(w[:, :n]).reshape(taps, c, n)
+    for t in range(taps):
+        ref[:, t * n8:t * n8 + n] = b[t]
+    return ref
+
+
+@pytest.mark.parametrize("taps,c,n,ldw,extra", [(1, 512, 60, 64, 0), (9, 64, 64, 64, 0), (9, 40, 20, 24, 32), (1, 8, 4, 4, 8)])
+def test_dgrad_image_cast(lanes, taps, c, n, ldw, extra):
+    cx, st, _ = lanes[0]
+    rs = np.random.RandomState(taps * 1000 + n)
+    w = rs.randn(taps * c, ldw).astype(np.float32)
+    w[0, 0], w[1, 0] = np.float32(1.0 + 2.0 ** -8), np.float32(1.0 + 3 * 2.0 ** -8)          # ties: to even, down and up
+    w[2, 0] = np.float32(1e-40)                                                             # a subnormal is kept
+    n8 = (n + 7) // 8 * 8
+    ldkd = (taps * n8 + 31) // 32 * 32 + extra
+    wd = torch.from_numpy(rs.randint(-32768, 32767, (c, ldkd)).astype(np.int16)).cuda()     # garbage: the padding must become 0
+    cx.call("radnet_weights_to_bf16_dgrad", torch.from_numpy(w).cuda(), taps, c, n, ldw, wd, ldkd)
+    st.synchronize()
+    ref = _dgrad_image_ref(w, taps, c, n, ldkd)
+    assert np.array_equal(wd.cpu().numpy().view(np.uint16), ref)
+    assert ref[0, 0] == 0x3F80 and ref[1, 0] == 0x3F82
+
+
+def test_dgrad_image_cast_arena_and_rejects(lanes):
+    from radnet_hip import lib as L
+    cx, st, _ = lanes[0]
+    rs = np.random.RandomState(5)
+    rows = [(0, 1, 512, 60, 64), (40000, 9, 16, 24, 24)]                     # (off, taps, c, n, ldw)
+    n_arena = 40000 + 9 * 16 * 24 + 64
+    p = rs.randn(n_arena).astype(np.float32)
+    pd = torch.from_numpy(p).cuda()
+    arr = (L.Bf16DgradImage * 16)()
+    imgs = []
+    for k, (off, taps, c, n, ldw) in enumerate(rows):
+        ldkd = (taps * ((n + 7) // 8 * 8) + 31) // 32 * 32
+        wd = torch.full((c, ldkd), -1, dtype=torch.int16, device="cuda")
+        imgs.append((wd, ldkd))
+        arr[k].off, arr[k].taps, arr[k].c, arr[k].n, arr[k].ldw, arr[k].wd, arr[k].ldkd = off, taps, c, n, ldw, wd.data_ptr(), ldkd
+    torch.cuda.synchronize()
+    cx.check(cx.lib.radnet_weights_to_bf16_dgrad_arena(cx.h, pd.data_ptr(), n_arena, arr, 2), "arena cast")
+    st.synchronize()
+    for (off, taps, c, n, ldw), (wd, ldkd) in zip(rows, imgs):
+        w = p[off:off + taps * c * ldw].reshape(taps * c, ldw)
+        assert np.array_equal(wd.cpu().numpy().view(np.uint16), _dgrad_image_ref(w, taps, c, n, ldkd))
+    before = [wd.clone() for wd, _ in imgs]
+    assert cx.lib.radnet_weights_to_bf16_dgrad_arena(cx.h, pd.data_ptr(), n_arena, arr, 17) < 0
+    arr[1].off = n_arena - 10                                                # outside the arena
+    assert cx.lib.radnet_weights_to_bf16_dgrad_arena(cx.h, pd.data_ptr(), n_arena, arr, 2) < 0
+    arr[1].off, arr[1].ldkd = 40000, imgs[1][1] - 8                          # pitch too short
+    assert cx.lib.radnet_weights_to_bf16_dgrad_arena(cx.h, pd.data_ptr(), n_arena, arr, 2) < 0
+    st.synchronize()
+    assert all(torch.equal(a, wd) for a, (wd, _) in zip(before, imgs))
+
+
+# ------------------------------------------------------------------------------------------------------------ 2.-4. kernels
+def _backward_shapes(nbs=(1, 2)):
+    """Every bf16 backward op of the 600x1000 training plans, per-GPU batch 1 and 2: (kind, nb, h, w, c, kh, stride, pad, n, ld_dy,
+    gscale?, dx_add?, dx_mask?, live columns of dy)."""
+    eng = _engine()
+    out = set()
+    for nb in nbs:
+        bp = eng._plan_base(nb, 600, 1000)
+        rp = eng._plan_rpn(bp["fh"], bp["fw"], bp["F"], nb=nb)
+        hp = eng._plan_head(eng.C.n_rois * nb, bp["fh"], bp["fw"], bp["F"], training=True, groups=nb)
+        for kind, d in rp["bwd"] + hp["bwd"]:
+            assert kind in ("dgrad_bf16", "wgrad_bf16", "colsum"), kind           # no fp32 conv gradient is left in a bf16-train program
+            if kind == "colsum":
+                continue
+            live = 5 * eng.A if d.n == 64 and d.c == 512 and d.kh == 1 and d.ld_dy == 64 else d.n
+            out.add((kind, d.nb, d.h, d.w_, d.c, d.kh, d.stride, d.pad_t, d.n, d.ld_dy, bool(d.gscale), bool(d.dx_add), bool(d.dx_mask), live))
+    return sorted(out)
+
+
+class _Case:
+    """Random unit-scale data for one backward shape and the launches on it."""
+
+    def __init__(self, shape, seed):
+        self.kind, self.nb, self.h, self.w, self.c, self.kh, self.stride, self.pad, self.n, self.ld_dy, gs, add, mask, self.live = shape
+        rs = np.random.RandomState(seed)
+        nb, h, w, c, kh, n = self.nb, self.h, self.w, self.c, self.kh, self.n
+        self.oh, self.ow = (h + 2 * self.pad - kh) // self.stride + 1, (w + 2 * self.pad - kh) // self.stride + 1
+        self.M, self.P, self.K = nb * self.oh * self.ow, nb * h * w, kh * kh * c
+        self.x = rs.randn(nb, h, w, c).astype(np.float32)
+        self.dy = rs.randn(self.M, self.ld_dy).astype(np.float32)
+        if self.kind == "dgrad_bf16" and self.live < n:
+            self.dy[:, self.live:] = np.nan                      # columns >= n of the pitch are read but must contribute zero
+        self.wgt = (rs.randn(self.K, n) / np.sqrt(kh * kh * n)).astype(np.float32)
+        self.gs = rs.uniform(0.5, 1.5, n).astype(np.float32) if gs else None
+        self.add = rs.randn(self.P, c).astype(np.float32) if add else None
+        self.mask = rs.randn(self.P, c).astype(np.float32) if mask else None
+        self.dw0 = rs.randn(self.K, n).astype(np.float32)
+        self.rs = rs
+        cu = lambda a: None if a is None else torch.from_numpy(a).cuda()
+        self.d_x, self.d_dy, self.d_w, self.d_gs, self.d_add, self.d_mask = (cu(a) for a in (self.x, self.dy, self.wgt, self.gs, self.add, self.mask))
+        self.n8 = (n + 7) // 8 * 8
+        self.ldkd = (kh * kh * self.n8 + 31) // 32 * 32
+        self.wd = torch.empty(c, self.ldkd, dtype=torch.int16, device="cuda")
+
+    def desc(self, dy=None):
+        from radnet_hip import lib as L
+        d = L.ConvDesc()
+        d.x, d.w = self.d_x.data_ptr(), self.d_w.data_ptr()
+        d.nb, d.h, d.w_, d.c, d.oh, d.ow, d.kh, d.kw = self.nb, self.h, self.w, self.c, self.oh, self.ow, self.kh, self.kh
+        d.stride, d.pad_t, d.pad_l, d.n, d.ldw, d.ldy = self.stride, self.pad, self.pad, self.n, self.n, self.n
+        d.dy, d.ld_dy = (self.d_dy if dy is None else dy).data_ptr(), self.ld_dy
+        if self.kind == "dgrad_bf16":
+            d.n = self.live                                      # rpn_heads: 60 live columns in a pitch of 64
+        d.gscale = self.d_gs.data_ptr() if self.d_gs is not None else None
+        d.ld_dx = d.ld_dx_add = d.ld_dx_mask = self.c
+        d.dx_add = self.d_add.data_ptr() if self.d_add is not None else None
+        d.dx_mask = self.d_mask.data_ptr() if self.d_mask is not None else None
+        return d
+
+    def split(self, lib):
+        if self.kind == "dgrad_bf16":
+            return int(lib.radnet_dgrad_bf16_pick_split(self.P, self.c, self.kh * self.kh * self.n8))
+        return int(lib.radnet_wgrad_bf16_pick_split(self.M, self.n, self.K))
+
+    def run(self, lane, split, mode=0, dy=None, plain=False, use_add=True):
+        """One launch; returns the output on the host.  wgrad: `mode` = dw_accumulate (1: onto dw0, 2: onto zeros)."""
+        cx, st, _ = lane
+        d = self.desc(dy)
+        if self.kind == "dgrad_bf16":
+            if not use_add:
+                d.dx_add = None
+            cx.call("radnet_weights_to_bf16_dgrad", self.d_w, self.kh * self.kh, self.c, self.live, self.n, self.wd, self.ldkd)
+            out = torch.full((self.P, self.c), float("nan"), dtype=torch.float32, device="cuda")
+            d.dx = out.data_ptr()
+            torch.cuda.synchronize()                             # `out` was filled on torch's stream, the launch goes to the lane's
+            if plain:
+                rc = cx.lib.radnet_conv_dgrad_bf16(cx.h, C.byref(d), self.wd.data_ptr(), self.ldkd)
+            else:
+                rc = cx.lib.radnet_conv_dgrad_bf16_split(cx.h, C.byref(d), self.wd.data_ptr(), self.ldkd, split)
+        else:
+            out = {0: lambda: torch.full((self.K, self.n), float("nan"), dtype=torch.float32, device="cuda"),
+                   1: lambda: torch.from_numpy(self.dw0).cuda(), 2: lambda: torch.zeros(self.K, self.n, dtype=torch.float32, device="cuda")}[mode]()
+            d.dw, d.dw_accumulate = out.data_ptr(), mode
+            torch.cuda.synchronize()
+            rc = cx.lib.radnet_conv_wgrad_bf16(cx.h, C.byref(d), split)
+        cx.check(rc, self.kind)
+        st.synchronize()
+        return out.cpu().numpy()
+
+    def g(self, rounded):
+        """dy * gscale as one fp32 multiply, columns >= live zero (the dgrad image holds zeros there; the wgrad shapes have none)."""
+        with np.errstate(invalid="ignore"):
+            g = self.dy[:, :self.n] * self.gs[None, :] if self.gs is not None else self.dy[:, :self.n].copy()
+        if self.kind == "dgrad_bf16":
+            g[:, self.live:] = 0
+        return _bf16_round(g) if rounded else g.astype(np.float64)
+
+    def reference(self, rows, rounded):
+        """(fp64 sum, sum |a*b|) for the sampled output rows: dgrad rows are pixels, wgrad rows are k indices."""
+        rd = _bf16_round if rounded else (lambda a: np.asarray(a, np.float64))
+        g = self.g(rounded)
+        if self.kind == "dgrad_bf16":
+            kh, h, w, oh, ow, pad = self.kh, self.h, self.w, self.oh, self.ow, self.pad
+            img, r = rows // (h * w), rows % (h * w)
+            ih, iw = r // w, r % w
+            A = np.zeros((len(rows), kh, kh, self.n), np.float64)
+            for ky in range(kh):
+                for kx in range(kh):
+                    qh, qw = ih + pad - ky, iw + pad - kx
+                    ok = (qh >= 0) & (qh < oh) & (qw >= 0) & (qw < ow)
+                    A[ok, ky, kx, :] = g[(img[ok] * oh + qh[ok]) * ow + qw[ok]]
+            wv = rd(self.wgt).reshape(kh, kh, self.c, self.n)
+            wv[..., self.live:] = 0
+            B = wv.transpose(0, 1, 3, 2).reshape(kh * kh * self.n, self.c)
+            return A.reshape(len(rows), -1) @ B, np.abs(A.reshape(len(rows), -1)) @ np.abs(B)
+        xp = np.pad(self.x, ((0, 0), (self.pad, self.pad), (self.pad, self.pad), (0, 0)))
+        tap, ch = rows // self.c, rows % self.c
+        A = np.zeros((self.M, len(rows)), np.float64)
+        for j, (t, cc) in enumerate(zip(tap, ch)):
+            ky, kx = t // self.kh, t % self.kh
+            A[:, j] = xp[:, ky:ky + self.stride * (self.oh - 1) + 1:self.stride, kx:kx + self.stride * (self.ow - 1) + 1:self.stride, cc].reshape(-1)
+        A = rd(A.astype(np.float32))
+        return A.T @ g, np.abs(A).T @ np.abs(g)
+
+
+@pytest.fixture(scope="module")
+def shapes():
+    s = _backward_shapes()
+    kinds = [x[0] for x in s]
+    assert kinds.count("dgrad_bf16") >= 6 and kinds.count("wgrad_bf16") >= 10, s
+    assert any(x[0] == "wgrad_bf16" and x[6] == 2 for x in s), "stride-2 1x1 weight gradients (res5a_branch2a / branch1)"
+    assert any(x[0] == "wgrad_bf16" and x[5] == 3 and x[7] == 1 for x in s), "padded 3x3 weight gradient"
+    assert any(x[0] == "dgrad_bf16" and x[13] == 60 for x in s), "rpn_heads data gradient: 60 live columns of 64"
+    return s
+
+
+def test_kernel_parity_every_backward_shape(lanes, shapes):
+    lib = lanes[0][0].lib
+    worst = {}
+    for i, shape in enumerate(shapes):
+        cs = _Case(shape, 100 + i)
+        s = cs.split(lib)
+        n_out = cs.P if cs.kind == "dgrad_bf16" else cs.K
+        rows = np.unique(np.concatenate([cs.rs.choice(n_out, min(n_out, 192), replace=False), np.arange(max(0, n_out - 4), n_out), np.arange(4)]))
+        dot, absdot = cs.reference(rows, True)
+        dot_u, _ = cs.reference(rows, False)
+        for mode in ((0,) if cs.kind == "dgrad_bf16" else (0, 1, 2)):
+            got = cs.run(lanes[0], s, mode)
+            assert np.isfinite(got).all(), shape
+            if cs.kind == "dgrad_bf16":
+                add = cs.add[rows].astype(np.float64) if cs.add is not None else 0.0
+                keep = cs.mask[rows] > 0 if cs.mask is not None else True
+                ref, ref_u = np.where(keep, dot + add, 0.0), np.where(keep, dot_u + add, 0.0)
+                tol = 1e-5 * absdot + 1e-6 * (1.0 + np.abs(add))
+            else:
+                base = cs.dw0[rows].astype(np.float64) if mode == 1 else 0.0
+                ref, ref_u = dot + base, dot_u + base
+                tol = 1e-5 * absdot + 1e-6 * (1.0 + np.abs(base))
+            err = np.abs(got[rows].astype(np.float64) - ref)
+            ratio, ratio_u = float((err / tol).max()), float((np.abs(got[rows].astype(np.float64) - ref_u) / tol).max())
+            print("%s mode %d split %d: max err / bound %.3f (against unrounded operands %.1f)" % (shape, mode, s, ratio, ratio_u))
+            worst[(shape, mode)] = ratio
+            assert (err <= tol).all(), (shape, mode, s, ratio)
+            assert ratio_u > 1.0, ("the result is as close to the unrounded operands: not a bf16 path?", shape, ratio_u)
+
+
+def test_reproducible_across_runs_lanes_and_unsplit(lanes, shapes):
+    lib = lanes[0][0].lib
+    n_split = 0
+    for i, shape in enumerate(shapes):
+        cs = _Case(shape, 300 + i)
+        s = cs.split(lib)
+        mode = 1 if cs.kind == "wgrad_bf16" else 0
+        if s > 1:
+            n_split += 1
+            a = cs.run(lanes[0], s, mode)
+            assert np.array_equal(a.view(np.int32), cs.run(lanes[0], s, mode).view(np.int32)), ("two runs differ", shape)
+            assert np.array_equal(a.view(np.int32), cs.run(lanes[1], s, mode).view(np.int32)), ("two lanes differ", shape)
+        one = cs.run(lanes[0], 1, mode)
+        unsplit = cs.run(lanes[1], 0, mode, plain=True)
+        assert np.array_equal(one.view(np.int32), unsplit.view(np.int32)), ("split 1 is not the one-pass launch", shape)
+    assert n_split > 0, "the split rules split no backward shape"
+
+
+def test_no_loss_scaling_needed(lanes, shapes):
+    """bf16 keeps fp32's exponent range: dy * 2^-40 gives dw * 2^-40 and dx * 2^-40 bit for bit (nothing subnormal; dx_add = 0)."""
+    lib = lanes[0][0].lib
+    picked = [s for s in shapes if s[0] == "dgrad_bf16"][:3] + [s for s in shapes if s[0] == "wgrad_bf16" and (s[5] == 3 or s[6] == 2)][:3]
+    for i, shape in enumerate(picked):
+        cs = _Case(shape, 500 + i)
+        tiny = np.abs(cs.dy) < 1e-3
+        cs.dy[tiny] = 1e-3                                       # 1e-3 * 2^-40 * |x| stays far above 2^-126
+        cs.d_dy = torch.from_numpy(cs.dy).cuda()
+        s = cs.split(lib)
+        a = cs.run(lanes[0], s, 0, use_add=False)
+        b = cs.run(lanes[0], s, 0, dy=torch.from_numpy(cs.dy * np.float32(2.0 ** -40)).cuda(), use_add=False)
+        nz = a != 0
+        assert nz.any() and (np.abs(a[nz]) > 1e-20).all()
+        assert np.array_equal((a * np.float32(2.0 ** -40)).view(np.int32), b.view(np.int32)), shape
+
+
+def test_unsupported_arguments_launch_nothing(lanes, shapes):
+    from radnet_hip import lib as L
+    cx, st, _ = lanes[0]
+    cs = _Case(("dgrad_bf16", 1, 6, 6, 16, 3, 1, 1, 16, 16, True, False, False, 16), 1)
+    out = torch.full((cs.P, cs.c), 7.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    cx.call("radnet_weights_to_bf16_dgrad", cs.d_w, 9, cs.c, cs.n, cs.n, cs.wd, cs.ldkd)
+
+    def dgrad(edit):
+        d = cs.desc()
+        d.dx = out.data_ptr()
+        wd, ldkd = edit(d) or (cs.wd.data_ptr(), cs.ldkd)
+        return cx.lib.radnet_conv_dgrad_bf16(cx.h, C.byref(d), wd, ldkd)
+
+    def wgrad(edit):
+        d = cs.desc()
+        d.dw = out.data_ptr()
+        edit(d)
+        return cx.lib.radnet_conv_wgrad_bf16(cx.h, C.byref(d), 1)
+
+    assert dgrad(lambda d: setattr(d, "stride", 2)) == -3                               # RADNET_ERR_UNSUPPORTED
+    assert dgrad(lambda d: setattr(d, "n", 14)) == -3
+    assert dgrad(lambda d: setattr(d, "dy", d.dy + 4)) == -3
+    assert dgrad(lambda d: (cs.wd.data_ptr() + 2, cs.ldkd)) == -3
+    assert dgrad(lambda d: (cs.wd.data_ptr(), cs.ldkd - 8)) < 0
+    assert wgrad(lambda d: setattr(d, "c", 12)) == -3
+    assert wgrad(lambda d: setattr(d, "n", 12)) == -3
+    assert wgrad(lambda d: setattr(d, "x", d.x + 4)) == -3
+    assert wgrad(lambda d: setattr(d, "dw_accumulate", 3)) < 0
+    st.synchronize()
+    assert bool((out == 7.0).all())
+    assert L.OP_CONV_DGRAD_BF16 == 18 and L.OP_CONV_WGRAD_BF16 == 19
+
+
+# ------------------------------------------------------------------------------------------------------------ 5. against the oracle
+def _arena_grads(eng, arena):
+    out = {}
+    for name, c in eng.convs.items():
+        if c.dweight is None or not (arena.g.data_ptr() <= c.dweight.data_ptr() < arena.g.data_ptr() + 4 * arena.n):
+            continue
+        g = c.dweight.detach().cpu().numpy()
+        if name == "rpn_heads":
+            out["rpn_out_class"] = g[:, :eng.A]
+            out["rpn_out_regress"] = g[:, eng.A:5 * eng.A]
+        else:
+            out[name] = g[:, :c.cout]
+    return out
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(a), 1e-30))
+
+
+@pytest.mark.parametrize("H,W", [(240, 400), (600, 1000)])
+def test_training_step_against_oracle(H, W, monkeypatch):
+    """Measured on one MI355X: every layer within 3 x emulated + 1e-4 of the fp32 oracle (worst: rpn_conv1, 1.32e-1 against an
+    emulated 1.06e-1 at 240x400); median distance to the bf16-train emulation / distance to the bf16-mixed emulation 0.957 at both panel
+    sizes -- below 1, but the forward's rounding dominates both distances: test_kernel_parity_every_backward_shape is the proof that the
+    backward computes in bf16."""
+    import bf16_emulate as E
+    import bf16_train_emulate as T
+    from oracle import dense, step as ostep
+    from radnet_hip import synth
+    from radnet_hip.trainer import TrainStep
+    Cc = _cfg(min(H, W))
+    Wt = synth.synthetic_weights(seed=3)
+    eng = _engine(min(H, W))
+    grads = {}
+    orig = eng.adam
+
+    def adam(arena, *a, **k):                # the gradient arena before Adam zeroes it
+        grads[id(arena)] = _arena_grads(eng, arena)
+        return orig(arena, *a, **k)
+    monkeypatch.setattr(eng, "adam", adam)
+    s = _sample(H, W)
+    np.random.seed(64)
+    ts = TrainStep(eng)
+    ts.capture = []
+    ts.step([s])
+    got = ts.losses()
+    R = ts.capture[0]["R"]
+    g_gpu = dict(grads[id(eng.rpn_arena)], **grads.get(id(eng.head_arena), {}))
+    monkeypatch.setattr(dense, "conv2d", E.conv2d_torch)
+    ref = {}
+    try:
+        for mode in ("fp32", "bf16", "bf16-train"):
+            E.MODE[0] = "bf16" if mode == "bf16-train" else mode
+            dense.conv2d_bwd = T.conv2d_bwd_bf16 if mode == "bf16-train" else T.CONV2D_BWD_FP32
+            np.random.seed(64)
+            det = {}
+            Ls = ostep.OracleTrainer(Cc, copy.deepcopy(Wt)).step(s, detail=det, override_R=R)
+            g = {k: v["kernel"].reshape(-1, v["kernel"].shape[-1]) for k, v in det["g_rpn"].items()}
+            g.update({k: v["kernel"].reshape(-1, v["kernel"].shape[-1]) for k, v in (det.get("g_head") or {}).items() if not k.startswith("dense")})
+            ref[mode] = (Ls, g)
+    finally:
+        E.MODE[0] = "fp32"
+        dense.conv2d_bwd = T.CONV2D_BWD_FP32
+    (L32, g32), (Lmx, gmx), (Ltr, gtr) = ref["fp32"], ref["bf16"], ref["bf16-train"]
+    for i, nm in enumerate(("rpn_cls", "rpn_regr", "det_cls", "det_regr")):
+        if L32[i] is None:
+            continue
+        emu = abs(Ltr[i] - L32[i])
+        print("%-9s gpu %.7g  oracle fp32 %.7g  bf16-train emulated %.7g" % (nm, got[nm], L32[i], Ltr[i]))
+        assert abs(got[nm] - L32[i]) <= 3 * emu + 1e-4, (nm, got[nm], L32[i], Ltr[i])
+    to_tr, to_mx = [], []
+    for name in g32:
+        emu = _rel(g32[name], gtr[name])
+        d32, dtr, dmx = _rel(g32[name], g_gpu[name]), _rel(gtr[name], g_gpu[name]), _rel(gmx[name], g_gpu[name])
+        print("%-20s emulated %.3e  gpu-fp32 %.3e  gpu-trainemu %.3e  gpu-mixedemu %.3e" % (name, emu, d32, dtr, dmx))
+        assert d32 <= 3 * emu + 1e-4, (name, d32, emu)
+        to_tr.append(dtr)
+        to_mx.append(dmx)
+    ratio = float(np.median(np.array(to_tr) / np.array(to_mx)))
+    print("median (distance to the bf16-train emulation) / (distance to the bf16-mixed emulation) = %.3f" % ratio)
+    assert ratio < 1.0, (to_tr, to_mx)
+
+
+# ------------------------------------------------------------------------------------------------------------ 6. reproducibility, images
+DGRAD_LAYERS = sorted(["rpn_heads"] + ["res5%s_branch2%s" % (b, k) for b in "abc" for k in "abc" if (b, k) != ("a", "a")])
+
+
+def _images_match(eng):
+    assert eng._bf16_w and sorted(c.name for _, _, c, _ in eng._bf16_wd.values()) == DGRAD_LAYERS
+    for wt, ldk, c, n in eng._bf16_w.values():
+        ref = torch.empty_like(wt)
+        eng.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, n, c.ldw, ref, ldk)
+        torch.cuda.synchronize()
+        assert torch.equal(ref, wt), c.name
+    for wd, ldkd, c, n in eng._bf16_wd.values():
+        ref = torch.empty_like(wd)
+        eng.ctx.call("radnet_weights_to_bf16_dgrad", c.weight, c.kh * c.kh, c.cin, n, c.ldw, ref, ldkd)
+        torch.cuda.synchronize()
+        assert torch.equal(ref, wd), "dgrad image of " + c.name
+
+
+def _run_steps(batches, prefetch, tune, defer=None):
+    from radnet_hip import synth
+    from radnet_hip.engine import FasterRCNNEngine
+    from radnet_hip.trainer import TrainStep
+    eng = FasterRCNNEngine(_cfg(300), precision="bf16-train")
+    if tune[0] is not None:
+        eng.load_tuning(tune[0])
+    eng.set_weights(synth.synthetic_weights(seed=3))
+    np.random.seed(64)
+    ts = TrainStep(eng, defer_head_update=defer)
+    ts.stack_base = False
+    losses = []
+    for k, b in enumerate(batches):
+        ts.step(b, upcoming=batches[k + 1:k + 4] if prefetch else None)
+        losses.append(ts.losses())
+    ts.flush()
+    torch.cuda.synchronize()
+    if tune[0] is None:
+        import tempfile
+        tune[0] = tempfile.mktemp(suffix=".txt")
+        eng.save_tuning(tune[0])
+    images = {c.name: wt.cpu().numpy().copy() for wt, _, c, _ in eng._bf16_w.values()}
+    images.update({"d:" + c.name: wd.cpu().numpy().copy() for wd, _, c, _ in eng._bf16_wd.values()})
+    return eng, losses, eng.get_weights(), images
+
+
+@pytest.mark.parametrize("per_batch", [1, 2])
+def test_pipelined_equals_call_by_call_and_images_follow(per_batch):
+    from radnet_hip import synth
+    batches = []
+    for i in range(4):
+        b = []
+        for j in range(per_batch):
+            meta = synth.synthetic_gt(40 + 2 * i + j, n=6, src_w=1000, src_h=600, smin=60, smax=300)
+            b.append(dict(img=synth.synthetic_panel(30 + 2 * i + j, 300, 500), bboxes=meta["bboxes"], width=1000, height=600))
+        batches.append(b)
+    tune = [None]
+    e0, l0, w0, i0 = _run_steps(batches, False, tune)
+    _images_match(e0)
+    e1, l1, w1, i1 = _run_steps(batches, True, tune)
+    _images_match(e1)
+    assert l0 == l1
+    for k in w0:
+        for kk in w0[k]:
+            assert np.array_equal(w0[k][kk], w1[k][kk]), k
+    assert i0.keys() == i1.keys()
+    assert all(np.array_equal(i0[k], i1[k]) for k in i0)
+    assert all(np.isfinite(v) for l in l0 for v in l.values() if v is not None)
+    # deferred head update (the data-parallel schedule): same bits as its own call-by-call run, images follow their masters
+    e2, l2, w2, i2 = _run_steps(batches, False, tune, defer=True)
+    e3, l3, w3, i3 = _run_steps(batches, True, tune, defer=True)
+    _images_match(e2)
+    _images_match(e3)
+    assert l2 == l3 and all(np.array_equal(i2[k], i3[k]) for k in i2)
+    assert all(np.array_equal(w2[k][kk], w3[k][kk]) for k in w2 for kk in w2[k])
+    e3.set_weights(synth.synthetic_weights(seed=5))
+    _images_match(e3)
+
+
+# ------------------------------------------------------------------------------------------------------------ 7. end to end, isolation
+AUG = ("use_horizontal_flips", "use_vertical_flips", "use_90_rotations", "use_rotations", "use_shear", "use_brightness", "use_noise")
+
+
+def test_fit_validate_save_load_and_isolation(tmp_path):
+    from faster_rcnn import data_feed, models as M
+    from radnet_hip import fit as F, synth
+    from radnet_hip.engine import FasterRCNNEngine
+    from radnet_hip.trainer import TrainStep
+    b = [[_sample(300, 500, k)] for k in range(2)]
+    tunes = {"fp32": [None], "bf16-mixed": [None]}
+
+    def other_steps(precision):
+        eng = FasterRCNNEngine(_cfg(300), precision=precision)
+        if tunes[precision][0] is not None:
+            eng.load_tuning(tunes[precision][0])              # same launch shapes -> same summation order
+        eng.set_weights(synth.synthetic_weights(seed=3))
+        np.random.seed(64)
+        ts = TrainStep(eng)
+        out = []
+        for x in b:
+            ts.step(x)
+            out.append(ts.losses())
+        ts.flush()
+        if tunes[precision][0] is None:
+            tunes[precision][0] = str(tmp_path / ("tune_%s.txt" % precision))
+            eng.save_tuning(tunes[precision][0])
+        return out, eng.get_weights()
+
+    before = {p: other_steps(p) for p in tunes}
+    C_ = _cfg(300)
+    C_.tile_size, C_.tile_overlap, C_.balanced_classes = 300, 150, False
+    for k in AUG:
+        setattr(C_, k, False)
+    m_rpn, m_cls, m_all, _, _ = M.build_models(C_, precision="bf16-train")
+    eng = m_all._s.eng
+    assert eng.precision == "bf16-train"
+    data, imgs = [], {}
+    for i in range(2):
+        meta = synth.synthetic_gt(50 + i, n=6, src_w=600, src_h=450, smin=60, smax=200)
+        data.append(dict(filepath="img_%d.png" % i, width=600, height=450, bboxes=meta["bboxes"]))
+        imgs["img_%d.png" % i] = synth.synthetic_panel(60 + i, 450, 600)
+    class_count = {}
+    for d in data:
+        for bb in d["bboxes"]:
+            class_count[bb["class"]] = class_count.get(bb["class"], 0) + 1
+    np.random.seed(3)
+    feed = iter(data_feed.TileFeed(data, C_, class_count, lambda d, t: imgs[d["filepath"]], rng=np.random.RandomState(9)))
+    ts = TrainStep(eng)
+    record = tmp_path / "record.csv"
+    val = [_sample(300, 500, k) for k in range(2)]
+    rows, _ = F.fit(ts, feed, epochs=1, epoch_length=3, val_samples=val, weights_path=str(tmp_path / "w.h5"), record_path=str(record))
+    assert record.exists() and rows
+    rec = ts.validate(val)
+    assert all(np.isfinite(v) for k, v in rec.items() if isinstance(v, float))
+    _images_match(eng)
+    path = str(tmp_path / "train.h5")
+    m_all.save_weights(path)
+    _, _, a32, _, _ = M.build_models(_cfg(300))
+    a32.load_weights(path, by_name=True)
+    w_tr, w32 = eng.get_weights(), a32._s.eng.get_weights()
+    for k in w_tr:
+        for kk in w_tr[k]:
+            assert np.array_equal(w_tr[k][kk], w32[k][kk]), k
+    # and back into a bf16-train engine whose images exist: forward and dgrad images are rewritten
+    _, _, a16, _, _ = M.build_models(_cfg(300), precision="bf16-train")
+    e16 = a16._s.eng
+    bp = e16._plan_base(1, 300, 500)
+    e16._plan_rpn(bp["fh"], bp["fw"], bp["F"])
+    e16._plan_head(e16.C.n_rois, bp["fh"], bp["fw"], bp["F"], training=True)
+    a16.load_weights(path, by_name=True)
+    _images_match(e16)
+    after = {p: other_steps(p) for p in tunes}
+    for p in tunes:
+        assert before[p][0] == after[p][0], p
+        assert all(np.array_equal(before[p][1][k][kk], after[p][1][k][kk]) for k in before[p][1] for kk in before[p][1][k]), p

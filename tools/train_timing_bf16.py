@@ -1,9 +1,11 @@
-"""fp32 against bf16-mixed (engine precision="bf16-mixed") on bench.py's train loop, as alternating A/B pairs on one box: the
+"""fp32 against bf16-mixed against bf16-train (engine precision=...) on bench.py's train loop, as alternating rounds on one box: the
 workload bench.make_batch builds (600x1000 panel, synthetic boxes), shipped launch-shape tables, the pipelined step with
 `upcoming`, warm-up and drain as bench.py does them.  Prints ms per step and images/s of every run, then the per-layer table
-of the training-shape forward convs (fp32 launch as the engine chooses it, bf16 with ksplit = 1, bf16 with the split rule).
-usage: python tools/train_timing_bf16.py [pairs=5] [per_gpu_batch=1] [steps=60]
-With --profile-mixed: only runs 40 bf16-mixed steps (the window for rocprofv3 --kernel-trace --stats)."""
+of the training-shape forward convs (fp32 launch as the engine chooses it, bf16 with ksplit = 1, bf16 with the split rule) and the
+per-layer BACKWARD table (each training-shape data gradient and weight gradient alone: the fp32 launch as the engine chooses it
+against the bf16 kernel with the split rule).
+usage: python tools/train_timing_bf16.py [rounds=5] [per_gpu_batch=1] [steps=60]
+With --profile-mixed / --profile-train: only runs 40 steps of that mode (the window for rocprofv3 --kernel-trace --stats)."""
 import ctypes as C
 import os
 import sys
@@ -79,6 +81,55 @@ def layer_table(eng, eng32, nb):
         print("%-18s %6d %5d %6d %9.4f %9.4f %3d %9.4f" % r)
 
 
+def backward_table(eng, eng32, nb):
+    """ms per launch of every distinct training-shape conv gradient, fp32 (radnet_conv_dgrad / radnet_conv_wgrad as the fp32 engine
+    launches them, each alone) against the bf16 kernel with the engine's split."""
+    bp = eng._plan_base(nb, 600, 1000)
+    rp = eng._plan_rpn(bp["fh"], bp["fw"], bp["F"], nb=nb)
+    hp = eng._plan_head(eng.C.n_rois * nb, bp["fh"], bp["fw"], bp["F"], training=True, groups=nb)
+    by_ptr = {c.weight.data_ptr(): c for c in eng.convs.values() if c.weight is not None}
+    seen, rows = set(), []
+
+    def t(fn, n=20):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+    for kind, d in rp["bwd"] + hp["bwd"]:
+        if kind not in ("dgrad_bf16", "wgrad_bf16"):
+            continue
+        M, N, K = d.nb * d.oh * d.ow, d.n, d.kh * d.kw * d.c
+        if (kind, M, N, K, d.kh, d.stride) in seen:
+            continue
+        seen.add((kind, M, N, K, d.kh, d.stride))
+        c = by_ptr[d.w]
+        d32 = L.ConvDesc.from_buffer_copy(d)
+        d32.w = eng32.convs[c.name].weight.data_ptr()
+        d32.dw = eng32.convs[c.name].dweight.data_ptr()
+        d32.db = None
+        if kind == "dgrad_bf16":
+            wd, ldkd, _, _ = eng._bf16_wd[d.w]
+            s = int(eng.lib.radnet_dgrad_bf16_pick_split(d.nb * d.h * d.w_, d.c, d.kh * d.kw * ((d.n + 7) // 8 * 8)))
+            f32 = t(lambda: eng32.ctx.check(eng32.lib.radnet_conv_dgrad(eng32.ctx.h, C.byref(d32)), "dgrad"))
+            b16 = t(lambda: eng.ctx.check(eng.lib.radnet_conv_dgrad_bf16_split(eng.ctx.h, C.byref(d), wd.data_ptr(), ldkd, s), "dgrad_bf16"))
+        else:
+            s = int(eng.lib.radnet_wgrad_bf16_pick_split(M, N, K))
+            f32 = t(lambda: eng32.ctx.check(eng32.lib.radnet_conv_wgrad(eng32.ctx.h, C.byref(d32)), "wgrad"))
+            b16 = t(lambda: eng.ctx.check(eng.lib.radnet_conv_wgrad_bf16(eng.ctx.h, C.byref(d), s), "wgrad_bf16"))
+        rows.append((c.name, kind[:5], M, N, K, f32, s, b16, f32 / b16))
+    print("%-18s %-5s %6s %5s %6s %9s %3s %9s %7s" % ("layer", "grad", "M", "N", "K", "fp32 ms", "s", "bf16 ms", "ratio"))
+    for r in rows:
+        print("%-18s %-5s %6d %5d %6d %9.4f %3d %9.4f %7.2f" % r)
+    eng.zero_grads(eng.rpn_arena), eng.zero_grads(eng.head_arena), eng32.zero_grads(eng32.rpn_arena), eng32.zero_grads(eng32.head_arena)
+    torch.cuda.synchronize()
+
+
+ARMS = ("fp32", "bf16-mixed", "bf16-train")
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     pairs = int(args[0]) if args else 5
@@ -86,23 +137,27 @@ def main():
     steps = int(args[2]) if len(args) > 2 else 60
     batch = bench.make_batch(0, per_gpu, 600, 1000)
     np.random.seed(64)
-    if "--profile-mixed" in sys.argv:
-        _, ts = make("bf16-mixed")
-        run(ts, batch, 40)
-        return
-    (e32, t32), (e16, t16) = make("fp32"), make("bf16-mixed")
-    run(t32, batch, 20)
-    run(t16, batch, 20)
-    res = {"fp32": [], "bf16-mixed": []}
+    for flag, mode in (("--profile-mixed", "bf16-mixed"), ("--profile-train", "bf16-train")):
+        if flag in sys.argv:
+            _, ts = make(mode)
+            run(ts, batch, 40)
+            return
+    made = {name: make(name) for name in ARMS}
+    for name in ARMS:
+        run(made[name][1], batch, 20)
+    res = {name: [] for name in ARMS}
     for p in range(pairs):
-        for name, ts in (("fp32", t32), ("bf16-mixed", t16)) if p % 2 == 0 else (("bf16-mixed", t16), ("fp32", t32)):
-            ms = timed(ts, batch, steps)
+        for name in ARMS[p % 3:] + ARMS[:p % 3]:            # the order rotates from round to round
+            ms = timed(made[name][1], batch, steps)
             res[name].append(ms)
-            print("pair %d %-10s %.4f ms/step  %.1f images/s" % (p, name, ms, per_gpu * 1e3 / ms), flush=True)
+            print("round %d %-10s %.4f ms/step  %.1f images/s" % (p, name, ms, per_gpu * 1e3 / ms), flush=True)
     for name, v in res.items():
-        print("%-10s median %.4f ms/step  %.1f images/s  (batch %d, %d pairs)" % (name, np.median(v), per_gpu * 1e3 / np.median(v), per_gpu, pairs))
-    print("speed-up %.3fx" % (np.median(res["fp32"]) / np.median(res["bf16-mixed"])))
-    layer_table(e16, e32, per_gpu)
+        print("%-10s median %.4f ms/step  %.1f images/s  (batch %d, %d rounds)" % (name, np.median(v), per_gpu * 1e3 / np.median(v), per_gpu, pairs))
+    print("bf16-mixed / fp32 speed-up %.3fx" % (np.median(res["fp32"]) / np.median(res["bf16-mixed"])))
+    print("bf16-train / fp32 speed-up %.3fx" % (np.median(res["fp32"]) / np.median(res["bf16-train"])))
+    print("bf16-train / bf16-mixed speed-up %.3fx" % (np.median(res["bf16-mixed"]) / np.median(res["bf16-train"])))
+    layer_table(made["bf16-mixed"][0], made["fp32"][0], per_gpu)
+    backward_table(made["bf16-train"][0], made["fp32"][0], per_gpu)
 
 
 if __name__ == "__main__":
