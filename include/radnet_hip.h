@@ -544,6 +544,49 @@ typedef struct radnet_tile_desc {
 } radnet_tile_desc;
 int radnet_predict_tile(radnet_ctx* ctx, const radnet_tile_desc* t);
 
+/* ---- the detection tail of a tile on the device (csrc/detect_tail.hip) ---------------------------------------------------
+ * From the classifier outputs to detections in source-image pixels, bit for bit what the reference's host code gives on the
+ * same tensors: the decode loop of apply_spatial_pyramid_pooling (RADNet.py:124-154) with rpn.apply_regr (rpn.py:346-378),
+ * the per-class NMS 0.2 (RADNet.py:562-575 over rpn.py:380-455) and get_real_coordinates (RADNet.py:44-51).
+ *
+ * Rows looked at: the first ceil(*n / k) * k (whole chunks of k = n_rois RoIs, padding rows included; never more than `rows`).
+ * Per row: best = the FIRST maximum of p_cls; dropped when max < bbox_threshold (an fp32 comparison, as NumPy 2 makes it against
+ *   a Python float) or best == bg.  t_q = p_regr[4*best + q] / regr_std[q] is an fp32 division, the rest fp64:
+ *   cx = tx*w + (x + w/2), w1 = exp(tw)*w, x1 = round_half_even(cx - w1/2), w1 = round_half_even(w1); where math.exp overflows
+ *   or a NaN / infinity reaches round(), the row keeps its undecoded (x, y, w, h).  Box = rpn_stride * (x, y, x+w, y+h).
+ *   exp is within 1 ulp of libm's: results can differ only where a value lies within 1 ulp of a half before rounding.
+ * Per class: greedy NMS in fp64 with radnet_nms's suppression test and tie rule (among equal scores the higher row first),
+ *   at most max_boxes picks.  A surviving box with x1 >= x2 or y1 >= y2 (the reference asserts): count = -1, no records.
+ * Per pick: int(round(v // ratio)) with Python's float floor division (fmod-based; not floor(v / ratio)).
+ * out: radnet_detect_tail_out_bytes(rows) bytes of int32 words: [0] count, [1] rows looked at, [2..7] reserved, then `count`
+ *   records (class, x1, y1, x2, y2, prob as fp32 bits) -- classes in order of their first surviving row (the insertion order of
+ *   the reference's dicts), picks of a class in pick order.  Coordinates beyond int32 saturate.
+ * One launch of one workgroup; rows <= 1024, nc <= 32; no scratch memory besides `out`. */
+typedef struct radnet_detect_tail_desc {
+  const float* p_cls;      /* [rows][nc] softmax                                              */
+  const float* p_regr;     /* [rows][4*(nc-1)]                                                */
+  const float* rois;       /* [rows][4] (x, y, w, h), integers in feature-map units           */
+  const int32_t* n;        /* device: proposal count                                          */
+  int32_t rows, nc, k, bg;
+  float bbox_threshold;
+  float regr_std[4];       /* C.classifier_regr_std                                           */
+  double rpn_stride, nms_thresh, ratio;
+  int32_t max_boxes;
+  void* out;
+} radnet_detect_tail_desc;
+uint64_t radnet_detect_tail_out_bytes(int32_t rows);
+int radnet_detect_tail(radnet_ctx* ctx, const radnet_detect_tail_desc* d);
+/* (x1,y1,x2,y2) int64 proposals R + device count (clamped to max_n) -> fp32 (x,y,w,h) RoIs for `rows` rows: row i < n is
+ * proposal i; the padding rows of the last chunk of k repeat THAT chunk's first row (RADNet.py:110-122); rows past
+ * ceil(n/k)*k, which radnet_detect_tail does not look at, repeat row 0. */
+int radnet_rois_from_proposals(radnet_ctx* ctx, const int64_t* R, const int32_t* n_dev, int32_t max_n, int32_t k, int32_t rows,
+                               float* rois);
+/* radnet_predict_tile followed by the tail: one tile of RADNet.predict up to its detections (RADNet.py:520-575), no host
+ * read-back inside the call.  t->head is built for ceil(t->max_boxes / d->k) * d->k rows, its RoIs come from
+ * radnet_rois_from_proposals; d names the head's rois / p_cls / p_regr and t->Rn.  The rows the tail looks at equal those of
+ * radnet_predict_tile on the same plan bit for bit (a GEMM row does not depend on the other rows of its launch). */
+int radnet_predict_tile_detect(radnet_ctx* ctx, const radnet_tile_desc* t, const radnet_detect_tail_desc* d);
+
 /* One flat optimizer arena (train.py:236-252: one Adam per model). */
 typedef struct radnet_adam_desc {
   float* p; float* g; float* m; float* v; int64_t n; int32_t t; float lr;

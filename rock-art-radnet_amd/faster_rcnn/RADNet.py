@@ -33,6 +33,7 @@ def _spans(length, tile, step):
 class RADNet():
 
     device_resident = True      # engine-backed models: keep tiles on the device between the stages (see _detect)
+    device_tail = True          # ... and decode + per-class NMS + source-pixel coordinates too (see _tail_on_device)
 
     def __init__(self, C, model_rpn, model_detector, preprocess_func):
         self.is_object_threshold = 0.5
@@ -166,6 +167,11 @@ class RADNet():
         preprocess -> base -> RPN -> decode/sort/NMS -> RoI crop-resize -> classifier): PCIe carries the source tile in and
         ~40 KB of proposals and class scores out.  `device_resident = False` forces the NumPy-facing calls the reference
         makes (RADNet.py:540-560); both give the same detections (same kernels), tests compare them."""
+        if self._tail_on_device():
+            img_dev, ratio = self.format_img_size(img, keep_on_device=True)
+            h = self.model_rpn.propose_launch(img_dev, overlap_thresh=0.7)
+            n = self.model_rpn.count_finish(self.model_rpn.count_launch(h))
+            return self._tail_collect(self._tail_launch(h, n, ratio))
         if self.device_resident and hasattr(self.model_rpn, "propose_device"):
             img_dev, ratio = self.format_img_size(img, keep_on_device=True)
             R, F = self.model_rpn.propose_device(img_dev, overlap_thresh=0.7)
@@ -189,6 +195,55 @@ class RADNet():
             out[key] = (real, [npr[j] for j in range(nb.shape[0])])
         return out
 
+    # ---- the detection tail on the device (csrc/detect_tail.hip) -------------------------------------------------------
+    def _tail_on_device(self):
+        """With engine-backed models and `device_tail`, _spp_decode + _per_class_nms + get_real_coordinates run as one kernel
+        behind the classifier pass and a tile's detections come back as one small record array: the host no longer waits for a
+        classifier pass before it has enqueued the next one (_detect_all).  Same detections as the host code, which stays the
+        path of `device_tail = False`, `device_resident = False` and duck-typed models (tests compare the two)."""
+        return (self.device_tail and self.device_resident and hasattr(self.model_rpn, "propose_launch")
+                and hasattr(self.model_rpn, "count_launch") and hasattr(self.model_detector, "detect_launch"))
+
+    def _tail_launch(self, h, n, ratio):
+        R_dev, Rn_dev, bp = h
+        return self.model_detector.detect_launch(bp, R_dev, Rn_dev, n, ratio, self.C.n_rois, self.bbox_threshold, nms_thresh=0.2)
+
+    def _tail_collect(self, handle):
+        cls, boxes, probs = self.model_detector.detect_finish(handle)
+        out = {}
+        for c, b, p in zip(cls.tolist(), boxes.tolist(), probs):
+            real, pr = out.setdefault(self.class_mapping[c], ([], []))
+            real.append(tuple(b))
+            pr.append(p)
+        return out
+
+    def _detect_all_tail(self, tiles, eng):
+        """_detect_all with the tail on the device.  Per tile the host reads 4 bytes -- the proposal count, from the side lane,
+        which finished it a classifier pass ago; it fixes the head plan's row count -- enqueues RoIs + classifier + tail for
+        tile j, starts the side lane on tile j+1, and only then collects the records of tile j-1."""
+        def launch(j, head_done):
+            with eng.lane("side"):
+                eng.after(head_done)                     # the classifier pass that last read this buffer set
+                img_dev, ratio = self.format_img_size(tiles[j], keep_on_device=True, ctx=eng.ctx)
+                h = self.model_rpn.propose_launch(img_dev, overlap_thresh=0.7, slot=j % 2)
+                return h, ratio, self.model_rpn.count_launch(h)
+
+        out, done, pending = [], [None, None], None
+        nxt = launch(0, None)
+        for j in range(len(tiles)):
+            (h, ratio, counted), nxt = nxt, None
+            n = self.model_rpn.count_finish(counted)     # waits for the side lane up to tile j's proposals, nothing else
+            eng.after(counted[1])
+            cur = self._tail_launch(h, n, ratio)         # enqueued, not waited for
+            done[j % 2] = eng.mark()
+            if j + 1 < len(tiles):
+                nxt = launch(j + 1, done[(j + 1) % 2])
+            if pending is not None:
+                out.append(self._tail_collect(pending))
+            pending = cur
+        out.append(self._tail_collect(pending))
+        return out
+
     def _detect_all(self, tiles):
         """_detect over a list of tiles, in order.  With the engine-backed models two tiles are in flight: while the
         classifier works on tile j (main lane), tile j+1 is uploaded, resized and run through the base network, the RPN and
@@ -196,6 +251,8 @@ class RADNet():
         eng = getattr(getattr(self.model_rpn, "_s", None), "eng", None)
         if not (self.device_resident and hasattr(self.model_rpn, "propose_launch") and eng is not None and hasattr(eng, "lane") and len(tiles) > 1):
             return [self._detect(t) for t in tiles]
+        if self._tail_on_device():
+            return self._detect_all_tail(tiles, eng)
 
         def launch(j, head_done):
             with eng.lane("side"):

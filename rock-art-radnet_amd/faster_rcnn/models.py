@@ -160,6 +160,20 @@ class RPNModel(_ModelBase):
         R, Rn = eng.proposals(rp, overlap_thresh=overlap_thresh, max_boxes=max_boxes)
         return R, Rn, bp
 
+    def count_launch(self, handle):
+        """The proposal count of a propose_launch handle on its way to the host, enqueued on the current lane (the one the
+        proposals ran on); count_finish waits for that lane alone."""
+        return self._s.eng.count_to_host(handle[1])
+
+    @staticmethod
+    def count_finish(counted):
+        h, ev = counted
+        ev.synchronize()
+        n = int(h[0])
+        if n <= 0:
+            raise ValueError("rpn_to_roi: no valid box")        # as propose_finish
+        return n
+
     @staticmethod
     def propose_finish(handle):
         R, Rn, bp = handle
@@ -277,6 +291,27 @@ class DetectorModel(_ModelBase):
 
     def predict(self, inputs, **kw):
         return self.predict_finish(self.predict_launch(inputs))
+
+    def detect_launch(self, bp, R_dev, Rn_dev, n, ratio, k, bbox_threshold, nms_thresh=0.2, max_boxes=300):
+        """The classifier pass of a tile AND its detection tail, enqueued on the current lane, nothing read back: RoIs from the
+        proposals on the device (R_dev int64 xyxy, Rn_dev their device count, n the same count on the host: it fixes the row
+        count ceil(n / k) * k, so the head runs the launches predict_launch would), classifier, decode + per-class NMS + source
+        pixels (csrc/detect_tail.hip), records into pinned memory."""
+        eng = self._s.eng
+        rows = (int(n) + k - 1) // k * k
+        hp = eng._plan_head(rows, bp["fh"], bp["fw"], bp["F"], training=False)
+        eng.head_rois_from_proposals(hp, R_dev, Rn_dev, k)
+        eng.head_forward(hp)
+        return eng.detect_tail(hp, Rn_dev, ratio, k, bbox_threshold, nms_thresh, max_boxes)
+
+    @staticmethod
+    def detect_finish(handle):
+        """(class index, boxes [m][4] in source pixels, probs fp32) of a detect_launch handle, in the order RADNet's host decode
+        yields them; AssertionError where the reference's NMS asserts."""
+        from radnet_hip.engine import read_detections
+        words, ev = handle
+        ev.synchronize()
+        return read_detections(words)
 
 
 class AllModel(_ModelBase):

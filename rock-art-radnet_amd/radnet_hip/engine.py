@@ -42,6 +42,30 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
+def threshold_f32(t):
+    """The fp32 value u with (s < t) == (s < u) for every np.float32 score s, as NumPy 2 evaluates `np.max(scores) < t`
+    (RADNet.py:131): a Python number is cast to fp32 first (np.float32(0.7) < 0.7 is False); a NumPy fp64 scalar makes the
+    comparison fp64, which equals comparing with the smallest fp32 that is >= t."""
+    if isinstance(t, (float, int)) and not isinstance(t, np.generic):
+        return float(np.float32(t))
+    u = np.float32(t)
+    if float(u) < float(t):
+        u = np.nextafter(u, np.float32(np.inf))
+    return float(u)
+
+
+def read_detections(words):
+    """The output of radnet_detect_tail (int32 words on the host, include/radnet_hip.h) -> (class index [m] int32, boxes [m][4]
+    int32 in source pixels, probs [m] float32), copies; AssertionError where the reference asserts (a box with x1 >= x2 or
+    y1 >= y2 reached the NMS, rpn.py:400-401)."""
+    words = words.numpy() if hasattr(words, "numpy") else np.asarray(words)
+    m = int(words[0])
+    if m < 0:
+        raise AssertionError("non_max_suppression_fast: box with x1 >= x2 or y1 >= y2")
+    rec = words[L.DETECT_HEADER:L.DETECT_HEADER + L.DETECT_RECORD * m].reshape(m, L.DETECT_RECORD).copy()
+    return rec[:, 0], rec[:, 1:5], rec[:, 5].view(np.float32)
+
+
 class Arena:
     """One flat fp32 parameter arena (+ grads, Adam moments) with named views: a single Adam launch and a
     single all-reduce cover every tensor of an optimizer (train.py:236-252 has one Adam per model)."""
@@ -1304,6 +1328,49 @@ class FasterRCNNEngine:
                                         rp["R"].data_ptr(), rp["Rp"].data_ptr(), rp["Rn"].data_ptr(), rp["prop_ws"].data_ptr())
         self.ctx.check(rc, "radnet_rpn_to_roi")
         return rp["R"], rp["Rn"]
+
+    # ------------------------------------------------------------------------------------------ detection tail (csrc/detect_tail.hip)
+    def count_to_host(self, n_dev):
+        """The 4 bytes of a device proposal count into a pinned word, enqueued on the current lane.  Returns (pinned int32 [1],
+        event): the reader waits for the event -- i.e. for this lane up to here, not for whatever the other lanes run."""
+        pins = self.__dict__.setdefault("_count_pins", {})
+        h = pins.get(n_dev.data_ptr())
+        if h is None:
+            h = pins[n_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._copy(h, n_dev)
+        return h, self.mark()
+
+    def head_rois_from_proposals(self, hp, R_dev, n_dev, k):
+        """The head plan's RoIs from the proposals on the device (RADNet.py:110-122, 566-567): xyxy int64 -> xywh fp32, the last
+        chunk of k padded with copies of its first row."""
+        self.ctx.call("radnet_rois_from_proposals", R_dev, n_dev, int(R_dev.shape[0]), int(k), hp["R"], hp["rois"])
+
+    def detect_tail_desc(self, hp, n_dev, ratio, k, bbox_threshold, nms_thresh=0.2, max_boxes=300, out=None):
+        """radnet_detect_tail_desc over a head plan's rois / pcls / pregr; `out` defaults to the plan's own record buffer."""
+        if out is None:
+            out = hp.get("det_out")
+            if out is None:
+                words = int(self.lib.radnet_detect_tail_out_bytes(hp["R"])) // 4
+                out = hp["det_out"] = torch.zeros(words, dtype=torch.int32, device=self.dev)
+                hp["det_host"] = torch.zeros(words, dtype=torch.int32).pin_memory()
+        d = L.DetectTailDesc()
+        d.p_cls, d.p_regr, d.rois, d.n = hp["pcls"].data_ptr(), hp["pregr"].data_ptr(), hp["rois"].data_ptr(), n_dev.data_ptr()
+        d.rows, d.nc, d.k, d.bg = hp["R"], self.nc, int(k), int(self.bg)
+        d.bbox_threshold = threshold_f32(bbox_threshold)
+        d.regr_std[:] = [float(np.float32(s)) for s in self.C.classifier_regr_std]
+        d.rpn_stride, d.nms_thresh, d.ratio = float(self.C.rpn_stride), float(nms_thresh), float(ratio)
+        d.max_boxes = min(int(max_boxes), 1024)
+        d.out = out.data_ptr()
+        return d
+
+    def detect_tail(self, hp, n_dev, ratio, k, bbox_threshold, nms_thresh=0.2, max_boxes=300):
+        """Decode + per-class NMS + source-pixel coordinates of a finished classifier pass (RADNet.py:124-154, 562-575, 44-51)
+        as one launch on the current lane, then the records into the plan's pinned buffer.  Nothing is waited for: returns
+        (pinned int32 words, event); read_detections() turns the words into records once the event has happened."""
+        d = self.detect_tail_desc(hp, n_dev, ratio, k, bbox_threshold, nms_thresh, max_boxes)
+        self.ctx.check(self.lib.radnet_detect_tail(self.ctx.h, C.byref(d)), "radnet_detect_tail")
+        self._copy(hp["det_host"], hp["det_out"])
+        return hp["det_host"], self.mark()
 
     # ------------------------------------------------------------------------------------------ classifier head
     def _plan_head(self, R, fh, fw, F, training=True, groups=1):

@@ -73,6 +73,18 @@ class TileDesc(C.Structure):
                 ("head", C.POINTER(HeadDesc))]
 
 
+class DetectTailDesc(C.Structure):
+    """Mirror of `radnet_detect_tail_desc`."""
+    _fields_ = [("p_cls", C.c_void_p), ("p_regr", C.c_void_p), ("rois", C.c_void_p), ("n", C.c_void_p),
+                ("rows", C.c_int32), ("nc", C.c_int32), ("k", C.c_int32), ("bg", C.c_int32),
+                ("bbox_threshold", C.c_float), ("regr_std", C.c_float * 4),
+                ("rpn_stride", C.c_double), ("nms_thresh", C.c_double), ("ratio", C.c_double),
+                ("max_boxes", C.c_int32), ("out", C.c_void_p)]
+
+
+DETECT_HEADER, DETECT_RECORD = 8, 6      # int32 words in front of / per record of radnet_detect_tail's output
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("t", C.c_int32), ("lr", C.c_float)]
 
@@ -237,6 +249,10 @@ def load_library():
         "radnet_program_run": (C.c_int, [vp, C.POINTER(Op), i32]),
         "radnet_rpn_forward": (C.c_int, [vp, C.POINTER(Op), i32, C.POINTER(Op), i32]),
         "radnet_predict_tile": (C.c_int, [vp, C.POINTER(TileDesc)]),
+        "radnet_detect_tail_out_bytes": (u64, [i32]),
+        "radnet_detect_tail": (C.c_int, [vp, C.POINTER(DetectTailDesc)]),
+        "radnet_rois_from_proposals": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+        "radnet_predict_tile_detect": (C.c_int, [vp, C.POINTER(TileDesc), C.POINTER(DetectTailDesc)]),
         "radnet_train_step": (C.c_int, [vp, C.POINTER(TrainDesc), C.POINTER(HostHooks), C.POINTER(C.c_float), C.POINTER(i32)]),
         "radnet_comm_unique_id": (C.c_int, [C.c_char_p]),
         "radnet_comm_init": (C.c_int, [vp, i32, i32, C.c_char_p]),

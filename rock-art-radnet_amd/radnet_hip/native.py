@@ -4,6 +4,7 @@ The engine lays the reference's graph out as static layer programs; here whole p
 
     rpn_forward(eng, bplan)            radnet_rpn_forward: base program + RPN program (model_rpn.predict, RADNet.py:552)
     predict_tile(eng, img_u8_dev, R)   radnet_predict_tile: preprocess .. proposals .. classifier outputs of the first R RoIs
+    predict_tile_detect(eng, img, ratio) radnet_predict_tile_detect: the same tile up to its detections in source pixels
     NativeTrainStep(eng).step(sample)  radnet_train_step: one reference iteration (train.py:288-402) on one image; the two
                                        NumPy-RNG-driven host steps arrive as callbacks (utils.py:785-813, train.py:93-129)
     comm_init / allreduce              radnet_comm_* / radnet_allreduce_grads: RCCL on the context's stream
@@ -42,9 +43,9 @@ def _head_desc(eng, hp):
     return h
 
 
-def predict_tile(eng, img_u8_dev, n_rois, overlap_thresh=0.7, max_boxes=300, slot=0):
-    """One tile already on the device at network size (uint8 BGR HWC) -> (proposals int64 [n][4] host, P_cls, P_regr host) for
-    the first n_rois proposals (padded with copies of the first, RADNet.py:115-122), everything in ONE radnet_predict_tile call."""
+def _tile_desc(eng, img_u8_dev, n_rois, overlap_thresh, max_boxes, slot):
+    """radnet_tile_desc of one tile already on the device at network size, with a head of n_rois rows; the second value keeps
+    what the descriptor points to alive."""
     H, W = int(img_u8_dev.shape[0]), int(img_u8_dev.shape[1])
     bp = eng._plan_base(1, H, W, slot)
     rp = eng._plan_rpn(bp["fh"], bp["fw"], bp["F"])
@@ -59,9 +60,28 @@ def predict_tile(eng, img_u8_dev, n_rois, overlap_thresh=0.7, max_boxes=300, slo
     t.std_scaling, t.overlap_thresh, t.max_boxes = float(eng.C.std_scaling), float(overlap_thresh), int(max_boxes)
     t.R, t.Rp, t.Rn, t.prop_ws = rp["R"].data_ptr(), rp["Rp"].data_ptr(), rp["Rn"].data_ptr(), rp["prop_ws"].data_ptr()
     t.head = C.pointer(head)
+    return t, (head, bp, rp, hp)
+
+
+def predict_tile(eng, img_u8_dev, n_rois, overlap_thresh=0.7, max_boxes=300, slot=0):
+    """One tile already on the device at network size (uint8 BGR HWC) -> (proposals int64 [n][4] host, P_cls, P_regr host) for
+    the first n_rois proposals (padded with copies of the first, RADNet.py:115-122), everything in ONE radnet_predict_tile call."""
+    t, (head, bp, rp, hp) = _tile_desc(eng, img_u8_dev, n_rois, overlap_thresh, max_boxes, slot)
     eng.ctx.check(eng.lib.radnet_predict_tile(eng.ctx.h, C.byref(t)), "radnet_predict_tile")
     n = int(rp["Rn"].cpu()[0])
     return rp["R"][:n].cpu().numpy(), hp["pcls"].cpu().numpy(), hp["pregr"].cpu().numpy()
+
+
+def predict_tile_detect(eng, img_u8_dev, ratio, bbox_threshold=0.7, overlap_thresh=0.7, max_boxes=300, nms_thresh=0.2, slot=0):
+    """One tile already on the device at network size -> its detections, everything in ONE radnet_predict_tile_detect call:
+    (class index [m], boxes [m][4] int32 in source pixels -- `ratio` is the tile's resize ratio --, probs [m] fp32), in the order
+    RADNet._detect yields them.  The head is built for ceil(max_boxes / n_rois) * n_rois rows; the tail looks at the first
+    ceil(n / n_rois) * n_rois of them.  AssertionError where the reference's NMS asserts."""
+    k = int(eng.C.n_rois)
+    t, (head, bp, rp, hp) = _tile_desc(eng, img_u8_dev, (int(max_boxes) + k - 1) // k * k, overlap_thresh, max_boxes, slot)
+    d = eng.detect_tail_desc(hp, rp["Rn"], ratio, k, bbox_threshold, nms_thresh, max_boxes)
+    eng.ctx.check(eng.lib.radnet_predict_tile_detect(eng.ctx.h, C.byref(t), C.byref(d)), "radnet_predict_tile_detect")
+    return E.read_detections(hp["det_out"].cpu())
 
 
 class NativeTrainStep:

@@ -1,5 +1,7 @@
 """Time the predict path (RADNet._detect: resize -> RPN -> proposals -> classifier on all RoIs -> per-class NMS) on a
-2048x2048 synthetic tile (BASELINE config 3), stage by stage.  usage: python tools/predict_timing.py [img_size]"""
+2048x2048 synthetic tile (BASELINE config 3), stage by stage.
+usage: python tools/predict_timing.py [img_size] [--device-tail 0|1] [--precision fp32|bf16]
+--device-tail: RADNet.device_tail for the _detect / _detect_all lines (decode + per-class NMS on the device or on the host)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,9 +13,17 @@ from faster_rcnn.base_models import resnet50
 from faster_rcnn.config import Config
 from radnet_hip import synth
 
-C = Config(); C.img_size = int(sys.argv[1]) if len(sys.argv) > 1 else 600
-m_rpn, m_cls, m_all, m_rpn3, m_det = M.build_models(C, weights=synth.synthetic_weights(seed=3))
+import argparse
+ap = argparse.ArgumentParser()
+ap.add_argument("img_size", nargs="?", type=int, default=600)
+ap.add_argument("--device-tail", type=int, choices=(0, 1), default=int(RADNet.device_tail))
+ap.add_argument("--precision", default="fp32")
+args = ap.parse_args()
+C = Config(); C.img_size = args.img_size
+m_rpn, m_cls, m_all, m_rpn3, m_det = M.build_models(C, weights=synth.synthetic_weights(seed=3), **({} if args.precision == "fp32" else dict(workload="predict", precision=args.precision)))
 net = RADNet(C, m_rpn3, m_det, resnet50.preprocess)
+net.device_tail = bool(args.device_tail)
+print("device_tail = %d, precision %s" % (args.device_tail, args.precision))
 tile = np.random.RandomState(4).randint(0, 256, (2048, 2048, 3)).astype(np.uint8)
 for _ in range(3):
     net._detect(tile)
