@@ -3,7 +3,8 @@
 Python here is a *scheduler*: it owns the weight / activation buffers (torch-ROCm tensors used purely
 as containers), lays the reference's Keras graph out as a static list of kernel launches per image
 size, and calls libradnet_hip.so through the C ABI (radnet_hip.lib).  No torch arithmetic runs on the
-hot path.
+hot path.  The launch lists themselves -- the op vocabulary, the passes that rewrite a list, its translation into
+radnet_op[] -- are radnet_hip.program (no device needed); the bf16 weight images are radnet_hip.bf16_images.
 
 Graph restated from the reference (never imported):
   base   faster_rcnn/base_models/resnet50.py:150-228   conv1 + stages 2-4, frozen BN folded into epilogues
@@ -21,12 +22,13 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import program as prog
+from .bf16_images import Bf16Images
+from .program import MIXED_PRECISIONS, PRECISIONS  # noqa: F401  (FasterRCNNEngine(precision=...): see __init__)
 
 BN_EPS = 1e-3        # FixedBatchNormalization.py:8
 RES_STAGES = ((2, "abc", (64, 64, 256), 1), (3, "abcd", (128, 128, 512), 2), (4, "abcdef", (256, 256, 1024), 2))
 HEAD_STAGE = (5, "abc", (512, 512, 2048), 2)
-PRECISIONS = ("fp32", "bf16", "bf16-mixed", "bf16-train")     # FasterRCNNEngine(precision=...): see __init__
-MIXED_PRECISIONS = ("bf16-mixed", "bf16-train")      # trainable bf16 modes: bf16 forward convs, fp32 masters and Adam
 RPN_LD = 64          # fused RPN head GEMM width (A + 4A = 60 for 12 anchors, padded)
 
 
@@ -174,10 +176,12 @@ class FasterRCNNEngine:
         if precision in MIXED_PRECISIONS and (workload or self.WORKLOAD) == "cont":
             raise NotImplementedError("precision='bf16-mixed' / 'bf16-train' is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)")
         self.precision = precision
-        self._bf16_w = {}              # fp32 weight pointer -> (bf16 copy [N][ldk], ldk, conv layer, N)
-        self._bf16_arena_layers = {}   # id(arena) -> (radnet_adam_bf16[], n): the bf16 images Adam rewrites for that arena
-        self._bf16_wd = {}             # bf16-train: fp32 weight pointer -> (dgrad image [cin][ldkd], ldkd, conv layer, N)
-        self._bf16_wd_arena = {}       # id(arena) -> [radnet_bf16_dgrad_image[], n made so far]: the dgrad images of that arena's layers
+        self.bf16 = Bf16Images(self)
+        self._inference_filters_stale = False      # the head weights changed since the inference plans' Winograd filters were made
+        self._head_shift_fresh = False             # adam() of the head arena has just refreshed the folded shifts in its own launch
+        self._chain_clamped = self._chain_warned = False
+        self._head_slices = False                  # head_exchange_slices(): not worked out yet
+        self._count_pins = {}                      # count_to_host(): device count pointer -> pinned word
         self.workload = workload or self.WORKLOAD
         self.TUNED_PREFIX = "%s_%s_" % (self.workload, self.NETWORK)
         if C_cfg.network != self.NETWORK:
@@ -370,15 +374,15 @@ class FasterRCNNEngine:
 
     def sync_inference_filters(self):
         """Winograd filter transforms of the classifier's 3x3 convs (inference plans only) after the head weights changed."""
-        if getattr(self, "_inference_filters_stale", False):
+        if self._inference_filters_stale:
             self._inference_filters_stale = False
-            self._refresh_bf16()
+            self.bf16.refresh()
             self._refresh_winograd([n for n in self.INFERENCE_WINOGRAD_LAYERS if getattr(self.convs.get(n), "wino_u", None) is not None])
 
     def refresh_head_shift(self):
         """shift = scale * bias + t0 for every stage-5 conv (FixedBatchNormalization.py:59-85 folded).  A no-op right after adam()
         of the head arena, which refreshes the shifts in the same launch (radnet_adam_step_affine)."""
-        if getattr(self, "_head_shift_fresh", False):
+        if self._head_shift_fresh:
             self._head_shift_fresh = False
             return
         bias = self.head_arena.p[self.head_bias_off:self.head_bias_off + self.head_bias_len]
@@ -434,7 +438,7 @@ class FasterRCNNEngine:
         self.dense_w.copy_(t(k)); self.dense_b.copy_(t(b))
         self.refresh_head_shift()
         self._refresh_winograd()
-        self._refresh_bf16()
+        self.bf16.refresh()
         torch.cuda.synchronize(self.dev)
 
     def get_weights(self, names=None):
@@ -484,9 +488,9 @@ class FasterRCNNEngine:
     INFERENCE_WINOGRAD_LAYERS = tuple("res5%s_branch2b" % b for b in "abc")
 
     def _uses_winograd(self, c, inference=False):
-        if getattr(self, "precision", "fp32") != "fp32":
+        if self.precision != "fp32":
             return False               # bf16 mode: every 3x3 conv in the direct form (the F(4x4) transforms amplify the rounding)
-        listed = c.name in self.WINOGRAD_LAYERS or ((inference or getattr(self, "head_train_wino", False)) and c.name in self.INFERENCE_WINOGRAD_LAYERS
+        listed = c.name in self.WINOGRAD_LAYERS or ((inference or self.head_train_wino) and c.name in self.INFERENCE_WINOGRAD_LAYERS
                                                     and os.environ.get("RADNET_NO_INFERENCE_WINOGRAD", "0") != "1")
         return self.use_winograd and listed and c.kh == 3 and c.stride == 1 and c.pad == 1 and c.cin % 32 == 0
 
@@ -504,7 +508,7 @@ class FasterRCNNEngine:
         """Filter transform U = G g G^T of the Winograd layers (all of them, or the named ones after a weight update)."""
         for name in (names if names is not None else self.WINOGRAD_LAYERS + tuple(n for n in self.INFERENCE_WINOGRAD_LAYERS
                                                                                    if getattr(self.convs.get(n), "wino_u", None) is not None
-                                                                                   or getattr(self, "head_train_wino", False))):
+                                                                                   or self.head_train_wino)):
             c = self.convs.get(name)
             if c is None or not self._uses_winograd(c, inference=True):
                 continue
@@ -516,113 +520,17 @@ class FasterRCNNEngine:
     # ------------------------------------------------------------------------------------------ bf16 inference / bf16-mixed modes
     def check_trainable(self, what):
         """Training entry points call this: a bf16 engine is an inference engine (fp32 and bf16-mixed engines train)."""
-        if getattr(self, "precision", "fp32") == "bf16":
+        if self.precision == "bf16":
             raise RuntimeError("%s: this engine was built with precision=%r, which is inference only; build an fp32 engine to train"
                                % (what, self.precision))
 
-    def _bf16_weights(self, c):
-        """bf16 copy [N][ldk] of conv `c`'s weights (N = the descriptor's output columns, ldk = K rounded up to 32), made on first
-        use; _refresh_bf16 rewrites it in place whenever the weights change, so compiled programs and hipGraphs keep their pointers."""
-        ent = self._bf16_w.get(c.weight.data_ptr())
-        if ent is None:
-            k = c.kh * c.kh * c.cin
-            n = c.ldw if c.name == "rpn_heads" else c.cout
-            ldk = (k + 31) // 32 * 32
-            wt = torch.empty(n, ldk, dtype=torch.int16, device=self.dev)
-            ent = (wt, ldk, c, n)
-            self._bf16_w[c.weight.data_ptr()] = ent
-            self.ctx.call("radnet_weights_to_bf16", c.weight, k, n, c.ldw, wt, ldk)
-        return ent
+    def _forward_program(self, ops, bottlenecks=False):
+        """A forward launch list as it runs in this engine's precision (program.forward_program keeps the order of the passes)."""
+        return prog.forward_program(ops, self.precision, self.bf16.forward_image, bottlenecks)
 
-    def _refresh_bf16(self):
-        for wt, ldk, c, n in self._bf16_w.values():
-            self.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, n, c.ldw, wt, ldk)
-        for wd, ldkd, c, n in getattr(self, "_bf16_wd", {}).values():
-            self.ctx.call("radnet_weights_to_bf16_dgrad", c.weight, c.kh * c.kh, c.cin, n, c.ldw, wd, ldkd)
-
-    def _bf16_dgrad_weights(self, c):
-        """bf16-train: the dgrad image [cin][ldkd] of conv `c` (radnet_weights_to_bf16_dgrad: element tap * n8 + j of row i is
-        bf16(w[(tap, i)][j]), n8 = N rounded up to 8, ldkd = taps * n8 rounded up to 32), made on first use and entered into its
-        arena's registry; _refresh_bf16 and adam() rewrite it in place, so compiled programs and hipGraphs keep their pointers."""
-        ent = self._bf16_wd.get(c.weight.data_ptr())
-        if ent is None:
-            taps = c.kh * c.kh
-            n = c.ldw if c.name == "rpn_heads" else c.cout
-            ldkd = (taps * ((n + 7) // 8 * 8) + 31) // 32 * 32
-            wd = torch.empty(c.cin, ldkd, dtype=torch.int16, device=self.dev)
-            ent = (wd, ldkd, c, n)
-            self._bf16_wd[c.weight.data_ptr()] = ent
-            self.ctx.call("radnet_weights_to_bf16_dgrad", c.weight, taps, c.cin, n, c.ldw, wd, ldkd)
-            for arena in (self.rpn_arena, self.head_arena):
-                lo = arena.p.data_ptr()
-                if lo <= c.weight.data_ptr() < lo + 4 * arena.n:
-                    reg = self._bf16_wd_arena.setdefault(id(arena), [(L.Bf16DgradImage * 16)(), 0])
-                    if reg[1] >= 16:
-                        raise L.RadnetError("engine: more than 16 dgrad images in one optimizer arena")
-                    r = reg[0][reg[1]]
-                    r.off, r.taps, r.c, r.n, r.ldw, r.wd, r.ldkd = (c.weight.data_ptr() - lo) // 4, taps, c.cin, n, c.ldw, wd.data_ptr(), ldkd
-                    reg[1] += 1
-        return ent
-
-    def _bf16_bwd_ops(self, ops):
-        """bf16-train: every ("dgrad", d) / ("wgrad", d) of a backward program whose reduction operand qualifies -> ("dgrad_bf16", d) /
-        ("wgrad_bf16", d) (radnet_conv_dgrad_bf16_split / radnet_conv_wgrad_bf16 with the splits of radnet_*_bf16_pick_split).
-        dgrad: stride 1, n and ld_dy multiples of 4; wgrad: c and n multiples of 8, ld_dy of 4.  Every other mode: `ops` unchanged.
-        Runs BEFORE _fuse_bias_grads and the wgrad + dgrad pairing of _compile, which both look for the fp32 kinds only: a bf16 weight
-        gradient keeps its bias-gradient column sum as the launch of its own behind it (exact fp32 sums of the unrounded dy) and
-        is never folded into radnet_conv_bwd."""
-        if getattr(self, "precision", "fp32") != "bf16-train":
-            return ops
-        by_ptr = {c.weight.data_ptr(): c for c in self.convs.values() if c.weight is not None}
-        out = []
-        for kind, p in ops:
-            if kind == "dgrad" and p.stride == 1 and p.n % 4 == 0 and p.ld_dy % 4 == 0 and p.ld_dy >= (p.n + 7) // 8 * 8:
-                self._bf16_dgrad_weights(by_ptr[p.w])
-                kind = "dgrad_bf16"
-            elif kind == "wgrad" and p.c % 8 == 0 and p.n % 8 == 0 and p.ld_dy % 4 == 0:
-                kind = "wgrad_bf16"
-            out.append((kind, p))
-        return out
-
-    def _adam_bf16_layers(self, arena):
-        """bf16-mixed: (radnet_adam_bf16[], n) -- the registry of the bf16 images whose fp32 masters live in `arena` (rpn_conv1 and
-        rpn_heads in the RPN arena, the ten stage-5 convs in the head arena), made on first use together with any image not made yet.
-        Adam #1 and the RPN forwards run on the main lane, Adam #2 and the classifier forward on the head lane: each image is written
-        and read on one lane.  The frozen base's images are written once per weight load (set_weights)."""
-        ent = self._bf16_arena_layers.get(id(arena))
-        if ent is None:
-            lo, hi = arena.p.data_ptr(), arena.p.data_ptr() + 4 * arena.n
-            rows = []
-            for c in self.convs.values():
-                if c.weight is not None and c.cin % 8 == 0 and lo <= c.weight.data_ptr() < hi:
-                    wt, ldk, _, n = self._bf16_weights(c)
-                    rows.append(((c.weight.data_ptr() - lo) // 4, c.kh * c.kh * c.cin, n, c.ldw, wt.data_ptr(), ldk))
-            arr = (L.AdamBf16 * max(len(rows), 1))()
-            for k, (off, kk, n, ldw, wt, ldk) in enumerate(rows):
-                arr[k].off, arr[k].k, arr[k].n, arr[k].ldw, arr[k].wt, arr[k].ldk = off, kk, n, ldw, wt, ldk
-            ent = (arr, len(rows))
-            self._bf16_arena_layers[id(arena)] = ent
-        return ent
-
-    def _bf16_split(self, d):
-        """K slices of a bf16 forward launch: radnet_conv_bf16_pick_split in bf16-mixed engines, one pass in bf16 inference engines."""
-        if getattr(self, "precision", "fp32") not in MIXED_PRECISIONS:
-            return 0
-        return int(self.lib.radnet_conv_bf16_pick_split(d.nb * d.oh * d.ow, d.n, d.kh * d.kw * d.c))
-
-    def _bf16_ops(self, ops):
-        """bf16 / bf16-mixed modes: every direct forward conv whose input has a multiple of 8 channels -> ("conv_bf16", desc); the
-        4-channel stem stays fp32.  fp32 mode: `ops` unchanged."""
-        if getattr(self, "precision", "fp32") == "fp32":
-            return ops
-        by_ptr = {c.weight.data_ptr(): c for c in self.convs.values()}
-        out = []
-        for kind, p in ops:
-            if kind == "conv" and p.c % 8 == 0:
-                self._bf16_weights(by_ptr[p.w])
-                kind = "conv_bf16"
-            out.append((kind, p))
-        return out
+    def _backward_program(self, ops):
+        """A backward launch list as it runs in this engine's precision (program.backward_program keeps the order of the passes)."""
+        return prog.backward_program(ops, self.precision, self.bf16.dgrad_image)
 
     def _fwd_op(self, c, x, nb, h, w, y, keep, relu=True, inference=False):
         """Forward op of conv `c` on x -> y: the direct implicit GEMM, or the Winograd form for the layers listed above."""
@@ -636,9 +544,9 @@ class FasterRCNNEngine:
         V = torch.empty((m + 2) ** 2, T, c.cin, dtype=torch.float32, device=self.dev)
         M = torch.empty((m + 2) ** 2, T, c.cout, dtype=torch.float32, device=self.dev)
         keep += [V, M]
-        op = ("wino", (x.data_ptr(), nb, h, w, c.cin, c.cout, V.data_ptr(), c.wino_u.data_ptr(), M.data_ptr(), T,
-                       c.scale.data_ptr() if c.scale is not None else None, c.shift.data_ptr() if c.shift is not None else None,
-                       1 if relu else 0, y.data_ptr(), c.cout, m))
+        op = prog.wino(x=x.data_ptr(), nb=nb, h=h, w=w, c=c.cin, n=c.cout, V=V.data_ptr(), U=c.wino_u.data_ptr(), M=M.data_ptr(), T=T,
+                    scale=c.scale.data_ptr() if c.scale is not None else None, shift=c.shift.data_ptr() if c.shift is not None else None,
+                    act=1 if relu else 0, y=y.data_ptr(), ldy=c.cout, form=m)
         return op, d
 
     def _plan_base(self, nb, H, W, slot=0):
@@ -663,7 +571,7 @@ class FasterRCNNEngine:
         ops.append(("conv", d))
         ph, pw = (oh - 3) // 2 + 1, (ow - 3) // 2 + 1
         p = buf(nb, ph, pw, 64)
-        ops.append(("maxpool", (y, p, nb, oh, ow, 64, 3, 2)))
+        ops.append(prog.maxpool(x=y, y=p, nb=nb, h=oh, w=ow, c=64, k=3, stride=2))
         cur, h, w = p, ph, pw
         for st, blocks, (f1, f2, f3), stride in RES_STAGES:
             for bl in blocks:
@@ -690,9 +598,7 @@ class FasterRCNNEngine:
                 out = buf(nb, oh, ow, f3)
                 d, _, _ = self._desc(cc, bb, nb, oh, ow, out, relu=True, addend=sc); ops.append(("conv", d))
                 cur, h, w = out, oh, ow
-        if self.bneck_fuse and not self.use_chain and self.FROZEN_BASE_FUSION:
-            ops = self._fuse_bottlenecks(ops)
-        ops = self._bf16_ops(ops)
+        ops = self._forward_program(ops, bottlenecks=self.bneck_fuse and not self.use_chain and self.FROZEN_BASE_FUSION)
         plan = dict(ops=ops, x=x, F=cur, fh=h, fw=w, keep=keep, nb=nb)
         if self.use_chain:
             self._chain_ops(plan, first=2)               # conv1 (4-channel stem) and the max-pool stay launches of their own
@@ -704,35 +610,9 @@ class FasterRCNNEngine:
     HEAD_TRAIN_WINOGRAD = True         # classifier 3x3 convs: Winograd forward in training too (engine_cont keeps the direct form)
     FROZEN_BASE_FUSION = True          # nn_base's stage 2 is frozen in every mode this engine runs (train.py, cont_train.py: stages 3-4 only)
 
-    @staticmethod
-    def _fuse_bottlenecks(ops):
-        """3x3 conv (64 -> 64 channels) + the 1x1 expand on its output (+ the next block's 1x1 reduce on THAT output) -> one
-        radnet_conv_bottleneck call: the 3x3's output and the expand's re-read never touch memory.  Only where the 3x3 output has no other
-        reader in the list (it is not written any more) -- stage 2 of nn_base (resnet50.py:197-199)."""
-        def conv(i):
-            return ops[i][1] if i < len(ops) and ops[i][0] == "conv" else None
-
-        def reads(d, ptr):
-            return ptr in (getattr(d, "x", None), getattr(d, "addend", None))
-
-        out, k = [], 0
-        while k < len(ops):
-            db, dc = conv(k), conv(k + 1)
-            ok = (db is not None and dc is not None and db.kh == 3 and db.stride == 1 and db.n == 64 and db.c % 32 == 0 and not db.addend and db.act == 1
-                  and dc.kh == 1 and dc.stride == 1 and dc.x == db.y and dc.c == 64 and dc.n % 64 == 0 and dc.act == 1)
-            if ok:                                  # nobody else may read the tensor that is no longer written
-                ok = not any(reads(p, db.y) for j, (kind, p) in enumerate(ops) if j != k + 1 and kind in ("conv", "conv_pair_first", "conv_pair_second"))
-                ok = ok and not any(kind in ("wino", "wino_reuse") and p[0] == db.y for kind, p in ops)
-            if not ok:
-                out.append(ops[k])
-                k += 1
-                continue
-            da = conv(k + 2)
-            if da is not None and not (da.kh == 1 and da.stride == 1 and da.x == dc.y and da.c == dc.n and da.n == 64 and not da.addend and da.act == 1):
-                da = None
-            out += [("bneck_first", db), ("bneck_second", dc)] + ([("bneck_third", da)] if da is not None else [])
-            k += 3 if da is not None else 2
-        return out
+    _fuse_bottlenecks = staticmethod(prog.fuse_bottlenecks)
+    _fuse_bias_grads = staticmethod(prog.fuse_bias_grads)
+    set_accumulate = staticmethod(prog.set_accumulate)
 
     def _chain_ops(self, plan, first=0):
         """Replace plan['ops'][first:] by ONE persistent launch (radnet_chain_build, include/radnet_hip.h): the same
@@ -743,18 +623,18 @@ class FasterRCNNEngine:
         h = C.c_void_p()
         # the static deal needs every workgroup of every chain that runs at the same time resident (4 per CU = 1 024 slots): one
         # chain per prefetch lane may be in flight, and the RPN / classifier lanes' launches need room beside them
-        lanes = max(1, getattr(self, "n_side_lanes", 1))
+        lanes = self.n_side_lanes
         cap = max(64, (4 * 256) // (lanes + 1))
         wgs = self.chain_wgs if self.chain_wgs > 0 else 512
         if wgs > cap:
-            if not getattr(self, "_chain_clamped", False):
+            if not self._chain_clamped:
                 self._chain_clamped = True
                 import sys
                 sys.stderr.write("radnet: RADNET_CHAIN_WGS=%d exceeds what %d concurrent chains can keep resident; using %d\n" % (wgs, lanes, cap))
             wgs = cap
         rc = self.lib.radnet_chain_build(self.ctx.h, C.cast(arr, C.c_void_p), len(sub), wgs, C.byref(h))
         if rc != 0:
-            if not getattr(self, "_chain_warned", False):
+            if not self._chain_warned:
                 self._chain_warned = True
                 import sys
                 sys.stderr.write("radnet: chain refused (%s); the layer program runs launch by launch\n" % self.lib.radnet_last_error(self.ctx.h).decode())
@@ -820,10 +700,8 @@ class FasterRCNNEngine:
             if isinstance(v, list):
                 lists.add(id(v))
                 lists.update(id(p[0]) for p in v if isinstance(p, tuple) and p and isinstance(p[0], list))     # bwd_parts
-        for gk in [k for k in self._graphs if k[0] in lists]:
-            del self._graphs[gk]
-        for ck in [k for k in self._compiled if k[0] in lists]:
-            del self._compiled[ck]
+        prog.evict(self._graphs, lists)
+        prog.evict(self._compiled, lists)
 
     def save_tuning(self, path):
         """Write the measured GEMM launch choices of this engine (one table for all lanes) to a text file."""
@@ -864,10 +742,9 @@ class FasterRCNNEngine:
         """Run a layer program on the current lane.  Programs are static (fixed buffers, fixed descriptors), so after one eager run -- which
         autotunes every new GEMM shape and builds its work-unit tables -- the launch sequence is recorded into a
         hipGraph and replayed: ~20 us of host time per launch (ctypes + hipLaunchKernel) become one graph launch, and
-        the host thread stays ahead of the GPU (tools/host_timeline.py).  Keyed by the program and the gradient
-        write modes of its wgrad descriptors (set_accumulate edits them in place)."""
-        key = (id(ops), id(self.ctx), tuple(p.dw_accumulate if kind in ("wgrad", "wgrad_bf16") else p[-1] for kind, p in ops
-                                            if kind in ("wgrad", "wgrad_bf16", "wino_wgrad")))
+        the host thread stays ahead of the GPU (tools/host_timeline.py).  Keyed by the program, the lane and the gradient
+        write modes of its ops (set_accumulate edits them in place)."""
+        key = (id(ops), id(self.ctx), prog.mode_key(ops))
         ent = self._graphs.get(key)
         if ent is None:
             # first run of this program: every new GEMM shape is measured here, so launches run one at a time
@@ -897,111 +774,8 @@ class FasterRCNNEngine:
         ent[1].replay()
 
     def _compile(self, ops):
-        """The launch list as a radnet_op array (include/radnet_hip.h): what radnet_program_run executes and what the composed
-        entry points (radnet_rpn_forward / radnet_predict_tile / radnet_train_step) take.  Cached per list and gradient write
-        mode (set_accumulate edits the Python descriptors in place; the array holds copies)."""
-        key = (id(ops), tuple(p.dw_accumulate if kind in ("wgrad", "wgrad_bf16") else (p[-1] if kind == "wino_wgrad" else p[6]) for kind, p in ops
-                              if kind in ("wgrad", "wgrad_bf16", "wino_wgrad", "colsum")))
-        ent = self._compiled.get(key)
-        if ent is not None:
-            return ent[0]
-        arr = (L.Op * max(len(ops), 1))()
-        ptr = lambda v: v.data_ptr() if hasattr(v, "data_ptr") else v
-        paired = False
-        for k, (kind, p) in enumerate(ops):
-            o = arr[k]
-            if paired:                              # the dgrad half of a pair: issued by the entry before (stays a no-op slot)
-                paired = False
-                o.kind = L.OP_NOP
-                continue
-            if kind == "conv_pair_first":           # branch2a + shortcut conv of a conv_block: one call (radnet_conv_fwd_pair), the second
-                o.kind = L.OP_CONV_FWD_PAIR         # descriptor rides in the following NOP slot
-                o.conv = p
-            elif kind == "conv_pair_second":
-                o.kind = L.OP_NOP
-                o.conv = p
-            elif kind == "bneck_first":             # 3x3 + 1x1 expand (+ next 1x1 reduce): one call, the other descriptors ride in the NOP slots behind
-                o.kind = L.OP_CONV_BNECK
-                o.conv = p
-                o.i[0] = 1 if k + 2 < len(ops) and ops[k + 2][0] == "bneck_third" else 0
-            elif kind in ("bneck_second", "bneck_third"):
-                o.kind = L.OP_NOP
-                o.conv = p
-            elif kind == "conv_bf16":              # bf16 modes: the layer's bf16 weight copy rides in p[0] / i[0], the K split in i[1]
-                wt, ldk, _, _ = self._bf16_w[p.w]
-                o.kind = L.OP_CONV_FWD_BF16
-                o.conv = p
-                o.p[0], o.i[0], o.i[1] = wt.data_ptr(), ldk, self._bf16_split(p)
-            elif kind == "dgrad_bf16":             # bf16-train: the layer's dgrad image rides in p[0] / i[0], the split of (tap, n) in i[1]
-                wd, ldkd, _, _ = self._bf16_wd[p.w]
-                o.kind = L.OP_CONV_DGRAD_BF16
-                o.conv = p
-                o.p[0], o.i[0] = wd.data_ptr(), ldkd
-                o.i[1] = int(self.lib.radnet_dgrad_bf16_pick_split(p.nb * p.h * p.w_, p.c, p.kh * p.kw * ((p.n + 7) // 8 * 8)))
-            elif kind == "wgrad_bf16":             # bf16-train: the split of the pixels in i[1]
-                o.kind = L.OP_CONV_WGRAD_BF16
-                o.conv = p
-                o.i[1] = int(self.lib.radnet_wgrad_bf16_pick_split(p.nb * p.oh * p.ow, p.n, p.kh * p.kw * p.c))
-            elif kind in ("conv", "dgrad", "wgrad"):
-                o.kind = {"conv": L.OP_CONV_FWD, "dgrad": L.OP_CONV_DGRAD, "wgrad": L.OP_CONV_WGRAD}[kind]
-                o.conv = p
-                # weight gradient and data gradient of one layer (same descriptor) -> one launch (radnet_conv_bwd)
-                if kind == "wgrad" and k + 1 < len(ops) and ops[k + 1][0] == "dgrad" and ops[k + 1][1] is p:
-                    o.kind = L.OP_CONV_BWD
-                    paired = True
-            elif kind == "maxpool":
-                x, y, nb, hh, ww, c, kk, st = p
-                o.kind = L.OP_MAXPOOL
-                o.p[0], o.p[1] = ptr(x), ptr(y)
-                o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5] = nb, hh, ww, c, kk, st
-            elif kind == "colsum":
-                g, m, n, ld, gs, out, acc = p
-                o.kind = L.OP_COLSUM
-                o.p[0], o.p[1], o.p[2] = ptr(g), ptr(gs), ptr(out)
-                o.i[0], o.i[1], o.i[2], o.i[3] = m, n, ld, acc
-            elif kind in ("wino", "wino_reuse"):
-                x, nb, hh, ww, c, n, V, U, M, T, scale, shift, act, y, ldy, form = p
-                o.kind = L.OP_WINO if kind == "wino" else L.OP_WINO_REUSE
-                for j, v in enumerate((x, V, U, M, scale, shift, y)):
-                    o.p[j] = ptr(v)
-                for j, v in enumerate((nb, hh, ww, c, n, T, act, ldy, form)):
-                    o.i[j] = v
-            elif kind == "wino_wgrad":
-                dy, nb, hh, ww, c, n, ld_dy, V, dZ, dU, T, dw, ldw, form, gscale, mode = p
-                o.kind = L.OP_WINO_WGRAD
-                for j, v in enumerate((dy, V, dZ, dU, dw, gscale)):
-                    o.p[j] = ptr(v)
-                for j, v in enumerate((nb, hh, ww, c, n, ld_dy, T, ldw, mode, form)):
-                    o.i[j] = v
-            elif kind == "scatter":
-                src, nb, oh, ow, c, st, hh, ww, mask, dst = p
-                o.kind = L.OP_SCATTER
-                o.p[0], o.p[1], o.p[2] = ptr(src), ptr(mask), ptr(dst)
-                for j, v in enumerate((nb, oh, ow, c, st, hh, ww)):
-                    o.i[j] = v
-            elif kind == "fill0":
-                dst, nbytes = p
-                o.kind = L.OP_FILL0
-                o.p[0] = ptr(dst)
-                o.i[0], o.i[1] = C.c_int32(nbytes & 0xFFFFFFFF).value, int(nbytes) >> 32
-            elif kind == "relu_mask":
-                g, act, n = p
-                o.kind = L.OP_RELU_MASK
-                o.p[0], o.p[1] = ptr(g), ptr(act)
-                o.i[0], o.i[1] = C.c_int32(n & 0xFFFFFFFF).value, int(n) >> 32
-            elif kind == "chain":
-                o.kind = L.OP_CHAIN
-                o.p[0] = p.value
-            elif kind == "roi_bwd":
-                dy, hh, ww, c, rois, r, ps, dF = p
-                o.kind = L.OP_ROI_BWD
-                o.p[0], o.p[1], o.p[2] = ptr(dy), ptr(rois), ptr(dF)
-                for j, v in enumerate((hh, ww, c, r, ps)):
-                    o.i[j] = v
-            else:
-                raise L.RadnetError("unknown op " + kind)
-        self._compiled[key] = (arr, ops)              # holds `ops` so its id stays unique
-        return arr
+        """The launch list as a radnet_op array (program.compile), cached per list and gradient write modes."""
+        return prog.compile(ops, self._compiled, self.precision, self.bf16.fwd.__getitem__, self.bf16.dgrad.__getitem__)
 
     def _run_eager(self, ops):
         """One native call per program (csrc/program.hip); Winograd layers are timed per layer inside it while ctx.timing is on
@@ -1009,35 +783,6 @@ class FasterRCNNEngine:
         rc = self.lib.radnet_program_run(self.ctx.h, self._compile(ops), len(ops))
         if rc != 0:
             self.ctx.check(rc, "radnet_program_run")
-
-    @staticmethod
-    def _fuse_bias_grads(ops):
-        """A bias-gradient column sum right after the wgrad of the same layer (same dy, pitch and scale) moves into
-        that wgrad launch (radnet_conv_desc.db): 12 launches of ~7 us less per train step."""
-        out = []
-        for kind, p in ops:
-            if kind == "colsum" and out and out[-1][0] == "wgrad":
-                d = out[-1][1]
-                g, m, n, ld, gs, db, _ = p
-                if d.dy == g and d.ld_dy == ld and d.n == n and (d.gscale or None) == (gs or None) and d.nb * d.oh * d.ow == m:
-                    d.db = db
-                    continue
-            out.append((kind, p))
-        return out
-
-    @staticmethod
-    def set_accumulate(ops, flag, prezeroed=False):
-        """Gradient write mode of a backward program: flag=False -> overwrite (self-contained; each split wgrad /
-        colsum zeroes its own slice), flag=True -> add.  prezeroed=True with flag=False: the caller zeroed the whole
-        arena with ONE memset, so the ~25 per-layer memsets disappear (dw_accumulate = 2)."""
-        v = 1 if flag else (2 if prezeroed else 0)
-        for kind, p in ops:
-            if kind in ("wgrad", "wgrad_bf16"):
-                p.dw_accumulate = v
-            elif kind == "wino_wgrad":
-                p[-1] = v
-            elif kind == "colsum":
-                p[6] = 1 if (flag or prezeroed) else 0
 
     # ------------------------------------------------------------------------------------------ forward pieces
     KERNEL_COPIES = os.environ.get("RADNET_KERNEL_COPIES", "1") == "1"
@@ -1158,17 +903,17 @@ class FasterRCNNEngine:
             dZ = torch.empty(P, T, c1.cout, dtype=torch.float32, device=dev)
             dU = torch.empty(P, c1.cin, c1.cout, dtype=torch.float32, device=dev)
             wino_keep += [dZ, dU]
-            wg1 = ("wino_wgrad", [dh.data_ptr(), nb, fh, fw, c1.cin, c1.cout, 512, V.data_ptr(), dZ.data_ptr(), dU.data_ptr(), T,
-                                  c1.dweight.data_ptr(), c1.ldw, c1.wino_m, None, 1])
+            wg1 = prog.wino_wgrad(dy=dh.data_ptr(), nb=nb, h=fh, w=fw, c=c1.cin, n=c1.cout, ld_dy=512, V=V.data_ptr(), dZ=dZ.data_ptr(), dU=dU.data_ptr(),
+                               T=T, dw=c1.dweight.data_ptr(), ldw=c1.ldw, form=c1.wino_m, gscale=None, mode=1)
         else:
             wg1 = ("wgrad", b1)
-        bwd = [("wgrad", b2), ("colsum", [dz.data_ptr(), M, RPN_LD, RPN_LD, None, ch.dbias.data_ptr(), 1]),
-               ("dgrad", b2), wg1, ("colsum", [dh.data_ptr(), M, 512, 512, None, c1.dbias.data_ptr(), 1])]      # M = all nb images
-        bwd = self._fuse_bias_grads(self._bf16_bwd_ops(bwd))
+        bwd = [("wgrad", b2), prog.colsum(g=dz.data_ptr(), m=M, n=RPN_LD, ld=RPN_LD, gscale=None, out=ch.dbias.data_ptr(), accumulate=1),
+               ("dgrad", b2), wg1, prog.colsum(g=dh.data_ptr(), m=M, n=512, ld=512, gscale=None, out=c1.dbias.data_ptr(), accumulate=1)]      # M = all nb images
+        bwd = self._backward_program(bwd)
         ws_bytes = int(self.lib.radnet_proposals_ws_bytes(M1 * self.A))
         # the re-prediction after Adam #1 (train.py:291) sees the same feature map: its input transform is already in V
-        refwd = self._bf16_ops([("wino_reuse", op1[1]) if op1[0] == "wino" else op1, ("conv", d2)])
-        plan = dict(fwd=self._bf16_ops([op1, ("conv", d2)]), refwd=refwd, bwd=bwd, b1=b1, h=hbuf, pred=pred, dz=dz, dh=dh, M=M1, nb=nb, fh=fh, fw=fw,
+        refwd = self._forward_program([prog.wino_reuse(op1) if op1[0] == "wino" else op1, ("conv", d2)])
+        plan = dict(fwd=self._forward_program([op1, ("conv", d2)]), refwd=refwd, bwd=bwd, b1=b1, h=hbuf, pred=pred, dz=dz, dh=dh, M=M1, nb=nb, fh=fh, fw=fw,
                     wino_keep=wino_keep,
                     prop_ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev),
                     R=torch.zeros(1024, 4, dtype=torch.int64, device=dev), Rp=torch.zeros(1024, dtype=torch.float32, device=dev),
@@ -1230,13 +975,13 @@ class FasterRCNNEngine:
         next step's backward accumulates into zeros without a memset (arenas start zeroed, Arena.finalize)."""
         self.check_trainable("adam")
         arena.t += 1
-        is_head = arena is getattr(self, "head_arena", None)
-        fused = (is_head and getattr(self, "head_bias_len", 0) > 0 and self.head_bias_off % 4 == 0
+        is_head = arena is self.head_arena
+        fused = (is_head and self.head_bias_len > 0 and self.head_bias_off % 4 == 0
                  and self.head_bias_len % 4 == 0 and os.environ.get("RADNET_NO_ADAM_AFFINE", "0") != "1")
-        wino = self._head_adam_wino() if is_head and getattr(self, "head_train_wino", False) else None
-        if getattr(self, "precision", "fp32") in MIXED_PRECISIONS:
+        wino = self._head_adam_wino() if is_head and self.head_train_wino else None
+        if self.precision in MIXED_PRECISIONS:
             # Adam (+ the folded shifts on the head arena) and the bf16 images of the arena's convs, one launch
-            arr, n_l = self._adam_bf16_layers(arena)
+            arr, n_l = self.bf16.adam_layers(arena)
             self.ctx.check(self.lib.radnet_adam_step_bf16(
                 self.ctx.h, arena.p.data_ptr(), arena.g.data_ptr(), arena.m.data_ptr(), arena.v.data_ptr(), C.c_int64(arena.n), arena.t, C.c_float(self.lr),
                 C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1 if zero_grad else 0,
@@ -1245,11 +990,11 @@ class FasterRCNNEngine:
                 arr, n_l), "radnet_adam_step_bf16")
             if fused:
                 self._head_shift_fresh = True
-            reg = self._bf16_wd_arena.get(id(arena))
-            if reg is not None and reg[1]:
+            reg = self.bf16.dgrad_arena.get(id(arena))
+            if reg is not None and reg.count:
                 # bf16-train: the dgrad images of this arena's layers, ONE cast launch over the registry behind Adam on the same lane
                 # (the lane whose backward programs read them); radnet_adam_step_bf16 keeps its signature and its 16-layer cap
-                self.ctx.check(self.lib.radnet_weights_to_bf16_dgrad_arena(self.ctx.h, arena.p.data_ptr(), C.c_int64(arena.n), reg[0], reg[1]),
+                self.ctx.check(self.lib.radnet_weights_to_bf16_dgrad_arena(self.ctx.h, arena.p.data_ptr(), C.c_int64(arena.n), reg.array, reg.count),
                                "radnet_weights_to_bf16_dgrad_arena")
             return
         if wino is not None:      # Adam #2 + folded shifts + the Winograd filters of the classifier's 3x3 convs, one launch
@@ -1273,9 +1018,9 @@ class FasterRCNNEngine:
                           C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1 if zero_grad else 0)
         if arena is self.rpn_arena:
             self._refresh_winograd(["rpn_conv1"])          # its forward runs on the transformed filter
-        elif arena is getattr(self, "head_arena", None):
+        elif arena is self.head_arena:
             self._inference_filters_stale = True           # transformed lazily, by the next inference pass (if any)
-            if getattr(self, "head_train_wino", False):    # (the fused pass above could not be used: dense-kernel check failed)
+            if self.head_train_wino:    # (the fused pass above could not be used: dense-kernel check failed)
                 self._refresh_winograd(list(self.INFERENCE_WINOGRAD_LAYERS))
                 self._inference_filters_stale = False
 
@@ -1288,8 +1033,8 @@ class FasterRCNNEngine:
         if key not in shared:
             shared[key] = (torch.empty(P, T, c.cout, dtype=torch.float32, device=self.dev), torch.empty(P, c.cin, c.cout, dtype=torch.float32, device=self.dev))
         dZ, dU = shared[key]
-        return ("wino_wgrad", [dy.data_ptr(), nb, h, w, c.cin, c.cout, ld_dy, V.data_ptr(), dZ.data_ptr(), dU.data_ptr(), T, c.dweight.data_ptr(), c.ldw,
-                               c.wino_m, c.scale.data_ptr() if c.scale is not None else None, 1])
+        return prog.wino_wgrad(dy=dy.data_ptr(), nb=nb, h=h, w=w, c=c.cin, n=c.cout, ld_dy=ld_dy, V=V.data_ptr(), dZ=dZ.data_ptr(), dU=dU.data_ptr(), T=T,
+                            dw=c.dweight.data_ptr(), ldw=c.ldw, form=c.wino_m, gscale=c.scale.data_ptr() if c.scale is not None else None, mode=1)
 
     def _head_adam_wino(self):
         """(radnet_adam_wino[], n) of the classifier's 3x3 kernels for radnet_adam_step_fused, or None when one of them is not a dense
@@ -1333,10 +1078,9 @@ class FasterRCNNEngine:
     def count_to_host(self, n_dev):
         """The 4 bytes of a device proposal count into a pinned word, enqueued on the current lane.  Returns (pinned int32 [1],
         event): the reader waits for the event -- i.e. for this lane up to here, not for whatever the other lanes run."""
-        pins = self.__dict__.setdefault("_count_pins", {})
-        h = pins.get(n_dev.data_ptr())
+        h = self._count_pins.get(n_dev.data_ptr())
         if h is None:
-            h = pins[n_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32).pin_memory()
+            h = self._count_pins[n_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._copy(h, n_dev)
         return h, self.mark()
 
@@ -1432,7 +1176,7 @@ class FasterRCNNEngine:
         y1, y2 = buf(R, self.nc), buf(R, 2 * self.nreg)
         tail_scratch = torch.zeros(int(self.lib.radnet_head_tail_scratch_bytes(R)), dtype=torch.uint8, device=dev)
         keep.append(tail_scratch)
-        fwd = self._bf16_ops(fwd)
+        fwd = self._forward_program(fwd)
         if not training:
             plan = dict(R=R, rois=rois, pooled=pooled, fwd=fwd, blocks=blocks, y5=cur, hw=h * w, M=M, feat=feat, pcls=pcls, pregr=pregr,
                         F=F, fh=fh, fw=fw, keep=keep, groups=groups, tail_scratch=tail_scratch)
@@ -1452,6 +1196,9 @@ class FasterRCNNEngine:
             ca, cb, cc = (self.convs[n] for n in B["names"][:3])
             g_b, g_a = buf(M, f2), buf(M, f1)
 
+            def bias_grad(g, n, conv):
+                return prog.colsum(g=g.data_ptr(), m=M, n=n, ld=n, gscale=conv.scale.data_ptr(), out=conv.dbias.data_ptr(), accumulate=1)
+
             def bdesc(fdesc, conv, dy, ld_dy, dx=None, ld_dx=0, dx_add=None, dx_mask=None):
                 d = L.ConvDesc.from_buffer_copy(fdesc)
                 d.dy, d.ld_dy, d.gscale = dy.data_ptr(), ld_dy, conv.scale.data_ptr()
@@ -1466,25 +1213,25 @@ class FasterRCNNEngine:
 
             B["g_out"], B["g_a"], B["g_b"] = g_out, g_a, g_b      # gradients w.r.t. this block's output / 2a / 2b outputs
             dC = bdesc(B["dc"], cc, g_out, f3, g_b, f2, None, B["b"])
-            bwd += [("wgrad", dC), ("colsum", [g_out.data_ptr(), M, f3, f3, cc.scale.data_ptr(), cc.dbias.data_ptr(), 1]), ("dgrad", dC)]
+            bwd += [("wgrad", dC), bias_grad(g_out, f3, cc), ("dgrad", dC)]
             dB = bdesc(B["db"], cb, g_b, f2, g_a, f1, None, B["a"])
             wg_b = self._wino_wgrad_op(cb, B.get("wino_v"), g_b, f2, R, B["db"].oh, B["db"].ow, shared_wg) if B.get("wino_v") is not None else None
-            bwd += [wg_b or ("wgrad", dB), ("colsum", [g_b.data_ptr(), M, f2, f2, cb.scale.data_ptr(), cb.dbias.data_ptr(), 1]), ("dgrad", dB)]
+            bwd += [wg_b or ("wgrad", dB), bias_grad(g_b, f2, cb), ("dgrad", dB)]
             if B["first"]:
                 dA = bdesc(B["da"], ca, g_a, f1)
-                bwd += [("wgrad", dA), ("colsum", [g_a.data_ptr(), M, f1, f1, ca.scale.data_ptr(), ca.dbias.data_ptr(), 1])]
+                bwd += [("wgrad", dA), bias_grad(g_a, f1, ca)]
                 cs = self.convs[B["names"][3]]
                 dS = bdesc(B["ds"], cs, g_out, f3)
-                bwd += [("wgrad", dS), ("colsum", [g_out.data_ptr(), M, f3, f3, cs.scale.data_ptr(), cs.dbias.data_ptr(), 1])]
+                bwd += [("wgrad", dS), bias_grad(g_out, f3, cs)]
             else:
                 g_prev = buf(M, f3)            # grad w.r.t. this block's input = previous block's output (post-ReLU)
                 dA = bdesc(B["da"], ca, g_a, f1, g_prev, f3, g_out, B["x"])
-                bwd += [("wgrad", dA), ("colsum", [g_a.data_ptr(), M, f1, f1, ca.scale.data_ptr(), ca.dbias.data_ptr(), 1]), ("dgrad", dA)]
+                bwd += [("wgrad", dA), bias_grad(g_a, f1, ca), ("dgrad", dA)]
                 g_out = g_prev
             # gradient slice of this block's kernels: contiguous in the arena (kernels are laid out in forward order)
             k0 = self.head_arena.offsets[B["names"][0] + "/kernel"][0]
             kl, sl = self.head_arena.offsets[B["names"][3 if B["first"] else 2] + "/kernel"]
-            bwd_parts.append((self._fuse_bias_grads(self._bf16_bwd_ops(bwd[part_from:])), (k0, kl + _pad4(sl))))
+            bwd_parts.append((self._backward_program(bwd[part_from:]), (k0, kl + _pad4(sl))))
         bwd = [op for part, _ in bwd_parts for op in part]
         cover = sorted(sl for _, sl in bwd_parts)
         if cover[0][0] != 0 or cover[-1][1] != self.head_bias_off or any(a[1] != b[0] for a, b in zip(cover, cover[1:])):
@@ -1503,9 +1250,9 @@ class FasterRCNNEngine:
         """Slices [lo, hi) of the flat head gradient arena in the order head_backward(on_part=...) completes them (last
         block first), or None when this engine's head backward is not cut per block.  Every rank of a data-parallel job
         must issue the same sequence of collectives, also a rank whose images all skipped their classifier step."""
-        if not hasattr(self, "_head_slices"):
+        if self._head_slices is False:
             self._head_slices = None
-            names = getattr(self, "head_conv_names", [])
+            names = self.head_conv_names
             blocks = []
             for n in names:                     # res5a_branch2a ... -> block prefix 'res5a'
                 b = n.split("_")[0]

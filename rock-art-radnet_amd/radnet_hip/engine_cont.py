@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import program as prog
 from .engine import PRECISIONS, RES_STAGES, Arena, FasterRCNNEngine
 
 
@@ -41,6 +42,9 @@ class ContEngine(FasterRCNNEngine):
         if precision != "fp32":
             raise NotImplementedError("precision=%r is not implemented for the cont_train.py mode (its gradients flow through stages 3/4)"
                                       % (precision,))
+        self._s34_wino = None        # _s34_adam_wino(): not worked out yet
+        self._base_of_F = {}         # feature-map pointer -> the base plan that produces it (its dF buffer)
+        self._wg_scratch = {}        # dZ / dU scratch of the Winograd-domain weight gradients, one set for layers of one shape
         super().__init__(C_cfg, device_index, n_classes, bce_mode, lr, autotune)
 
     # ------------------------------------------------------------------------------------------ layers
@@ -115,7 +119,7 @@ class ContEngine(FasterRCNNEngine):
 
     def _s34_adam_wino(self):
         """(radnet_adam_wino[], n) of the stage-3/4 3x3 kernels whose forward runs on Winograd F(4x4) filters, or None."""
-        if getattr(self, "_s34_wino", None) is None:
+        if self._s34_wino is None:
             ent = []
             if self.S34_WINOGRAD and self.use_winograd and self.s34_bias_off % 4 == 0 and self.s34_bias_len % 4 == 0:
                 for name in self.WINOGRAD_F4_LAYERS:
@@ -159,7 +163,7 @@ class ContEngine(FasterRCNNEngine):
         stem.append(("conv", d))
         ph, pw = (oh - 3) // 2 + 1, (ow - 3) // 2 + 1
         p = buf(nb, ph, pw, 64)
-        stem.append(("maxpool", (y, p, nb, oh, ow, 64, 3, 2)))
+        stem.append(prog.maxpool(x=y, y=p, nb=nb, h=oh, w=ow, c=64, k=3, stride=2))
         cur, h, w = p, ph, pw
         for st, bls, (f1, f2, f3), stride in RES_STAGES:
             ops = s34 if st >= 3 else stem
@@ -194,13 +198,11 @@ class ContEngine(FasterRCNNEngine):
                                        cin=ca.cin, f=(f1, f2, f3), stride=ca.stride, names=(b + "2a", b + "2b", b + "2c", b + "1")))
                 cur, h, w = out, oh, ow
         F = cur
-        if self.bneck_fuse and not self.use_chain:
-            stem[:] = self._fuse_bottlenecks(stem)
+        stem[:] = self._forward_program(stem, bottlenecks=self.bneck_fuse and not self.use_chain)
         dF = buf(nb * h * w, 1024)                # dL/dF, the producer's ReLU mask (F > 0) already applied
         bwd = self._blocks_backward(blocks, dF, nb, buf, lowest_stage=3)
         plan = dict(ops=stem + s34, ops_stem=stem, ops_s34=s34, bwd34=bwd, x=x, F=F, dF=dF, fh=h, fw=w, keep=keep, blocks=blocks)
         self._plans[key] = plan
-        self._base_of_F = getattr(self, "_base_of_F", {})
         self._base_of_F[F.data_ptr()] = plan
         return plan
 
@@ -240,9 +242,8 @@ class ContEngine(FasterRCNNEngine):
             bwd += [("wgrad", dC), ("dgrad", dC)]
             dB = self._bdesc(B["db"], cb, g_b, f2, g_a, f1, None, B["a"])
             if B.get("wino_v") is not None:        # weight gradient in the Winograd domain (4x fewer flops), bias gradient as a column sum
-                self._wg_scratch = getattr(self, "_wg_scratch", {})
                 bwd += [self._wino_wgrad_op(cb, B["wino_v"], g_b, f2, nb, B["oh"], B["ow"], self._wg_scratch),
-                        ("colsum", [g_b.data_ptr(), M, f2, f2, cb.scale.data_ptr(), cb.dbias.data_ptr(), 1]), ("dgrad", dB)]
+                        prog.colsum(g=g_b.data_ptr(), m=M, n=f2, ld=f2, gscale=cb.scale.data_ptr(), out=cb.dbias.data_ptr(), accumulate=1), ("dgrad", dB)]
             else:
                 bwd += [("wgrad", dB), ("dgrad", dB)]
             if B["first"]:
@@ -259,7 +260,8 @@ class ContEngine(FasterRCNNEngine):
                     dSc = self._bdesc(self._compact(B["ds"]), cs, g_out, f3, gs_c, cin, ga_c)
                     g_prev = buf(nb * B["h"] * B["w"], cin)
                     bwd += [("dgrad", dAc), ("dgrad", dSc),
-                            ("scatter", (gs_c.data_ptr(), nb, B["oh"], B["ow"], cin, B["stride"], B["h"], B["w"], B["x"].data_ptr(), g_prev.data_ptr()))]
+                            prog.scatter(src=gs_c.data_ptr(), nb=nb, oh=B["oh"], ow=B["ow"], c=cin, stride=B["stride"], h=B["h"], w=B["w"],
+                                      mask=B["x"].data_ptr(), dst=g_prev.data_ptr())]
                     g_out = g_prev
             else:
                 g_prev = buf(M, f3)
@@ -315,10 +317,10 @@ class ContEngine(FasterRCNNEngine):
             dF = base["dF"]
             hp["dpooled"] = dpooled
             hp["pool_bwd"] = [("dgrad", dAc), ("dgrad", dSc),
-                              ("scatter", (gs_c.data_ptr(), R, 7, 7, 1024, 2, 14, 14, None, dpooled.data_ptr())),
-                              ("fill0", (dF.data_ptr(), dF.numel() * 4)),
-                              ("roi_bwd", (dpooled.data_ptr(), fh, fw, 1024, hp["rois"].data_ptr(), R, 14, dF.data_ptr())),
-                              ("relu_mask", (dF.data_ptr(), F.data_ptr(), dF.numel()))]
+                              prog.scatter(src=gs_c.data_ptr(), nb=R, oh=7, ow=7, c=1024, stride=2, h=14, w=14, mask=None, dst=dpooled.data_ptr()),
+                              prog.fill0(dst=dF.data_ptr(), nbytes=dF.numel() * 4),
+                              prog.roi_bwd(dy=dpooled.data_ptr(), h=fh, w=fw, c=1024, rois=hp["rois"].data_ptr(), r=R, ps=14, dF=dF.data_ptr()),
+                              prog.relu_mask(g=dF.data_ptr(), act=F.data_ptr(), n=dF.numel())]
         return hp
 
     def head_backward(self, hp, accumulate=False, loss_out=None):

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import program as prog
 from .engine import Arena, ConvLayer, FasterRCNNEngine, RPN_LD
 
 VGG_BLOCKS = ((1, 2, 64), (2, 2, 128), (3, 3, 256), (4, 3, 512), (5, 3, 512))
@@ -32,6 +33,7 @@ class VGG16Engine(FasterRCNNEngine):
     CROP_AHEAD = False           # (its head_forward crops 7x7 itself)
     supports_batched = False     # the mini-batch runs image by image (fc head plan is per feature map)
     feat_len = staticmethod(vgg_feat_len)
+    head_bias_off = head_bias_len = 0      # no BN in the fc head: no folded shifts for adam() to refresh with the head arena
 
     # ------------------------------------------------------------------------------------------ layers
     def _build_layers(self):
@@ -157,7 +159,7 @@ class VGG16Engine(FasterRCNNEngine):
             if b < 5:
                 ph, pw = h // 2, w // 2
                 p = buf(nb, ph, pw, ch)
-                ops.append(("maxpool", (cur, p, nb, h, w, ch, 2, 2)))
+                ops.append(prog.maxpool(x=cur, y=p, nb=nb, h=h, w=w, c=ch, k=2, stride=2))
                 cur, h, w = p, ph, pw
         plan = dict(ops=ops, x=x, F=cur, fh=h, fw=w, keep=keep)
         self._plans[key] = plan
@@ -206,9 +208,9 @@ class VGG16Engine(FasterRCNNEngine):
         b1 = L.ConvDesc.from_buffer_copy(fd1)
         b1.dy, b1.ld_dy, b1.gscale = g1.data_ptr(), 4096, None
         b1.dw, b1.dw_accumulate = f1.dweight.data_ptr(), 1
-        bwd_a = [("wgrad", b2), ("colsum", [g2.data_ptr(), R, 4096, 4096, None, f2.dbias.data_ptr(), 1]), ("dgrad", b2)]
-        bwd_b = [("wgrad", b1), ("colsum", [g1.data_ptr(), R, 4096, 4096, None, f1.dbias.data_ptr(), 1])]
-        bwd_a, bwd_b = self._fuse_bias_grads(bwd_a), self._fuse_bias_grads(bwd_b)
+        bwd_a = [("wgrad", b2), prog.colsum(g=g2.data_ptr(), m=R, n=4096, ld=4096, gscale=None, out=f2.dbias.data_ptr(), accumulate=1), ("dgrad", b2)]
+        bwd_b = [("wgrad", b1), prog.colsum(g=g1.data_ptr(), m=R, n=4096, ld=4096, gscale=None, out=f1.dbias.data_ptr(), accumulate=1)]
+        bwd_a, bwd_b = self._backward_program(bwd_a), self._backward_program(bwd_b)
         plan = dict(R=R, rois=rois, pooled=pooled, fwd1=[("conv", fd1)], fwd2=[("conv", fd2)], bwd=bwd_a + bwd_b, bwd_a=bwd_a, bwd_b=bwd_b,
                     h1=h1, d1=d1, h2=h2, d2=d2, m1=m1, m2=m2, zero=zero, feat=d2, pcls=pcls, pregr=pregr, y1=y1, y2=y2, dz=dz, g2=g2, g1=g1,
                     F=F, fh=fh, fw=fw, keep=keep)

@@ -1,7 +1,7 @@
 """bf16-train mode, host side (no GPU needed): the backward entry points and the dgrad-image registry struct are declared, exported
 and bound with the header's layout, the program ops are 18 / 19 and documented, the split rules are the documented fixed functions,
 and precision="bf16-train" passes the argument checks of FasterRCNNEngine / build_models before any device is touched -- while
-VGG16, the cont_train.py mode and NativeTrainStep refuse it.  The engine's op passes are exercised on a device-free stand-in."""
+VGG16, the cont_train.py mode and NativeTrainStep refuse it.  The op passes (radnet_hip.program) need no device and no engine."""
 import ctypes as C
 import os
 import re
@@ -190,22 +190,19 @@ def _desc(**kw):
 
 
 def test_bwd_op_pass_bias_fusion_pairing_and_accumulate_keys():
-    """_bf16_bwd_ops on a stand-in engine (no device): which ops become bf16, that _fuse_bias_grads leaves their column sums alone,
-    that set_accumulate reaches them, and that every other precision keeps its list."""
-    from radnet_hip.engine import FasterRCNNEngine as E
-    made = []
-    conv = types.SimpleNamespace(weight=types.SimpleNamespace(data_ptr=lambda: 0x1000))
+    """program.bf16_backward: which ops become bf16, that fuse_bias_grads leaves their column sums alone, that set_accumulate
+    reaches them, and that every other precision keeps its list."""
+    from radnet_hip import program as E
+    made = []                                             # the weight pointers a dgrad image was asked for
     d1, d2, d3 = _desc(), _desc(stride=2, h=14, w_=14), _desc(c=4, n=64, ld_dy=64)
     ops = [("wgrad", d1), ("colsum", [1, 49, 2048, 2048, None, 2, 1]), ("dgrad", d1), ("wgrad", d2), ("dgrad", d2), ("wgrad", d3), ("dgrad", d3),
            ("colsum", [1, 49, 64, 64, None, 3, 1])]
     for precision in ("fp32", "bf16", "bf16-mixed"):
-        eng = types.SimpleNamespace(precision=precision)
-        assert E._bf16_bwd_ops(eng, ops) is ops
-    eng = types.SimpleNamespace(precision="bf16-train", convs={"x": conv}, _bf16_dgrad_weights=made.append)
-    out = E._bf16_bwd_ops(eng, ops)
+        assert E.bf16_backward(ops, precision, made.append) is ops
+    out = E.bf16_backward(ops, "bf16-train", made.append)
     assert [k for k, _ in out] == ["wgrad_bf16", "colsum", "dgrad_bf16", "wgrad_bf16", "dgrad", "wgrad", "dgrad_bf16", "colsum"]
-    assert made == [conv, conv]                           # a dgrad image per bf16 data gradient; the stride-2 dgrad and the 4-channel wgrad stay fp32
-    fused = E._fuse_bias_grads(out)
+    assert made == [0x1000, 0x1000]                       # a dgrad image per bf16 data gradient; the stride-2 dgrad and the 4-channel wgrad stay fp32
+    fused = E.fuse_bias_grads(out)
     assert [k for k, _ in fused] == [k for k, _ in out] and not d1.db, "a bf16 weight gradient keeps its exact fp32 column sum launch"
     E.set_accumulate(out, False, prezeroed=True)
     assert d1.dw_accumulate == 2 and d2.dw_accumulate == 2 and d3.dw_accumulate == 2 and out[1][1][6] == 1

@@ -69,9 +69,8 @@ class FakeEngine:
     def anchor_targets_finish(self, tp):
         return None, None, 0
 
-    @staticmethod
-    def set_accumulate(ops, flag, prezeroed=False):
-        pass
+    from radnet_hip.program import set_accumulate
+    set_accumulate = staticmethod(set_accumulate)             # the real one (the stand-in's programs are empty lists)
 
     def rpn_backward(self, rp, ycls, yregr, loss_out=None):
         self.rpn_arena.g += float(self.rank + 1)

@@ -135,7 +135,8 @@ def test_adam_bf16_bit_identical_real_arenas(ctx, mixed_eng):
     eng = mixed_eng
     rs = np.random.RandomState(1)
     for arena, expect in ((eng.rpn_arena, 2), (eng.head_arena, 10)):
-        arr, n_l = eng._adam_bf16_layers(arena)
+        reg = eng.bf16.adam_layers(arena)
+        arr, n_l = reg.array, reg.count
         assert n_l == expect
         rows = [(arr[j].off, arr[j].k, arr[j].n, arr[j].ldw, arr[j].ldk) for j in range(n_l)]
         is_head = arena is eng.head_arena
@@ -348,11 +349,11 @@ def test_training_step_against_oracle(H, W, monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------------ 4. / 5. reproducibility, images
 def _images_match(eng):
-    for wt, ldk, c, n in eng._bf16_w.values():
-        ref = torch.empty_like(wt)
-        eng.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, n, c.ldw, ref, ldk)
+    for im in eng.bf16.fwd.values():
+        c, ref = im.conv, torch.empty_like(im.wt)
+        eng.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, im.n, c.ldw, ref, im.ldk)
         torch.cuda.synchronize()
-        assert torch.equal(ref, wt), c.name
+        assert torch.equal(ref, im.wt), c.name
 
 
 def _run_steps(batches, prefetch, tune, defer=None):
@@ -376,7 +377,7 @@ def _run_steps(batches, prefetch, tune, defer=None):
         import tempfile
         tune[0] = tempfile.mktemp(suffix=".txt")
         eng.save_tuning(tune[0])
-    images = {c.name: wt.cpu().numpy().copy() for wt, _, c, _ in eng._bf16_w.values()}
+    images = {im.conv.name: im.wt.cpu().numpy().copy() for im in eng.bf16.fwd.values()}
     return eng, losses, eng.get_weights(), images
 
 
@@ -456,8 +457,8 @@ def test_fit_validate_and_save_load(tmp_path):
     # and back into a bf16-mixed engine: the images are rewritten
     _, _, a16, _, _ = M.build_models(_cfg(300), precision="bf16-mixed")
     e16 = a16._s.eng
-    e16._adam_bf16_layers(e16.rpn_arena)
-    e16._adam_bf16_layers(e16.head_arena)                    # the trainable images exist before the load
+    e16.bf16.adam_layers(e16.rpn_arena)
+    e16.bf16.adam_layers(e16.head_arena)                     # the trainable images exist before the load
     a16.load_weights(path, by_name=True)
     _images_match(a16._s.eng)
 

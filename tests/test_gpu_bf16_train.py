@@ -449,17 +449,17 @@ DGRAD_LAYERS = sorted(["rpn_heads"] + ["res5%s_branch2%s" % (b, k) for b in "abc
 
 
 def _images_match(eng):
-    assert eng._bf16_w and sorted(c.name for _, _, c, _ in eng._bf16_wd.values()) == DGRAD_LAYERS
-    for wt, ldk, c, n in eng._bf16_w.values():
-        ref = torch.empty_like(wt)
-        eng.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, n, c.ldw, ref, ldk)
+    assert eng.bf16.fwd and sorted(im.conv.name for im in eng.bf16.dgrad.values()) == DGRAD_LAYERS
+    for im in eng.bf16.fwd.values():
+        c, ref = im.conv, torch.empty_like(im.wt)
+        eng.ctx.call("radnet_weights_to_bf16", c.weight, c.kh * c.kh * c.cin, im.n, c.ldw, ref, im.ldk)
         torch.cuda.synchronize()
-        assert torch.equal(ref, wt), c.name
-    for wd, ldkd, c, n in eng._bf16_wd.values():
-        ref = torch.empty_like(wd)
-        eng.ctx.call("radnet_weights_to_bf16_dgrad", c.weight, c.kh * c.kh, c.cin, n, c.ldw, ref, ldkd)
+        assert torch.equal(ref, im.wt), c.name
+    for im in eng.bf16.dgrad.values():
+        c, ref = im.conv, torch.empty_like(im.wd)
+        eng.ctx.call("radnet_weights_to_bf16_dgrad", c.weight, c.kh * c.kh, c.cin, im.n, c.ldw, ref, im.ldkd)
         torch.cuda.synchronize()
-        assert torch.equal(ref, wd), "dgrad image of " + c.name
+        assert torch.equal(ref, im.wd), "dgrad image of " + c.name
 
 
 def _run_steps(batches, prefetch, tune, defer=None):
@@ -483,8 +483,8 @@ def _run_steps(batches, prefetch, tune, defer=None):
         import tempfile
         tune[0] = tempfile.mktemp(suffix=".txt")
         eng.save_tuning(tune[0])
-    images = {c.name: wt.cpu().numpy().copy() for wt, _, c, _ in eng._bf16_w.values()}
-    images.update({"d:" + c.name: wd.cpu().numpy().copy() for wd, _, c, _ in eng._bf16_wd.values()})
+    images = {im.conv.name: im.wt.cpu().numpy().copy() for im in eng.bf16.fwd.values()}
+    images.update({"d:" + im.conv.name: im.wd.cpu().numpy().copy() for im in eng.bf16.dgrad.values()})
     return eng, losses, eng.get_weights(), images
 
 

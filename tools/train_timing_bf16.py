@@ -59,7 +59,8 @@ def layer_table(eng, eng32, nb):
         if (M, N, K, d.kh, d.stride) in seen:
             continue
         seen.add((M, N, K, d.kh, d.stride))
-        wt, ldk, c, _ = eng._bf16_w[d.w]
+        im = eng.bf16.fwd[d.w]
+        wt, ldk, c = im.wt, im.ldk, im.conv
         s = int(eng.lib.radnet_conv_bf16_pick_split(M, N, K))
         d32 = L.ConvDesc.from_buffer_copy(d)
         d32.w = eng32.convs[c.name].weight.data_ptr()
@@ -111,7 +112,7 @@ def backward_table(eng, eng32, nb):
         d32.dw = eng32.convs[c.name].dweight.data_ptr()
         d32.db = None
         if kind == "dgrad_bf16":
-            wd, ldkd, _, _ = eng._bf16_wd[d.w]
+            wd, ldkd = eng.bf16.dgrad[d.w].wd, eng.bf16.dgrad[d.w].ldkd
             s = int(eng.lib.radnet_dgrad_bf16_pick_split(d.nb * d.h * d.w_, d.c, d.kh * d.kw * ((d.n + 7) // 8 * 8)))
             f32 = t(lambda: eng32.ctx.check(eng32.lib.radnet_conv_dgrad(eng32.ctx.h, C.byref(d32)), "dgrad"))
             b16 = t(lambda: eng.ctx.check(eng.lib.radnet_conv_dgrad_bf16_split(eng.ctx.h, C.byref(d), wd.data_ptr(), ldkd, s), "dgrad_bf16"))
