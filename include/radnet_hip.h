@@ -204,9 +204,14 @@ int radnet_conv_fwd_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint1
  * radnet_conv_fwd_bf16 bit for bit; at most 64 and the number of 32-deep K tiles.  The split changes the summation order, so
  * results differ from ksplit = 1 within the rounding of an fp32 sum.
  * radnet_conv_bf16_pick_split: the split the bf16-mixed engine uses, a fixed function of (M = nb*oh*ow, N, K = kh*kw*c): the
- * smallest power of two (at most 16) that gives >= 256 workgroups, doubled only while every slice keeps >= 8 K tiles. */
+ * smallest power of two (at most 16) that gives >= 256 workgroups, doubled only while every slice keeps >= 8 K tiles.
+ * radnet_conv_bf16_tile_shape: the output tile *bm x *bn (128x128, 128x64 or 64x64) every bf16 matrix-core conv launch uses for an
+ * output of rows x cols, and as return value the number of such tiles (0 and nothing written for an empty output or a null pointer).
+ * Forward: (M, n); radnet_conv_dgrad_bf16: (P = nb*h*w, c); radnet_conv_wgrad_bf16: (K = kh*kw*c, n).  Needs no device.  The slabs of
+ * a split launch take tiles * slices * bm * bn * 4 bytes of the context's workspace. */
 int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wt, int32_t ldk, int32_t ksplit);
 int32_t radnet_conv_bf16_pick_split(int64_t m, int32_t n, int32_t k);
+int64_t radnet_conv_bf16_tile_shape(int64_t rows, int32_t cols, int32_t* bm, int32_t* bn);
 
 /* ---- convolution backward on bf16 matrix cores (csrc/conv_bf16_bwd.hip; engine precision "bf16-train") ---------------
  * The backward semantics of radnet_conv_dgrad / radnet_conv_wgrad with bf16 operands and fp32 accumulation.  With

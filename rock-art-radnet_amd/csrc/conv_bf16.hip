@@ -308,19 +308,29 @@ extern "C" int radnet_weights_to_bf16(radnet_ctx* ctx, const float* w, int32_t k
   return RADNET_OK;
 }
 
-// output tile of the launch: a fixed rule of (M, N) -- the largest tile that still gives every CU a workgroup (0: 128x128, 1: 128x64, 2: 64x64)
-static int bf16_tile_shape(long long M, int N, long long* tiles) {
-  const long long t128 = (long long)radnet_cdiv(M, 128) * radnet_cdiv(N, 128), t128x64 = (long long)radnet_cdiv(M, 128) * radnet_cdiv(N, 64);
-  if (N > 64 && t128 >= 256) { *tiles = t128; return 0; }
+// output tile of the launch: a fixed rule of (rows, cols) -- the largest tile that still gives every CU a workgroup (0: 128x128, 1: 128x64,
+// 2: 64x64).  The ONE copy of the rule: the forward, both backward launchers (conv_bf16_bwd.hip) and radnet_conv_bf16_tile_shape use it.
+int radnet_bf16_tile_shape(long long rows, int cols, long long* tiles) {
+  const long long t128 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 128), t128x64 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 64);
+  if (cols > 64 && t128 >= 256) { *tiles = t128; return 0; }
   if (t128x64 >= 256) { *tiles = t128x64; return 1; }
-  *tiles = (long long)radnet_cdiv(M, 64) * radnet_cdiv(N, 64);
+  *tiles = (long long)radnet_cdiv(rows, 64) * radnet_cdiv(cols, 64);
   return 2;
+}
+
+extern "C" int64_t radnet_conv_bf16_tile_shape(int64_t rows, int32_t cols, int32_t* bm, int32_t* bn) {
+  if (rows <= 0 || cols <= 0 || !bm || !bn) return 0;
+  long long tiles = 0;
+  const int shape = radnet_bf16_tile_shape(rows, cols, &tiles);
+  *bm = shape == 2 ? 64 : 128;
+  *bn = shape == 0 ? 128 : 64;
+  return tiles;
 }
 
 extern "C" int32_t radnet_conv_bf16_pick_split(int64_t M, int32_t N, int32_t K) {
   if (M <= 0 || N <= 0 || K <= 0) return 1;
   long long tiles = 0;
-  bf16_tile_shape(M, N, &tiles);
+  radnet_bf16_tile_shape(M, N, &tiles);
   const long long nkt = (K + BK - 1) / BK;
   int s = 1;
   while (tiles * s < 256 && nkt >= 16ll * s && s < 16) s *= 2;      // double while short of 256 workgroups and slices keep >= 8 K tiles
@@ -362,7 +372,7 @@ extern "C" int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_des
     RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: K split %d (at most 64 and the %d K tiles)", ksplit, g.nkt);
   g.ksplit = ksplit > 1 ? ksplit : 1;
   long long tiles = 0;
-  const int shape = bf16_tile_shape(M, d->n, &tiles);
+  const int shape = radnet_bf16_tile_shape(M, d->n, &tiles);
   if (shape == 0) return launch_bf16<128, 128>(ctx, g);
   if (shape == 1) return launch_bf16<128, 64>(ctx, g);
   return launch_bf16<64, 64>(ctx, g);

@@ -377,15 +377,6 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_bwd_kernel(BwdArgs g) {
   }
 }
 
-// output tile of the launch: conv_bf16.hip's fixed rule on (rows, cols) -- 0: 128x128, 1: 128x64, 2: 64x64
-int tile_shape(long long rows, int cols, long long* tiles) {
-  const long long t128 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 128), t128x64 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 64);
-  if (cols > 64 && t128 >= 256) { *tiles = t128; return 0; }
-  if (t128x64 >= 256) { *tiles = t128x64; return 1; }
-  *tiles = (long long)radnet_cdiv(rows, 64) * radnet_cdiv(cols, 64);
-  return 2;
-}
-
 template <int BM, int BN, int MODE>
 int launch_bwd(radnet_ctx* ctx, BwdArgs g, double flops) {
   const char* what = MODE == MODE_DGRAD ? "conv_dgrad_bf16" : "conv_wgrad_bf16";
@@ -411,7 +402,7 @@ int launch_bwd(radnet_ctx* ctx, BwdArgs g, double flops) {
 template <int MODE>
 int launch_by_shape(radnet_ctx* ctx, const BwdArgs& g, double flops) {
   long long tiles = 0;
-  const int shape = tile_shape(g.rows, g.cols, &tiles);
+  const int shape = radnet_bf16_tile_shape(g.rows, g.cols, &tiles);      // conv_bf16.hip: the forward's fixed rule on (rows, cols)
   if (shape == 0) return launch_bwd<128, 128, MODE>(ctx, g, flops);
   if (shape == 1) return launch_bwd<128, 64, MODE>(ctx, g, flops);
   return launch_bwd<64, 64, MODE>(ctx, g, flops);

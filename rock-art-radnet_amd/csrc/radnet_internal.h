@@ -147,6 +147,8 @@ void radnet_timing_arm(radnet_ctx* ctx);
 void radnet_timing_end_armed(radnet_ctx* ctx, int cls, double flops);
 
 static inline int radnet_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// output tile of every bf16 matrix-core conv launch (conv_bf16.hip): 0: 128x128, 1: 128x64, 2: 64x64; *tiles = output tiles of that shape
+int radnet_bf16_tile_shape(long long rows, int cols, long long* tiles);
 // environment switch: set and neither empty nor "0"
 static inline bool radnet_env_flag(const char* name) {
   const char* v = getenv(name);

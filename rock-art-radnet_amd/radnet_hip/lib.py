@@ -185,6 +185,7 @@ def load_library():
         "radnet_conv_fwd_bf16": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32]),
         "radnet_conv_fwd_bf16_split": (C.c_int, [vp, C.POINTER(ConvDesc), vp, i32, i32]),
         "radnet_conv_bf16_pick_split": (i32, [C.c_int64, i32, i32]),
+        "radnet_conv_bf16_tile_shape": (i64, [i64, i32, C.POINTER(i32), C.POINTER(i32)]),
         "radnet_weights_to_bf16": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
         "radnet_weights_to_bf16_dgrad": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32]),
         "radnet_weights_to_bf16_dgrad_arena": (C.c_int, [vp, vp, i64, C.POINTER(Bf16DgradImage), i32]),

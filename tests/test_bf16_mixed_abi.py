@@ -11,7 +11,7 @@ import pytest
 
 from radnet_hip import lib as L
 
-NEW = ("radnet_adam_step_bf16", "radnet_conv_fwd_bf16_split", "radnet_conv_bf16_pick_split")
+NEW = ("radnet_adam_step_bf16", "radnet_conv_fwd_bf16_split", "radnet_conv_bf16_pick_split", "radnet_conv_bf16_tile_shape")
 
 
 def _lib():
@@ -34,6 +34,8 @@ def test_header_declares_and_library_exports_bf16_mixed_entry_points():
         assert hasattr(lib, n), "libradnet_hip.so does not export %s" % n
         assert getattr(lib, n).argtypes is not None, "%s has no ctypes binding" % n
     assert lib.radnet_adam_step_bf16.argtypes[-2] == C.POINTER(L.AdamBf16)
+    assert lib.radnet_conv_bf16_tile_shape.restype == C.c_int64
+    assert lib.radnet_conv_bf16_tile_shape.argtypes == [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
 
 
 def test_adam_bf16_struct_matches_header():

@@ -120,6 +120,9 @@ def test_split_rules():
         assert s == 1 or (M + 31) // 32 >= 8 * s                         # every slice keeps >= 8 pixel tiles
         assert s == fwd(K, N, min(M, 1 << 30))                           # the forward's rule on (rows = K, cols = N, reduction = M)
         tiles, elems = _tiles(K, N)
+        bm, bn = C.c_int32(), C.c_int32()
+        if M > 0:                                                        # the exported rule is the one the launchers use
+            assert lib.radnet_conv_bf16_tile_shape(K, N, C.byref(bm), C.byref(bn)) == tiles and bm.value * bn.value == elems
         assert s == 1 or tiles * (s // 2) < 256                          # the smallest that reaches 256 workgroups
         # the slabs of every training shape fit the 256 MB workspace of a lane (rpn_conv1's 18.9 MB gradient is not split at all)
         if (M, N, K) in WGRAD_600x1000:
