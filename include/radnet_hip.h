@@ -427,6 +427,54 @@ int radnet_resize_bicubic_u8(radnet_ctx* ctx, const uint8_t* src, int32_t sh, in
  * module's NumPy restatement; against OpenCV itself unpinned (absent here). */
 int radnet_warp_affine_u8(radnet_ctx* ctx, const uint8_t* src, int32_t sh, int32_t sw, int32_t channels, uint8_t* dst, int32_t dh,
                           int32_t dw, const int32_t* col_tab, const int32_t* row_tab);
+/* ---- train-time tile augmentation on the device (csrc/augment.hip) -------------------------------------------------------
+ * The image operations of faster_rcnn/augmentation.py for a tile that stays on the device from crop to network input
+ * (faster_rcnn/augmentation_device.py drives them; the +-3 degree rotation and the shear use radnet_warp_affine_u8, the final
+ * resize radnet_resize_bicubic_u8).  All images are uint8 HWC with 3 channels, contiguous, any extent >= 1 x 1.  Integer
+ * atomics only: results are reproducible run to run. */
+/* dst[y][x][c] = src[map(y, x)][c]: the window [y0, y0 + wh) x [x0, x0 + ww) of the sh x sw source under one of the eight
+ * dihedral transforms.  transform: bit 2 transposes the window first, then bit 0 reverses the rows and bit 1 the columns of
+ * the result; dst is wh x ww, or ww x wh when bit 2 is set.  0 with a window: the tile crop (utils.py:420) and the strap slice
+ * img[row_min:row_max, col_min:col_max] (augmentation.py:209, 262); 1 / 2 / 3: cv2.flip codes 0 / 1 / -1, i.e. vertical_flip
+ * (augmentation.py:101-115), horizontal_flip (augmentation.py:85-99) and the 180 degree case; 6 / 5: the 90 / 270 degree cases
+ * of ninety_degree_rotation (augmentation.py:117-156: transpose, then flip 1 / 0); 4 the bare transpose, 7 the anti-transpose. */
+int radnet_aug_gather_u8(radnet_ctx* ctx, const uint8_t* src, int32_t sh, int32_t sw, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
+                         int32_t transform, uint8_t* dst);
+/* strap_img (augmentation.py:17-31): out4 = {row_min, row_max, col_min, col_max} (device int32) of the pixels whose channel 1 is
+ * non-zero; {INT32_MAX, -1, INT32_MAX, -1} when there is none (the caller raises what the host function raises).  uint8 holds no
+ * non-finite value: that branch of the host function has no device form. */
+int radnet_aug_extent_u8(radnet_ctx* ctx, const uint8_t* img, int32_t h, int32_t w, int32_t* out4);
+/* bins256[v] (device uint32, overwritten) = number of elements equal to v over channel 0 (all_channels = 0) or over all three:
+ * per-workgroup bins in LDS, integer adds to global memory.  The host derives from it what brightness (augmentation.py:303-333:
+ * sum and count of the non-zero elements -> the foreground mean) and the poisson mode (augmentation.py:443-478 through
+ * skimage.util.random_noise: the number of distinct values) decide on; h * w * channels < 2^32. */
+int radnet_aug_histogram_u8(radnet_ctx* ctx, const uint8_t* img, int32_t h, int32_t w, int32_t all_channels, uint32_t* bins256);
+/* The pointwise modes, one launch each; src == dst is allowed.  Background -- exact zeros of the input, per element, or per pixel of
+ * channel 0 when `grey` -- stays zero, as brightness and the shared tail of the noise functions restore it; with `grey`
+ * ("grey" in C.img_types[0]; noise modes only) ONE plane computed from channel 0 is written to all three channels.
+ *   RADNET_AUG_BRIGHTNESS (augmentation.py:303-333): f = float(v); f -= d (p1 != 0) or f += d (p1 == 0) in fp32 with d = (float)p0,
+ *     the host's delta; clip to [0, 255]; truncate.
+ *   RADNET_AUG_CONTRAST (augmentation.py:335-351, skimage.exposure.rescale_intensity in fp64): f = clip(v, lo = p0, hi = p1);
+ *     f = (f - lo) / (hi - lo) unless lo == hi; truncate f * 255.0.  No background restore (0 maps to 0 for lo >= 0 anyway).
+ *   The noise modes (augmentation.py:353-478: skimage.util.random_noise + img_as_ubyte in fp64): x = v / 255.0, the mode, clip
+ *     to [0, 1], rint(x * 255) half-to-even.  scikit-image draws the field from a generator the reference never seeds -- only the
+ *     distribution is specified -- so the device has a reproducible field of its own, Philox4x32-10 (multipliers 0xD2511F53,
+ *     0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds): key = low and high half of `noise_seed`; counter =
+ *     (element_index_lo, element_index_hi, field_id, 0), element_index the row-major index in the field's own shape (H x W with
+ *     `grey`, H x W x 3 otherwise), field_id the sample's ordinal in the feed.  The output words x0..x3 give two uniforms, in fp64
+ *     as written: u_a = ((((x0 << 32) | x1) >> 11) + 0.5) * 2^-53 and u_b likewise from x2, x3.
+ *   RADNET_AUG_SALT_PEPPER: hit = u_a <= amount (p0), salt = u_b <= salt_vs_pepper (p1); a hit becomes 1 (salt) or 0.
+ *   RADNET_AUG_GAUSSIAN: z = sqrt(-2 ln u_a) * cos(2 pi u_b); x + (mean + sigma * z), p0 = mean, p1 = sigma = sqrt(var) rounded
+ *     once on the host.
+ *   RADNET_AUG_POISSON: lam = x * v (p0 = v = 2 ** ceil(log2(#distinct values)), 1 <= v <= 256); the CDF is walked in fp64: p = s =
+ *     exp(-lam), k = 0, while u_a > s and k < 1023: k += 1, p *= lam / k, s += p; the result is k / v. */
+#define RADNET_AUG_BRIGHTNESS 0
+#define RADNET_AUG_CONTRAST 1
+#define RADNET_AUG_SALT_PEPPER 2
+#define RADNET_AUG_GAUSSIAN 3
+#define RADNET_AUG_POISSON 4
+int radnet_aug_pointwise_u8(radnet_ctx* ctx, const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int32_t mode, int32_t grey, double p0,
+                            double p1, uint64_t noise_seed, uint32_t field_id);
 int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes);
 /* y = x * alpha (n floats); used to average gradients after all-reduce */
 int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha);

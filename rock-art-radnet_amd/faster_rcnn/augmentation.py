@@ -214,6 +214,43 @@ def ninety_degree_rotation(img, bboxes, verbose=False, rng=np.random):
     return img, bboxes
 
 
+def _rotation_plan(h, w, angle):
+    """augmentation.py:171-186: the matrix of a rotation by `angle` degrees about (w // 2, h // 2), shifted to the centre of the
+    canvas that holds the rotated image, and that canvas (new_w, new_h)."""
+    cx, cy = w // 2, h // 2
+    mat = rotation_matrix_2d((cx, cy), angle, 1.0)
+    c, s = abs(mat[0, 0]), abs(mat[0, 1])
+    new_w, new_h = int(h * s + w * c), int(h * c + w * s)
+    mat[0, 2] += new_w / 2 - cx
+    mat[1, 2] += new_h / 2 - cy
+    return mat, (new_w, new_h)
+
+
+def _rotated_hulls(arr, mat):
+    """augmentation.py:188-225: each box of `arr` (N x 4; anything else, i.e. no boxes, passes through) becomes the axis-aligned
+    hull of its four corners moved by `mat`."""
+    if arr.ndim != 2:
+        return arr
+    x1, y1, x2, y2 = (arr[:, i] for i in range(4))
+    px = np.stack((x1, x1 + (x2 - x1), x1, x2), 1)                    # corner order of the reference: tl, tr, bl, br
+    py = np.stack((y1, y1, y1 + (y2 - y1), y2), 1)
+    homog = np.stack((px.ravel(), py.ravel(), np.ones(px.size, dtype=px.dtype)), 1)
+    moved = np.dot(mat, homog.T).T.reshape(-1, 4, 2)                   # the reference's product, same operand shapes
+    rx, ry = moved[:, :, 0], moved[:, :, 1]
+    return np.stack((rx.min(1), ry.min(1), rx.max(1), ry.max(1)), 1)
+
+
+def _strapped_rotation_boxes(bboxes, arr, extent):
+    """augmentation.py:227-230: the hulls clipped to the strap extent (row_min, row_max, col_min, col_max), dropped when less than
+    half is left, written back in the strapped frame."""
+    row_min, row_max, col_min, col_max = extent
+    if arr.ndim == 2:
+        arr, mask = clip_box(arr, [col_min, row_min, col_max, row_max], 0.5)
+        bboxes = [b for b, m in zip(bboxes, mask) if m]
+        _write_back(bboxes, arr, col_min, row_min)
+    return bboxes
+
+
 def any_degree_rotation(img, bboxes, verbose=False, rng=np.random, warp=None):
     """augmentation.py:158-232: one draw, U(-3, 3) degrees about (w // 2, h // 2); the canvas grows to hold the rotated image,
     each box becomes the axis-aligned hull of its four rotated corners, the result is strapped to its non-black extent and
@@ -221,28 +258,26 @@ def any_degree_rotation(img, bboxes, verbose=False, rng=np.random, warp=None):
     arr = _boxes_array(bboxes)
     h, w = img.shape[:2]
     angle = rng.uniform(-3.0, 3.0)
-    cx, cy = w // 2, h // 2
-    mat = rotation_matrix_2d((cx, cy), angle, 1.0)
-    c, s = abs(mat[0, 0]), abs(mat[0, 1])
-    new_w, new_h = int(h * s + w * c), int(h * c + w * s)
-    mat[0, 2] += new_w / 2 - cx
-    mat[1, 2] += new_h / 2 - cy
-    img = (warp or warp_affine_u8)(img, mat, (new_w, new_h))
-    if arr.ndim == 2:
-        x1, y1, x2, y2 = (arr[:, i] for i in range(4))
-        px = np.stack((x1, x1 + (x2 - x1), x1, x2), 1)                    # corner order of the reference: tl, tr, bl, br
-        py = np.stack((y1, y1, y1 + (y2 - y1), y2), 1)
-        homog = np.stack((px.ravel(), py.ravel(), np.ones(px.size, dtype=px.dtype)), 1)
-        moved = np.dot(mat, homog.T).T.reshape(-1, 4, 2)                   # the reference's product, same operand shapes
-        rx, ry = moved[:, :, 0], moved[:, :, 1]
-        arr = np.stack((rx.min(1), ry.min(1), rx.max(1), ry.max(1)), 1)
+    mat, dsize = _rotation_plan(h, w, angle)
+    img = (warp or warp_affine_u8)(img, mat, dsize)
+    arr = _rotated_hulls(arr, mat)
     row_min, row_max, col_min, col_max = strap_img(img)
     img = img[row_min:row_max, col_min:col_max, :]
-    if arr.ndim == 2:
-        arr, mask = clip_box(arr, [col_min, row_min, col_max, row_max], 0.5)
-        bboxes = [b for b, m in zip(bboxes, mask) if m]
-        _write_back(bboxes, arr, col_min, row_min)
+    bboxes = _strapped_rotation_boxes(bboxes, arr, (row_min, row_max, col_min, col_max))
     return img, bboxes
+
+
+def _shear_plan(h, w, f):
+    """augmentation.py:246-252: the matrix x' = x + |f| y and the canvas widened by |f| h."""
+    return np.array([[1, abs(f), 0], [0, 1, 0]], dtype=np.float64), (int(w + abs(f * h)), h)
+
+
+def _sheared_boxes(bboxes, f):
+    """augmentation.py:243-245: box x coordinates move by int(|f| y) of their own corner."""
+    arr = _boxes_array(bboxes)
+    if arr.ndim == 2:
+        arr[:, [0, 2]] += (arr[:, [1, 3]] * abs(f)).astype(int)
+    return arr
 
 
 def shear(img, bboxes, verbose=False, rng=np.random, warp=None):
@@ -252,10 +287,9 @@ def shear(img, bboxes, verbose=False, rng=np.random, warp=None):
     if f < 0.0:
         img, bboxes = horizontal_flip(img, bboxes)
     h, w = img.shape[:2]
-    arr = _boxes_array(bboxes)
-    if arr.ndim == 2:
-        arr[:, [0, 2]] += (arr[:, [1, 3]] * abs(f)).astype(int)
-    img = (warp or warp_affine_u8)(img, np.array([[1, abs(f), 0], [0, 1, 0]], dtype=np.float64), (int(w + abs(f * h)), h))
+    arr = _sheared_boxes(bboxes, f)
+    mat, dsize = _shear_plan(h, w, f)
+    img = (warp or warp_affine_u8)(img, mat, dsize)
     row_min, row_max, col_min, col_max = strap_img(img)
     img = img[row_min:row_max, col_min:col_max, :]
     if arr.ndim == 2:

@@ -123,13 +123,26 @@ def tile_grid(width, height, tile_size, step):
 
 class TileFeed:
     """Iterator over training samples (see module docstring).  data: list of {filepath, width, height, bboxes:[{class,x1,
-    y1,x2,y2}]}; class_count: {class: number of boxes} (utils.get_data's third return value)."""
+    y1,x2,y2}]}; class_count: {class: number of boxes} (utils.get_data's third return value).
+    device_augment=True (opt-in; default: the host path, unchanged): the decoded image is uploaded once per load, the tile crop,
+    the whole augmentation chain and the resize run on the device (faster_rcnn/augmentation_device.py, which states what equals
+    the host path and what does not: the noise fields, keyed by `noise_seed` and the sample's ordinal) and the sample's `img` is
+    a uint8 HWC cuda tensor, which TrainStep takes as it is.  A validation feed (train_mode=False) takes the device crop and
+    resize and no augmentation."""
 
-    def __init__(self, data, C, class_count, load_image, train_mode=True, rng=None, resize=None, noise_rng=None):
+    def __init__(self, data, C, class_count, load_image, train_mode=True, rng=None, resize=None, noise_rng=None, device_augment=False,
+                 noise_seed=None):
         self.data, self.C, self.load_image, self.train_mode = data, C, load_image, train_mode
+        self.device_augment, self.noise_seed = bool(device_augment), noise_seed
+        self._ordinal = 0                         # samples yielded so far: the field_id of the device path's noise fields
+        if self.device_augment:
+            if resize is not None:
+                raise ValueError("TileFeed: device_augment=True keeps the tile on the device; it takes no host resize= hook")
+            if getattr(C, "use_noise", False) and noise_seed is None:
+                raise ValueError("TileFeed: device_augment=True with C.use_noise needs a noise_seed (the key of the device's noise fields)")
         self.noise_rng = noise_rng                # numpy Generator of the noise augmentations' fields; None = unseeded, as scikit-image's
         self.warp = None                          # rotation / shear warp: the device kernel beside the device resize, else NumPy
-        if resize is None and train_mode and (getattr(C, "use_rotations", False) or getattr(C, "use_shear", False)):
+        if resize is None and train_mode and not self.device_augment and (getattr(C, "use_rotations", False) or getattr(C, "use_shear", False)):
             from .RADNet import warp_affine_device
             self.warp = warp_affine_device
         self.rng = np.random if rng is None else rng
@@ -160,6 +173,33 @@ class TileFeed:
         return dict(img=np.ascontiguousarray(img), bboxes=img_data["bboxes"], width=width, height=height,
                     filepath=img_data.get("filepath"))
 
+    def _upload(self, img):
+        """device_augment: the decoded image goes up once, when a tile of it is taken; everything after it reads the device copy."""
+        import torch
+        from . import augmentation_device as AD
+        with AD.feed_stream() as (_, _side):
+            return torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).cuda()
+
+    def _sample_device(self, img_dev, img_data, window=None):
+        """device_augment: [tile crop ->] [augmentation ->] resize, all on the device; the sample's img is a cuda tensor.  The
+        producing stream has drained before the sample leaves: any lane of the consumer may read it."""
+        import torch
+        from . import augmentation_device as AD
+        C = self.C
+        with AD.feed_stream() as (ctx, side):
+            if window is not None:
+                img_dev = AD.gather(ctx, img_dev, AD.IDENTITY, window)
+            if self.train_mode:
+                img_data, img_dev = AD.augment_device(img_data, img_dev, C, self.rng, self.noise_seed or 0, self._ordinal, ctx=ctx)
+            width, height = img_data["width"], img_data["height"]
+            if img_dev.shape[1] != width or img_dev.shape[0] != height:
+                raise AssertionError("image size does not match its annotation")           # utils.py:437-438
+            new_w, new_h = get_new_img_size(width, height, C.img_size)
+            img_dev = AD.resize(ctx, img_dev, new_w, new_h)
+            torch.cuda.current_stream().synchronize()
+        self._ordinal += 1
+        return dict(img=AD.hand_over(img_dev, side), bboxes=img_data["bboxes"], width=width, height=height, filepath=img_data.get("filepath"))
+
     def __iter__(self):
         C, sel = self.C, self.selector
         balanced = self.train_mode and C.balanced_classes
@@ -187,10 +227,15 @@ class TileFeed:
                     for i, b in enumerate(kept):
                         b["x1"], b["y1"] = int(arr[i, 0] - tile[0]), int(arr[i, 1] - tile[1])
                         b["x2"], b["y2"] = int(math.ceil(arr[i, 2] - tile[0])), int(math.ceil(arr[i, 3] - tile[1]))
-                    crop = np.copy(img[tile[1]:tile[3], tile[0]:tile[2], :])
+                    crop = img[tile[1]:tile[3], tile[0]:tile[2], :]
                     tile_data = dict(img_data, bboxes=kept, width=crop.shape[1], height=crop.shape[0])
                     if balanced and sel.skip_tile_for_balanced_class(tile_data):
                         continue
+                    if self.device_augment:
+                        done += 1
+                        yield self._sample_device(self._upload(img), tile_data, (tile[1], tile[0], crop.shape[0], crop.shape[1]))
+                        continue
+                    crop = np.copy(crop)
                     if self.train_mode:
                         tile_data, crop = augment_geometric(tile_data, crop, C, self.rng, self.noise_rng, self.warp)
                     done += 1
@@ -200,6 +245,9 @@ class TileFeed:
                         continue
                     img = self._image(img_data, C.use_img_type)
                     full = copy.deepcopy(img_data)
+                    if self.device_augment:
+                        yield self._sample_device(self._upload(img), full)
+                        continue
                     if self.train_mode:
                         full, img = augment_geometric(full, img, C, self.rng, self.noise_rng, self.warp)
                     yield self._sample(img, full)

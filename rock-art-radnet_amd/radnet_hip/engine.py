@@ -799,8 +799,18 @@ class FasterRCNNEngine:
             raise L.RadnetError("engine._copy: %d != %d bytes, or a strided side" % (n, src.numel() * src.element_size()))
         self.ctx.call("radnet_copy_bytes", dst, src, C.c_uint64(n))
 
+    def _copy_device_image(self, dst, img):
+        """dst (a plan's raw panel) <- img, a uint8 HWC cuda tensor (a sample of TileFeed(device_augment=True)): a device-to-device
+        copy on the current lane, where the preprocess kernel runs, in place of the pinned staging.  The tensor may have been made
+        on another stream (the feed worker's): the allocator is told that this lane reads it."""
+        if img.dtype != torch.uint8 or img.device != dst.device or tuple(img.shape) != tuple(dst.shape) or not img.is_contiguous():
+            raise L.RadnetError("upload_image: a device image must be a contiguous uint8 %s tensor on %s" % (tuple(dst.shape), dst.device))
+        img.record_stream(torch.cuda.current_stream())
+        self.ctx.call("radnet_copy_bytes", dst, img, C.c_uint64(img.numel()))
+
     def upload_image(self, img_bgr_u8, slot=0):
-        """uint8 BGR HWC host image -> preprocessed fp32 NHWC(4) on device (RADNet.py:83-87)."""
+        """uint8 BGR HWC image -> preprocessed fp32 NHWC(4) on device (RADNet.py:83-87).  A host array goes through the pinned
+        staging buffer; a cuda uint8 tensor is copied device to device."""
         H, W = img_bgr_u8.shape[:2]
         plan = self._plan_base(1, H, W, slot)
         # through a pinned staging buffer: a pageable H2D copy blocks the host thread for ~1 ms per 1.8 MB panel,
@@ -811,6 +821,11 @@ class FasterRCNNEngine:
             plan["raw_free"] = torch.cuda.Event()       # staging buffer drained
             plan["raw_read"] = torch.cuda.Event()       # device panel consumed by the preprocess kernel
             plan["raw_read"].record()
+        if isinstance(img_bgr_u8, torch.Tensor) and img_bgr_u8.is_cuda:
+            self._copy_device_image(plan["raw"], img_bgr_u8)
+            self.ctx.call("radnet_preprocess_bgr", plan["raw"], H, W, 4, plan["x"])
+            plan["raw_read"].record()
+            return plan
         if isinstance(img_bgr_u8, torch.Tensor) and img_bgr_u8.is_pinned():
             src = img_bgr_u8
         else:
@@ -837,7 +852,7 @@ class FasterRCNNEngine:
         """Per-GPU mini-batch as ONE layer program (BASELINE cfg 4: per-GPU batch 2): the nb images (same size) land in one
         [nb][H][W][4] input tensor, so every base / RPN GEMM runs once with M = nb * H' * W' rows instead of nb times with
         H' * W' -- at batch 1 the launches are too small to fill 256 CUs, doubling M halves the fixed cost
-        per image.  Same pinned-staging path per image as upload_image."""
+        per image.  Same pinned-staging path per image as upload_image; cuda uint8 tensors are copied device to device."""
         nb = len(imgs)
         H, W = imgs[0].shape[:2]
         plan = self._plan_base(nb, H, W, slot)
@@ -850,6 +865,9 @@ class FasterRCNNEngine:
         for i, img in enumerate(imgs):
             if img.shape[:2] != (H, W):
                 raise L.RadnetError("upload_images: images of one mini-batch must share their size")
+            if isinstance(img, torch.Tensor) and img.is_cuda:
+                self._copy_device_image(plan["raws"][i], img)
+                continue
             np.copyto(plan["h_raws"][i].numpy(), img)
             self._copy(plan["raws"][i], plan["h_raws"][i])
         plan["raw_free"].record()

@@ -82,6 +82,7 @@ class DetectTailDesc(C.Structure):
                 ("max_boxes", C.c_int32), ("out", C.c_void_p)]
 
 
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SALT_PEPPER, AUG_GAUSSIAN, AUG_POISSON = range(5)      # RADNET_AUG_* modes of radnet_aug_pointwise_u8
 DETECT_HEADER, DETECT_RECORD = 8, 6      # int32 words in front of / per record of radnet_detect_tail's output
 
 
@@ -245,6 +246,10 @@ def load_library():
         "radnet_preprocess_bgr": (C.c_int, [vp, vp, i32, i32, i32, vp]),
         "radnet_resize_bicubic_u8": (C.c_int, [vp, vp, i32, i32, vp, i32, i32, i32]),
         "radnet_warp_affine_u8": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
+        "radnet_aug_gather_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "radnet_aug_extent_u8": (C.c_int, [vp, vp, i32, i32, vp]),
+        "radnet_aug_histogram_u8": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+        "radnet_aug_pointwise_u8": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f64, f64, u64, C.c_uint32]),
         "radnet_fill_zero": (C.c_int, [vp, vp, u64]),
         "radnet_copy_bytes": (C.c_int, [vp, vp, vp, C.c_uint64]),
         "radnet_program_run": (C.c_int, [vp, C.POINTER(Op), i32]),

@@ -204,7 +204,10 @@ class NativeTrainStep:
         return ent
 
     def step(self, sample):
-        """One image; returns self (losses())."""
+        """One image; returns self (losses()).  The image is a host array: a device-resident sample (TileFeed(device_augment=True))
+        raises TypeError -- the pipelined trainer.TrainStep is the form that takes those."""
+        if isinstance(sample["img"], torch.Tensor) and sample["img"].is_cuda:
+            raise TypeError("NativeTrainStep.step takes host images (uint8 HWC ndarray); device-resident samples go to trainer.TrainStep")
         eng = self.eng
         d, buf, head, bp, rp, hp = self._desc(sample)
         Cc = eng.C

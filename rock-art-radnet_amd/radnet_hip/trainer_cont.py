@@ -43,7 +43,11 @@ class ContTrainStep:
         return s["_gt_dev"]
 
     def _launch_stem(self, batch, slot):
-        """What does not depend on any trainable weight: labelling kernels, upload, conv1 .. stage 2 (frozen)."""
+        """What does not depend on any trainable weight: labelling kernels, upload, conv1 .. stage 2 (frozen).  Images are host
+        arrays: a device-resident sample (TileFeed(device_augment=True)) raises TypeError here -- trainer.TrainStep takes those."""
+        for s in batch:
+            if isinstance(s["img"], torch.Tensor) and s["img"].is_cuda:
+                raise TypeError("ContTrainStep takes host images (uint8 HWC ndarray); device-resident samples go to trainer.TrainStep")
         eng = self.eng
         nloc = len(batch)
         tp, plans = [], []
