@@ -1,6 +1,6 @@
 // Inference convolution as implicit GEMM on the gfx950 bf16 matrix cores (v_mfma_f32_32x32x16_bf16), fp32 accumulation.
 //
-// The predict-only twin of conv_mfma.hip's forward kernel (keras Conv2D + FixedBatchNormalization + Add + Activation,
+// The predict-only twin of the fp32 forward kernel (conv_igemm_body.h, conv_mfma.hip) (keras Conv2D + FixedBatchNormalization + Add + Activation,
 // base_models/resnet50.py:41-147,183-186; rpn.py:41-64) for frozen weights: bf16 MFMA runs at 16x the fp32 MFMA rate on
 // gfx950 (no TF32 there), and at inference nothing accumulates the rounding over steps.
 //
@@ -15,9 +15,9 @@
 //   * 4 wavefronts in a 2x2 arrangement; each wave owns (BM/2)x(BN/2) of the output as 32x32 accumulator tiles.  Both
 //     operands are row-major [row][32 k + 8 pad] bf16 in LDS (80-byte rows), read as one ds_read_b128 per fragment.  Two
 //     LDS buffers, the global loads of tile t+1 in registers while tile t is multiplied: one barrier per K tile.
-//   * Fused epilogue as in conv_mfma.hip: per-column scale / shift, residual addend, ReLU or sigmoid on [0, act_cols).
+//   * Fused epilogue as in conv_igemm_body.h: per-column scale / shift, residual addend, ReLU or sigmoid on [0, act_cols).
 //   * Ordered K split (bf16-mixed training: small M, deep K -- radnet_conv_bf16_pick_split): blockIdx.z = slice of the K
-//     tiles.  conv_mfma.hip's in-launch protocol: every slice writes its partial tile as a write-through (sc1) slab, drains
+//     tiles.  conv_igemm_body.h's in-launch protocol: every slice writes its partial tile as a write-through (sc1) slab, drains
 //     it, takes a ticket from the tile's arrival counter; the last arrival sums ALL slabs in slice order (its own read back
 //     too, with sc1 loads), so the result does not depend on arrival order, then runs the epilogue and leaves the counter
 //     at zero.  Slabs live in the context's workspace, counters in its aux block: each lane has its own.  No float atomics:

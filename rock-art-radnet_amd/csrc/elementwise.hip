@@ -295,7 +295,7 @@ __global__ void __launch_bounds__(256) dense_heads_bwd_kernel(const float* __res
 // ---- column sums (bias gradients) ----------------------------------------------------------------------
 // `partials` != null (radnet_ctx::deterministic): the row blocks of a column block hand their partial sums to the last one
 // to arrive, which adds them in a fixed shape (sc1 stores / relaxed agent-scope ticket / sc1 loads, as the split-K
-// reduction of conv_mfma.hip) -- the same bits on every run.  partials == null: one fp32 atomic per block and column.
+// reduction of conv_igemm_body.h) -- the same bits on every run.  partials == null: one fp32 atomic per block and column.
 __global__ void __launch_bounds__(256) colsum_kernel(const float* __restrict__ g, int m, int n, int ld, const float* __restrict__ gscale,
                                                      float* __restrict__ out, int rows_per_block, float* __restrict__ partials,
                                                      unsigned* __restrict__ counters) {

@@ -48,7 +48,7 @@ constexpr int kPosGroups = 4;    // position groups per workgroup (threads 64 x 
 // the pooled 256 channels of the slice into the dense heads; the LAST slice of a RoI to finish adds the slices' partial
 // sums in slice order (deterministic), applies softmax and, with targets, the detector losses of that RoI; the LAST RoI sums
 // the loss terms in RoI order.  Hand-offs: agent-scope (sc1, write-through) stores drained before a relaxed ticket,
-// agent-scope loads by the reader (cdna_hip_programming.md 6 Guideline 16, write-through form; as conv_mfma.hip's split-K).
+// agent-scope loads by the reader (cdna_hip_programming.md 6 Guideline 16, write-through form; as conv_igemm_body.h's split-K).
 template <int NP>
 __global__ void __launch_bounds__(256) head_tail_fwd_kernel(TailArgs g) {
   __shared__ float4 pool[kPosGroups][64];

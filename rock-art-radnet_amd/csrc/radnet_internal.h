@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "radnet_hip.h"
+#include "radnet_host.h"
 
 struct radnet_timing_slot {
   double ms = 0.0;
@@ -63,7 +64,7 @@ struct radnet_ctx {
   // measured launch choices; contexts of one engine share ONE table (radnet_share_tuning), calls come from one host thread
   std::shared_ptr<std::map<radnet_shape_key, radnet_tuned>> tuned = std::make_shared<std::map<radnet_shape_key, radnet_tuned>>();
   std::map<std::array<int, 6>, radnet_unit_table> unit_tables;
-  // conv geometry -> device row table (conv_mfma.hip: get_row_table): read-only once built, so the contexts of one engine share
+  // conv geometry -> device row table (conv_wgrad.hip: get_row_table): read-only once built, so the contexts of one engine share
   // them like the tuning table (radnet_share_tuning) -- a context that first meets a geometry inside a graph capture must not
   // have to build (allocate + copy) its table there.  Freed by the last context that holds the map.
   struct RowTables {
@@ -82,7 +83,7 @@ struct radnet_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   radnet_timing_slot slots[5];      // 0 fwd, 1 dgrad, 2 wgrad, 3 Winograd layers of a program, 4 dgrad + wgrad of a layer in one launch
   hipEvent_t arm0 = nullptr, arm1 = nullptr;      // event pair of the launch being timed (radnet_timing_arm), or null
-  void* pair_capture = nullptr;     // conv_mfma.hip: radnet_conv_bwd collects the two launches of a layer here instead of issuing them
+  void* pair_capture = nullptr;     // conv_host.h (PairCapture): radnet_conv_bwd collects the two launches of a layer here instead of issuing them
   // pending (not yet resolved) event pairs are resolved lazily to avoid a sync per launch
   static constexpr int kMaxPending = 4096;
   hipEvent_t pend0[kMaxPending];
@@ -119,12 +120,6 @@ constexpr size_t kAuxBf16SplitCounters = kAuxColsumScratch + kAuxColsumRows * kA
 constexpr size_t kAuxBf16SplitCounterCount = 8192;                                                  // K-split bf16 forward launch
 constexpr size_t kAuxBytes = kAuxBf16SplitCounters + kAuxBf16SplitCounterCount * 4;
 
-#define RADNET_FAIL(ctx, code, ...)                         \
-  do {                                                      \
-    snprintf((ctx)->err, sizeof((ctx)->err), __VA_ARGS__);  \
-    return (code);                                          \
-  } while (0)
-
 #define RADNET_CHECK_HIP(ctx, expr)                                                              \
   do {                                                                                           \
     hipError_t _e = (expr);                                                                      \
@@ -146,7 +141,6 @@ void radnet_timing_end(radnet_ctx* ctx, int cls, double flops);
 void radnet_timing_arm(radnet_ctx* ctx);
 void radnet_timing_end_armed(radnet_ctx* ctx, int cls, double flops);
 
-static inline int radnet_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // output tile of every bf16 matrix-core conv launch (conv_bf16.hip): 0: 128x128, 1: 128x64, 2: 64x64; *tiles = output tiles of that shape
 int radnet_bf16_tile_shape(long long rows, int cols, long long* tiles);
 // environment switch: set and neither empty nor "0"
@@ -177,5 +171,13 @@ static inline int radnet_time_launches(radnet_ctx* ctx, F&& launch, int iters, f
   return RADNET_OK;
 }
 
-// exact floor(m / d) for m, d < 2^20 as (m * magic) >> 40  (m*d < 2^40, see conv_mfma.hip)
-static inline uint64_t radnet_div_magic(uint32_t d) { return ((1ull << 40) + d - 1) / d; }
+// A finalist of the autotuners: `iters` launches measured twice, the smaller figure (the 3-launch screening is noisy, see run_igemm)
+template <typename F>
+static inline int radnet_time_launches_twice(radnet_ctx* ctx, F&& launch, int iters, float* ms_out) {
+  float m1 = 0.f, m2 = 0.f;
+  int rc = radnet_time_launches(ctx, launch, iters, &m1);
+  if (rc == RADNET_OK) rc = radnet_time_launches(ctx, launch, iters, &m2);
+  if (rc != RADNET_OK) return rc;
+  *ms_out = std::min(m1, m2);
+  return RADNET_OK;
+}

@@ -1,5 +1,5 @@
 // F(4x4, 3x3) Winograd building blocks shared by winograd.hip (one launch per transform) and the chain kernel of
-// conv_mfma.hip (transforms as work items of a persistent launch).  See winograd.hip for the matrices and the layouts.
+// chain.hip (transforms as work items of a persistent launch).  See winograd.hip for the matrices and the layouts.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(256) wino_filter_grad_kernel(const float* __re
 // largest activation at C = 1024 (F(2x2): 1e-6, direct fp32: 5e-7) -- inside the 2e-4 the kernel tests state.
 // Layouts as above with 36 positions p = 6*xi + nu and tiles of 4x4 outputs (input rows 4ti-1 .. 4ti+4).
 // Kernels are templates over the per-thread channel vector (instantiated for float4, see RADNET_WINO4_LAUNCH).
-// (vector helpers and the 1-D transforms bt6 / at6 / a6 / g6 / gt6: radnet_wino4.h, shared with the chain kernel of conv_mfma.hip)
+// (vector helpers and the 1-D transforms bt6 / at6 / a6 / g6 / gt6: radnet_wino4.h, shared with the chain kernel, chain.hip)
 template <typename VT>
 __global__ void __launch_bounds__(256) wino4_filter_kernel(const float* __restrict__ g, int C, int N, int ldw, float* __restrict__ U) {
   constexpr int W = sizeof(VT) / 4;

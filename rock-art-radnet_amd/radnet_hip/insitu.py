@@ -1,6 +1,6 @@
 """Launch shapes tuned IN SITU: against the throughput of the running step instead of each launch alone.
 
-The engine's autotuner (csrc/conv_mfma.hip: run_igemm / run_wgrad) times every problem shape by itself on an idle chip.  In the
+The engine's autotuner (csrc/conv_mfma.hip: run_igemm, csrc/conv_wgrad.hip: run_wgrad) times every problem shape by itself on an idle chip.  In the
 pipelined train step (trainer.TrainStep, four lanes) a launch shares the CUs with the other lanes' launches, and the shape that is
 fastest alone is not always the one that packs best (+6 % at 1000x600).  `tune()` starts from the table of the shapes
 the workload launches and walks it entry by entry: the neighbouring shapes the autotuner itself would consider (other tile, other
@@ -47,7 +47,7 @@ WIDE = False      # --wide: every K-slice count (both unit orders) instead of th
 
 
 def neighbours(key, cur):
-    """Launch shapes next to `cur` inside the autotuner's own candidate space (conv_mfma.hip: run_igemm / run_wgrad)."""
+    """Launch shapes next to `cur` inside the autotuner's own candidate space (conv_mfma.hip: run_igemm, conv_wgrad.hip: run_wgrad)."""
     kind, m, n, k, c, npos, stride = key
     a, b, s, _, w = cur
     out = []

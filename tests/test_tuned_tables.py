@@ -14,7 +14,7 @@ def _tool():
 
 
 def _valid(key, a, b, s, w):
-    """What csrc/conv_mfma.hip (run_igemm / run_wgrad) and radnet_tune_load accept for a measured shape."""
+    """What csrc/conv_mfma.hip (run_igemm), csrc/conv_wgrad.hip (run_wgrad) and radnet_tune_load accept for a measured shape."""
     kind, m, n, k, c, npos, stride = key
     if kind == 32:                                                   # forward pair (branch2a + shortcut): one launch on that tile, or two
         assert (a, b) in ((64, 64), (32, 64), (32, 32)) and s in (1, 2) and w == 4, (key, a, b, s, w)
