@@ -475,6 +475,35 @@ int radnet_aug_histogram_u8(radnet_ctx* ctx, const uint8_t* img, int32_t h, int3
 #define RADNET_AUG_POISSON 4
 int radnet_aug_pointwise_u8(radnet_ctx* ctx, const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int32_t mode, int32_t grey, double p0,
                             double p1, uint64_t noise_seed, uint32_t field_id);
+/* ---- PNG images onto the device (csrc/png.hip) ------------------------------------------------------------------------------
+ * faster_rcnn/png.py reads the container and inflates the IDAT stream on the host; the per-byte work runs here, on the inflated
+ * stream after ONE upload: per pass (one for a non-interlaced file, up to seven for Adam7) a reconstruction launch and an
+ * expansion launch.  A pass is pass_h scanlines of 1 + rowbytes bytes: the filter-type byte, then the packed samples.  The result
+ * is what cv2.imdecode(buf, cv2.IMREAD_COLOR) returns, uint8 [dst_h][dst_w][3] in B, G, R order; both steps restate the PNG
+ * specification and libpng's documented transforms as OpenCV requests them -- against OpenCV itself unpinned (absent here). */
+/* Scanline reconstruction (PNG specification, section 9) IN PLACE on one pass: rows x (1 + rowbytes) bytes at `stream`; the filter-type
+ * bytes stay, every other byte x becomes Recon(x) = x + predictor modulo 256 with a = the reconstructed byte bpp to the left, b = the
+ * one above, c = the one above a (0 left of the row and above row 0): type 0 None 0; 1 Sub a; 2 Up b; 3 Average floor((a + b) / 2)
+ * on the 9-bit sum; 4 Paeth p = a + b - c, the first of a, b, c (in that order, compared with <=) nearest to p.
+ * bpp = max(1, channels * bit_depth / 8), one of 1, 2, 3, 4, 6, 8, and divides rowbytes.  A filter-type byte above 4 is the CALLER's
+ * to refuse (png.py checks the column on the host); the kernel treats it as None.  One workgroup walks the pass in bands of
+ * RADNET_PNG_UNFILTER_BAND_ROWS rows, one lane per row, each row one pixel behind the row above, and moves row data between global
+ * memory and LDS in chunks of RADNET_PNG_UNFILTER_CHUNK_BYTES per row: the seams tests/test_gpu_png.py straddles.  Nothing waits
+ * on another workgroup; the loop bounds depend on (rows, rowbytes, bpp) alone. */
+#define RADNET_PNG_UNFILTER_BAND_ROWS 512
+#define RADNET_PNG_UNFILTER_CHUNK_BYTES 96
+int radnet_png_unfilter_u8(radnet_ctx* ctx, uint8_t* stream, int32_t rows, int32_t rowbytes, int32_t bpp);
+/* Expansion of one reconstructed pass: pixel (r, c) of the pass_h x pass_w pass goes to dst[y0 + r * dy][x0 + c * dx] (a
+ * non-interlaced image: y0 = x0 = 0, dy = dx = 1; Adam7: the pass's origin and spacing).  colour types 0 (grey; depth 1, 2, 4, 8, 16),
+ * 2 (RGB; 8, 16), 3 (palette; 1, 2, 4, 8), 4 (grey + alpha; 8, 16), 6 (RGBA; 8, 16).  Sub-byte samples unpack MSB first; grey is
+ * replicated to the three channels, depths 1 / 2 / 4 scaled by 255 / 85 / 17; a 16-bit sample keeps its high byte (libpng's
+ * strip_16); alpha is dropped, not blended; a palette index selects palette_bgr[index] (device, 256 x 3 bytes in B, G, R order,
+ * entries beyond the file's PLTE zero; ignored for the other colour types and may then be null).  No gamma, sBIT, tRNS or
+ * background handling.  The pass must lie inside dst and rowbytes must hold pass_w pixels: refused otherwise, never read or
+ * written out of bounds. */
+int radnet_png_expand_bgr_u8(radnet_ctx* ctx, const uint8_t* stream, int32_t pass_h, int32_t pass_w, int32_t rowbytes, int32_t color_type,
+                             int32_t bit_depth, const uint8_t* palette_bgr, uint8_t* dst, int32_t dst_h, int32_t dst_w, int32_t y0,
+                             int32_t x0, int32_t dy, int32_t dx);
 int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes);
 /* y = x * alpha (n floats); used to average gradients after all-reduce */
 int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha);

@@ -349,15 +349,15 @@ class RADNet():
         return dets
 
     def predict_from_path(self, img_path):
-        """RADNet.py:482-500 (needs an image decoder; OpenCV is the reference's and is absent here)."""
-        try:
-            import cv2  # noqa: F401
-        except ImportError as e:
-            raise NotImplementedError("predict_from_path needs OpenCV to decode images; pass decoded BGR arrays to predict()") from e
-        from .utils_io import get_image
+        """RADNet.py:482-500: one image per type of C.img_types when C.use_img_type, else the first type's, each read by
+        utils_io.get_image (faster_rcnn/png.py decodes; no OpenCV), then predict on the host arrays."""
+        from . import utils_io
         C = self.C
-        types = C.img_types if C.use_img_type else [C.img_types[0]]
-        return self.predict([get_image(img_path, [t], random_type=False) for t in types])
+        if C.use_img_type:
+            images = [utils_io.get_image(img_path, [img_type], random_type=False) for img_type in C.img_types]
+        else:
+            images = [utils_io.get_image(img_path, C.img_types, random_type=False)]
+        return self.predict(images)
 
 
 def resize_cubic(img, new_w, new_h, to_host=True, ctx=None):

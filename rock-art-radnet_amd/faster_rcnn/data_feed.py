@@ -12,8 +12,10 @@ Same control flow and the same draws from the random stream as the reference, in
 Augmentation (augmentation.py:85-533) is `faster_rcnn/augmentation.py` of this package: every switch of
 the reference's Config (flips, 90-degree and +-3-degree rotation, shear, brightness, the noise / contrast family) with the
 reference's draws in its order; which parts are pinned by the reference's own outputs and which restate OpenCV /
-scikit-image semantics unpinned is listed in that module's header.  Images are decoded by the caller
-(`load_image(img_data, img_type) -> uint8 BGR HWC`): OpenCV, which the reference decodes with, is not part of this build.
+scikit-image semantics unpinned is listed in that module's header.  Images come from the caller's decoder
+(`load_image(img_data, img_type) -> uint8 BGR HWC`); faster_rcnn/utils_io.py has the package's own for PNG files, `load_image`
+(NumPy arrays) and `DeviceImageLoader` (cuda tensors, for device_augment=True) -- OpenCV, which the reference decodes with, is not
+part of this build.
 
 rng: None = NumPy's global stream, i.e. exactly the reference's interleaving with the step's own draws when samples are
 pulled one per step; pass a RandomState to pull samples AHEAD of the step (TrainStep's `upcoming` lookahead) without
@@ -174,9 +176,12 @@ class TileFeed:
                     filepath=img_data.get("filepath"))
 
     def _upload(self, img):
-        """device_augment: the decoded image goes up once, when a tile of it is taken; everything after it reads the device copy."""
+        """device_augment: the decoded image goes up once, when a tile of it is taken; everything after it reads the device copy.
+        An image the loader already decoded onto the device (utils_io.DeviceImageLoader: a uint8 cuda tensor) passes through."""
         import torch
         from . import augmentation_device as AD
+        if isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.uint8:
+            return img.contiguous()
         with AD.feed_stream() as (_, _side):
             return torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).cuda()
 

@@ -1,0 +1,176 @@
+"""PNG reader for the subset the job needs: the reference decodes every input map with cv2.imdecode(buf, cv2.IMREAD_COLOR)
+(utils.py:127-130), and this module produces the same thing -- uint8 [H][W][3] in B, G, R order -- without OpenCV, as
+faster_rcnn/keras_h5.py reads Keras weight files without h5py.
+
+Host (this file, no device needed): signature, chunk walk (IHDR, PLTE, the concatenated IDAT data, IEND; ancillary chunks are
+skipped, tRNS among them), CRC-32 of every chunk (zlib.crc32), inflate (zlib.decompressobj of the standard library), the pass
+geometry (one pass, or Adam7's up to seven) and the check that every filter-type byte is at most 4.
+Device (csrc/png.hip through the C ABI, include/radnet_hip.h): scanline reconstruction in place on the uploaded stream
+(radnet_png_unfilter_u8) and expansion to BGR (radnet_png_expand_bgr_u8), one launch of each per pass.  The file becomes a device
+image after one upload; nothing comes back unless the caller asks for a NumPy array.  There is no CPU reconstruction.
+
+Formats: colour types 0, 2, 3, 4, 6 with the bit depths 1, 2, 4, 8, 16 the PNG specification allows for each; non-interlaced and
+Adam7.  Output rules: grey is replicated to three channels, depths 1 / 2 / 4 scaled by 255 / 85 / 17; palette entries are looked up
+(an index beyond the PLTE length gives 0); alpha channels and tRNS are dropped, not blended; 16-bit samples keep their high byte
+(libpng's strip_16); no gamma, no sBIT, no background.
+
+This restates libpng's documented transforms as OpenCV requests them for IMREAD_COLOR.  Parity with cv2 itself is UNPINNED: cv2 is
+not importable in this build, so no test compares against it (tests/png_cases.py holds an independent encoder and a NumPy statement
+of the rules above).  A file this module refuses raises ValueError naming the cause, where cv2.imdecode returns None.
+"""
+import collections
+import os
+import struct
+import zlib
+
+import numpy as np
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+LEGAL_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
+ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))      # x0, y0, dx, dy
+
+Header = collections.namedtuple("Header", "width height bit_depth color_type interlace")
+Pass = collections.namedtuple("Pass", "x0 y0 dx dy pass_w pass_h rowbytes stream_offset")
+# palette: uint8 [256][3] in B, G, R order, zero beyond the file's PLTE; stream: the inflated scanlines of all passes as bytes;
+# passes: the non-empty passes in stream order; bpp: the filter's byte distance, max(1, channels * bit_depth / 8)
+Image = collections.namedtuple("Image", "header palette stream passes bpp")
+
+
+def _unfilter_constant(name):
+    from radnet_hip.lib import header_constant
+    return header_constant(name)
+
+
+# band and chunk of radnet_png_unfilter_u8 (the seams its tests straddle), read from the header the kernel is compiled with
+UNFILTER_BAND_ROWS = _unfilter_constant("RADNET_PNG_UNFILTER_BAND_ROWS")
+UNFILTER_CHUNK_BYTES = _unfilter_constant("RADNET_PNG_UNFILTER_CHUNK_BYTES")
+
+
+def _chunk(data, pos):
+    """(type, payload, position after the chunk) of the chunk at `pos`; checks its length and CRC."""
+    if pos + 12 > len(data):
+        raise ValueError("PNG: truncated file (chunk header at byte %d)" % pos)
+    length, kind = struct.unpack(">I4s", data[pos:pos + 8])
+    end = pos + 8 + length
+    if length > 0x7fffffff or end + 4 > len(data):
+        raise ValueError("PNG: truncated file (%r chunk of %d bytes at byte %d)" % (kind, length, pos))
+    payload = data[pos + 8:end]
+    if zlib.crc32(payload, zlib.crc32(kind)) != struct.unpack(">I", data[end:end + 4])[0]:
+        raise ValueError("PNG: CRC mismatch in the %r chunk at byte %d" % (kind, pos))
+    return kind, payload, end + 4
+
+
+def _header(data):
+    if data[:8] != SIGNATURE:
+        raise ValueError("PNG: bad signature")
+    if len(data) < 33 or data[8:16] != b"\x00\x00\x00\rIHDR":
+        raise ValueError("PNG: IHDR missing or not the first chunk")
+    _, ihdr, _ = _chunk(data, 8)
+    width, height, depth, color, compression, filt, interlace = struct.unpack(">IIBBBBB", ihdr)
+    if width == 0 or height == 0 or width > 0x7fffffff or height > 0x7fffffff:
+        raise ValueError("PNG: illegal size %d x %d" % (width, height))
+    if color not in LEGAL_DEPTHS or depth not in LEGAL_DEPTHS[color]:
+        raise ValueError("PNG: illegal colour type / bit depth pair %d / %d" % (color, depth))
+    if compression != 0 or filt != 0 or interlace not in (0, 1):
+        raise ValueError("PNG: unknown compression / filter / interlace method %d / %d / %d" % (compression, filt, interlace))
+    return Header(width, height, depth, color, interlace)
+
+
+def read_header(data_or_path):
+    """(width, height, bit_depth, color_type, interlace) from the first 33 bytes of a file (a path) or of its bytes."""
+    if isinstance(data_or_path, (str, os.PathLike)):
+        with open(data_or_path, "rb") as f:
+            head = f.read(33)
+    else:
+        head = bytes(memoryview(data_or_path)[:33])
+    return _header(head)
+
+
+def pass_geometry(header):
+    """The non-empty passes of an image, in stream order: Pass(x0, y0, dx, dy, pass_w, pass_h, rowbytes, stream_offset)."""
+    bits = CHANNELS[header.color_type] * header.bit_depth
+    grid = ADAM7 if header.interlace else ((0, 0, 1, 1),)
+    passes, offset = [], 0
+    for x0, y0, dx, dy in grid:
+        pw, ph = -(-(header.width - x0) // dx), -(-(header.height - y0) // dy)
+        if pw <= 0 or ph <= 0:
+            continue                                   # an empty pass occupies no bytes in the stream
+        rowbytes = (pw * bits + 7) // 8
+        passes.append(Pass(x0, y0, dx, dy, pw, ph, rowbytes, offset))
+        offset += ph * (1 + rowbytes)
+    return passes, offset
+
+
+def parse(data):
+    """Container and zlib: Image(header, palette, stream, passes, bpp).  Raises ValueError naming the cause for a bad signature, a
+    CRC mismatch, a missing / misplaced IHDR, an illegal colour type / depth pair, a type-3 file without PLTE, a truncated or
+    over-long inflated stream and a filter-type byte above 4.  Data after IEND is ignored."""
+    data = bytes(data)
+    header = _header(data)
+    pos, idat, plte, ended = 33, [], None, False
+    while pos < len(data):
+        kind, payload, pos = _chunk(data, pos)
+        if kind == b"IHDR":
+            raise ValueError("PNG: a second IHDR chunk")
+        if kind == b"PLTE":
+            if len(payload) % 3 or not 3 <= len(payload) <= 768:
+                raise ValueError("PNG: PLTE chunk of %d bytes" % len(payload))
+            plte = payload
+        elif kind == b"IDAT":
+            idat.append(payload)
+        elif kind == b"IEND":
+            ended = True
+            break
+    if not ended:
+        raise ValueError("PNG: truncated file (no IEND chunk)")
+    if header.color_type == 3 and plte is None:
+        raise ValueError("PNG: palette (PLTE) missing for colour type 3")
+    palette = np.zeros((256, 3), np.uint8)
+    if plte is not None:
+        rgb = np.frombuffer(plte, np.uint8).reshape(-1, 3)
+        palette[:rgb.shape[0]] = rgb[:, ::-1]
+    passes, expected = pass_geometry(header)
+    inflater = zlib.decompressobj()
+    try:
+        stream = inflater.decompress(b"".join(idat), expected + 1)
+    except zlib.error as e:
+        raise ValueError("PNG: the IDAT stream does not inflate (%s)" % e) from e
+    if len(stream) < expected:
+        raise ValueError("PNG: truncated inflated stream (%d of %d bytes)" % (len(stream), expected))
+    if len(stream) > expected:
+        raise ValueError("PNG: over-long inflated stream (more than the %d bytes of the image)" % expected)
+    column = np.frombuffer(stream, np.uint8)
+    for p in passes:
+        worst = int(column[p.stream_offset:p.stream_offset + p.pass_h * (1 + p.rowbytes):1 + p.rowbytes].max())
+        if worst > 4:
+            raise ValueError("PNG: filter type %d (above 4) in the pass at (%d, %d)" % (worst, p.x0, p.y0))
+    return Image(header, palette, stream, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8))
+
+
+def decode_device(data, ctx=None):
+    """The decoded image as a uint8 [H][W][3] (B, G, R) cuda tensor: parse, ONE pinned upload of the inflated stream (the palette
+    rides behind it), then reconstruction and expansion per pass.  ctx: a radnet context whose stream is torch's current one;
+    None = the calling thread's default context, on a BackgroundFeed worker thread on that thread's own stream."""
+    import torch
+    from . import augmentation_device as AD
+    img = parse(data)
+    n = len(img.stream)
+    with AD.feed_stream(ctx) as (ctx, side):
+        staged = torch.empty(n + 768, dtype=torch.uint8, pin_memory=True)
+        host = staged.numpy()
+        host[:n] = np.frombuffer(img.stream, np.uint8)
+        host[n:] = img.palette.reshape(-1)
+        dev = staged.cuda(non_blocking=True)
+        out = torch.empty((img.header.height, img.header.width, 3), dtype=torch.uint8, device="cuda")
+        base = dev.data_ptr()
+        for p in img.passes:
+            ctx.call("radnet_png_unfilter_u8", base + p.stream_offset, p.pass_h, p.rowbytes, img.bpp)
+            ctx.call("radnet_png_expand_bgr_u8", base + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, img.header.color_type, img.header.bit_depth,
+                     base + n, out, img.header.height, img.header.width, p.y0, p.x0, p.dy, p.dx)
+    return AD.hand_over(out, side)
+
+
+def imdecode_color(data):
+    """cv2.imdecode(data, cv2.IMREAD_COLOR) for a PNG file's bytes: decode_device, downloaded to a NumPy array."""
+    return decode_device(data).cpu().numpy()

@@ -149,6 +149,15 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(radnet_[a-z0-9_]+)\s*\(", text)))
 
 
+def header_constant(name):
+    """Integer value of `#define name <integer>` in the public header (constants a kernel and its tests share)."""
+    with open(HEADER_PATH) as f:
+        m = re.search(r"^#define\s+%s\s+(-?\d+)\s*$" % re.escape(name), f.read(), flags=re.M)
+    if m is None:
+        raise RadnetError("include/radnet_hip.h does not define %s" % name)
+    return int(m.group(1))
+
+
 def load_library():
     """dlopen the in-tree library; raises RadnetError (never falls back) when it is absent."""
     global _lib
@@ -250,6 +259,8 @@ def load_library():
         "radnet_aug_extent_u8": (C.c_int, [vp, vp, i32, i32, vp]),
         "radnet_aug_histogram_u8": (C.c_int, [vp, vp, i32, i32, i32, vp]),
         "radnet_aug_pointwise_u8": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f64, f64, u64, C.c_uint32]),
+        "radnet_png_unfilter_u8": (C.c_int, [vp, vp, i32, i32, i32]),
+        "radnet_png_expand_bgr_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32]),
         "radnet_fill_zero": (C.c_int, [vp, vp, u64]),
         "radnet_copy_bytes": (C.c_int, [vp, vp, vp, C.c_uint64]),
         "radnet_program_run": (C.c_int, [vp, C.POINTER(Op), i32]),
