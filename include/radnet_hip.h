@@ -420,6 +420,16 @@ int radnet_copy_bytes(radnet_ctx* ctx, void* dst, const void* src, uint64_t byte
  * Parity unpinned (OpenCV absent offline). */
 int radnet_resize_bicubic_u8(radnet_ctx* ctx, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh,
                              int32_t dw, int32_t channels);
+/* The tile cut and the resize of the predict tile loop in ONE launch, for an image that is already on the device (RADNet.py:545-547:
+ * np.copy(img[ty0:ty1, tx0:tx1, :]) then format_img's cv2.resize; RADNet.py:348-350: the full-image pass, the window that covers
+ * the image).  dst (dh x dw x channels, contiguous) receives exactly the bytes radnet_resize_bicubic_u8 writes for a contiguous
+ * copy of the window src[y0:y0+wh, x0:x0+ww, :] of the sh x sw image: the four taps replicate at the WINDOW's edges, not the
+ * image's (a tile from the middle of a scan never sees its neighbours' pixels), the scale factors come from (wh, ww) -> (dh, dw),
+ * and with (dh, dw) == (wh, ww) the output is the window's bytes (coefficients exactly 0, 2048, 0, 0).  The kernel never reads
+ * outside the window.  RADNET_ERR_ARG, and nothing is launched, when ctx, src or dst is null, any extent is below 1, y0 < 0,
+ * x0 < 0, y0 + wh > sh or x0 + ww > sw. */
+int radnet_resize_bicubic_window_u8(radnet_ctx* ctx, const uint8_t* src, int32_t sh, int32_t sw, int32_t y0, int32_t x0, int32_t wh,
+                                    int32_t ww, uint8_t* dst, int32_t dh, int32_t dw, int32_t channels);
 /* cv2.warpAffine(src, M, (dw, dh)) with its defaults (INTER_LINEAR, BORDER_CONSTANT 0) for uint8 HWC tiles: the +-3 degree rotation
  * and the shear of the train-time augmentation (augmentation.py:158-271).  The caller inverts M and passes the inverse map's
  * per-column and per-row terms in 10-bit fixed point, rounded in float64 as OpenCV does: col_tab = {adelta[dw], bdelta[dw]},

@@ -25,8 +25,11 @@ __device__ __forceinline__ void cubic_coeffs(float x, short* c) {
   }
 }
 
-__global__ void __launch_bounds__(256) resize_bicubic_u8_kernel(const uint8_t* __restrict__ src, int sh, int sw, uint8_t* __restrict__ dst, int dh,
-                                                                int dw, int ch) {
+// One body for both entry points: `src` points at the first byte of the sh x sw region the taps may read (the whole image, or the
+// window's origin inside a larger image), `pitch` is the distance in bytes between two of its rows (the IMAGE's sw * ch; equal to
+// the region's own for a whole image).  The taps clamp to the region, so nothing outside it is read.
+__global__ void __launch_bounds__(256) resize_bicubic_u8_kernel(const uint8_t* __restrict__ src, long long pitch, int sh, int sw,
+                                                                uint8_t* __restrict__ dst, int dh, int dw, int ch) {
   const long long total = (long long)dh * dw;
   const double scale_x = 1.0 / ((double)dw / sw), scale_y = 1.0 / ((double)dh / sh);      // OpenCV: 1. / inv_scale
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -47,7 +50,7 @@ __global__ void __launch_bounds__(256) resize_bicubic_u8_kernel(const uint8_t* _
         int row = 0;
         for (int i = 0; i < 4; ++i) {
           const int xx = min(max(sx - 1 + i, 0), sw - 1);
-          row += (int)src[((long long)yy * sw + xx) * ch + c] * ax[i];
+          row += (int)src[(long long)yy * pitch + (long long)xx * ch + c] * ax[i];
         }
         acc += row * ay[j];
       }
@@ -57,17 +60,33 @@ __global__ void __launch_bounds__(256) resize_bicubic_u8_kernel(const uint8_t* _
   }
 }
 
+int launch_resize(radnet_ctx* ctx, const char* what, const uint8_t* src, long long pitch, int sh, int sw, uint8_t* dst, int dh, int dw, int ch) {
+  long long total = (long long)dh * dw;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(resize_bicubic_u8_kernel, dim3(blocks), dim3(256), 0, ctx->stream, src, pitch, sh, sw, dst, dh, dw, ch);
+  RADNET_CHECK_LAUNCH(ctx, what);
+  return RADNET_OK;
+}
+
 }  // namespace
 
 extern "C" int radnet_resize_bicubic_u8(radnet_ctx* ctx, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw,
                                         int32_t channels) {
   if (!ctx || !src || !dst || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || channels <= 0) return RADNET_ERR_ARG;
-  long long total = (long long)dh * dw;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(resize_bicubic_u8_kernel, dim3(blocks), dim3(256), 0, ctx->stream, src, sh, sw, dst, dh, dw, channels);
-  RADNET_CHECK_LAUNCH(ctx, "resize_bicubic_u8");
-  return RADNET_OK;
+  return launch_resize(ctx, "resize_bicubic_u8", src, (long long)sw * channels, sh, sw, dst, dh, dw, channels);
+}
+
+// The tile cut and the resize of RADNet.predict's tile loop (RADNet.py:545-547 np.copy(img[ty0:ty1, tx0:tx1, :]) -> format_img, and
+// 348-350 for the full image) in one launch on an image that is already on the device: the same computation with the source
+// pointer moved to the window's origin, the image's row pitch kept, and the window's extent as the clamp extent -- so a tile cut
+// from the middle of a scan replicates ITS OWN edge pixels, exactly as the resize of a contiguous copy of it does.
+extern "C" int radnet_resize_bicubic_window_u8(radnet_ctx* ctx, const uint8_t* src, int32_t sh, int32_t sw, int32_t y0, int32_t x0, int32_t wh,
+                                               int32_t ww, uint8_t* dst, int32_t dh, int32_t dw, int32_t channels) {
+  if (!ctx || !src || !dst || sh <= 0 || sw <= 0 || wh <= 0 || ww <= 0 || dh <= 0 || dw <= 0 || channels <= 0) return RADNET_ERR_ARG;
+  if (y0 < 0 || x0 < 0 || (long long)y0 + wh > sh || (long long)x0 + ww > sw) return RADNET_ERR_ARG;
+  const long long pitch = (long long)sw * channels;
+  return launch_resize(ctx, "resize_bicubic_window_u8", src + (long long)y0 * pitch + (long long)x0 * channels, pitch, wh, ww, dst, dh, dw, channels);
 }
 
 // ---- affine warp of uint8 HWC tiles: the arbitrary-angle rotation and the shear of the train-time augmentation -------------

@@ -8,7 +8,8 @@
 
 The model objects are duck-typed exactly as in the reference (anything with .predict works, which is how the
 golden tests drive this class with closed-form fake models); load_radnet() builds them on the HIP engine.
-NMS runs in libradnet_hip.so through faster_rcnn.rpn; the tile resize runs on the device (radnet_resize_bicubic_u8).
+NMS runs in libradnet_hip.so through faster_rcnn.rpn; the tile resize runs on the device (radnet_resize_bicubic_u8, or for an
+image that is already there radnet_resize_bicubic_window_u8: tile cut + resize in one launch, see ImageWindow).
 """
 import pickle
 import sys
@@ -28,6 +29,61 @@ def _spans(length, tile, step):
     pairs = {(int(s), int(e)) for s, e in zip(starts[ok], ends[ok])}
     pairs.add((max(0, length - tile), int(length)))
     return sorted(pairs)
+
+
+class ImageWindow:
+    """A tile of an image that is on the device, as a DESCRIPTION: the image and the window [y0, y0 + wh) x [x0, x0 + ww) of it,
+    where the host path holds np.copy(img[y0:y0+wh, x0:x0+ww, :]) (RADNet.py:545).  `.shape` is the copied tile's, so
+    format_img_size derives the same ratio, new_w and new_h from it; format_img_size(..., keep_on_device=True) turns it into one
+    resize_cubic_window launch.  `ready`: an event after which the image's bytes are valid (its producer's position; None: they
+    already are for every stream that will read them)."""
+    __slots__ = ("img", "x0", "y0", "ww", "wh", "ready")
+
+    def __init__(self, img, x0, y0, ww, wh, ready=None):
+        self.img, self.x0, self.y0, self.ww, self.wh, self.ready = img, int(x0), int(y0), int(ww), int(wh), ready
+
+    @property
+    def shape(self):
+        return (self.wh, self.ww, 3)
+
+    def covers_image(self):
+        return (self.y0, self.x0) == (0, 0) and (self.wh, self.ww) == tuple(self.img.shape[:2])
+
+
+def tile_windows(img, C, ready=None):
+    """The work list of one image in predict (RADNet.py:511-547, 348-350) as (windows, offsets): the tiles of _spans in the
+    reference's order -- rows outer, columns inner -- when C.max_n_tiles_train > 0, then the whole image when C.include_full_img.
+    Only img.shape is looked at."""
+    h, w = img.shape[:2]
+    spans = []
+    if C.max_n_tiles_train > 0:                 # the reference gates tiling on this training knob (RADNet.py:511)
+        spans = [(tx0, ty0, tx1, ty1) for (ty0, ty1) in _spans(h, C.tile_size, C.tile_overlap) for (tx0, tx1) in _spans(w, C.tile_size, C.tile_overlap)]
+    work = [ImageWindow(img, tx0, ty0, tx1 - tx0, ty1 - ty0, ready) for (tx0, ty0, tx1, ty1) in spans]
+    offs = [(tx0, ty0) for (tx0, ty0, tx1, ty1) in spans]
+    if C.include_full_img:
+        work.append(ImageWindow(img, 0, 0, w, h, ready))
+        offs.append((0, 0))
+    return work, offs
+
+
+def _is_device_image(img):
+    return not isinstance(img, np.ndarray) and bool(getattr(img, "is_cuda", False))
+
+
+def check_device_image(img):
+    """predict takes a device image as a uint8 [H][W][3] contiguous cuda tensor; anything else is refused here, by what is wrong."""
+    import torch
+    if img.dtype != torch.uint8:
+        raise TypeError("predict: a device image must be uint8, not %s" % (img.dtype,))
+    if img.dim() != 3:
+        raise ValueError("predict: a device image must have rank 3 ([H][W][3]), not rank %d" % img.dim())
+    if img.shape[2] != 3:
+        raise ValueError("predict: a device image must have 3 channels ([H][W][3]), not %d" % img.shape[2])
+    if img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("predict: a device image must not be empty, shape %s" % (tuple(img.shape),))
+    if not img.is_contiguous():
+        raise ValueError("predict: a device image must be contiguous (strides %s for shape %s)" % (img.stride(), tuple(img.shape)))
+    return img
 
 
 class RADNet():
@@ -51,7 +107,8 @@ class RADNet():
 
     def format_img_size(self, img, keep_on_device=False, ctx=None):
         """Short side -> C.img_size, long side truncated (RADNet.py:53-74); bicubic resize on the device.
-        keep_on_device: return the resized uint8 image as a device tensor (the device-resident tile path)."""
+        keep_on_device: return the resized uint8 image as a device tensor (the device-resident tile path).  An ImageWindow (a tile
+        of an image that is already on the device) becomes one resize_cubic_window launch on the lane this is called from."""
         side = float(self.C.img_size)
         height, width = img.shape[:2]
         if width <= height:
@@ -60,6 +117,15 @@ class RADNet():
         else:
             ratio = side / height
             new_w, new_h = int(ratio * width), int(side)
+        if isinstance(img, ImageWindow):
+            if not keep_on_device:
+                raise TypeError("format_img_size: an ImageWindow is resized on the device (keep_on_device=True)")
+            if img.ready is not None:
+                import torch
+                torch.cuda.current_stream().wait_event(img.ready)      # the lane reads the image only behind its producer
+            if (new_h, new_w) == (height, width) and img.covers_image():
+                return img.img, ratio                                  # propose_launch copies it into the plan's panel
+            return resize_cubic_window(img.img, img.x0, img.y0, img.ww, img.wh, new_w, new_h, ctx=ctx), ratio
         if keep_on_device:
             return resize_cubic(img, new_w, new_h, to_host=False, ctx=ctx), ratio
         if (new_h, new_w) != (height, width):
@@ -167,19 +233,29 @@ class RADNet():
         preprocess -> base -> RPN -> decode/sort/NMS -> RoI crop-resize -> classifier): PCIe carries the source tile in and
         ~40 KB of proposals and class scores out.  `device_resident = False` forces the NumPy-facing calls the reference
         makes (RADNet.py:540-560); both give the same detections (same kernels), tests compare them."""
+        ctx = self._engine().ctx if isinstance(img, ImageWindow) else None      # a window is resized on the lane the network runs on
         if self._tail_on_device():
-            img_dev, ratio = self.format_img_size(img, keep_on_device=True)
+            img_dev, ratio = self.format_img_size(img, keep_on_device=True, ctx=ctx)
             h = self.model_rpn.propose_launch(img_dev, overlap_thresh=0.7)
             n = self.model_rpn.count_finish(self.model_rpn.count_launch(h))
             return self._tail_collect(self._tail_launch(h, n, ratio))
         if self.device_resident and hasattr(self.model_rpn, "propose_device"):
-            img_dev, ratio = self.format_img_size(img, keep_on_device=True)
+            img_dev, ratio = self.format_img_size(img, keep_on_device=True, ctx=ctx)
             R, F = self.model_rpn.propose_device(img_dev, overlap_thresh=0.7)
         else:
             X, ratio = self.format_img(img)
             Y1, Y2, F = self.model_rpn.predict(X)
             R = rpn.rpn_to_roi(Y1, Y2, self.C, overlap_thresh=0.7)
         return self._finish_detect(R, F, ratio)
+
+    def _engine(self):
+        return getattr(getattr(self.model_rpn, "_s", None), "eng", None)
+
+    def _takes_device_images(self):
+        """Engine-backed models with `device_resident`: a device image stays where it is and its tiles are ImageWindows.  Otherwise
+        (duck-typed models, device_resident = False) predict downloads it once and takes the host path."""
+        return (self.device_resident and hasattr(self.model_rpn, "propose_launch") and hasattr(self.model_rpn, "propose_device")
+                and self._engine() is not None)
 
     def _finish_detect(self, R, F, ratio):
         R[:, 2] -= R[:, 0]
@@ -248,7 +324,7 @@ class RADNet():
         """_detect over a list of tiles, in order.  With the engine-backed models two tiles are in flight: while the
         classifier works on tile j (main lane), tile j+1 is uploaded, resized and run through the base network, the RPN and
         the proposal kernels on the engine's side lane, in the other buffer set.  Same kernels, same results as _detect."""
-        eng = getattr(getattr(self.model_rpn, "_s", None), "eng", None)
+        eng = self._engine()
         if not (self.device_resident and hasattr(self.model_rpn, "propose_launch") and eng is not None and hasattr(eng, "lane") and len(tiles) > 1):
             return [self._detect(t) for t in tiles]
         if self._tail_on_device():
@@ -311,10 +387,29 @@ class RADNet():
         assert all(o is not None for o in out)
         return out
 
+    def _detect_device_image(self, img):
+        """The tile passes of one image that is on the device: (detections per window, window offsets).  The image may have been
+        produced on the caller's current stream (png.decode_device hands it over there): its position is recorded and every lane
+        waits for it before its first read (ImageWindow.ready).  The passes run with the engine's main stream current -- the stream
+        its main context launches on -- whatever stream the caller is on.  The caller's reference keeps the image alive until the
+        last window's records are on the host, which is behind the last launch that reads it."""
+        import torch
+        eng = self._engine()
+        ready = eng.mark()
+        work, offs = tile_windows(img, self.C, ready)
+        with torch.cuda.stream(eng.main_stream):
+            return self._detect_sharded(work), offs
+
     def predict(self, images):
         """RADNet.py:502-718: tile -> RPN -> NMS -> RoI crop-resize -> classifier -> per-class NMS, box-averaging
-        merge per image, then NMS 0.4 across images."""
+        merge per image, then NMS 0.4 across images.  An image is a NumPy array or a uint8 [H][W][3] contiguous cuda tensor
+        (png.decode_device, utils_io.get_image(..., to_host=False), utils_io.DeviceImageLoader).  With the engine-backed models a
+        device image stays on the device: every tile is cut out of it and resized in one launch (ImageWindow) and nothing
+        image-sized crosses PCIe; the detections are those of the host array with the same bytes."""
         C = self.C
+        for img in images:
+            if _is_device_image(img):
+                check_device_image(img)             # every image, before any device work starts
         all_boxes, all_probs = {}, {}
         for img in images:
             boxes_img, probs_img = {}, {}
@@ -325,14 +420,20 @@ class RADNet():
                         boxes_img.setdefault(key, []).append([ox + rx1, oy + ry1, ox + rx2, oy + ry2])
                         probs_img.setdefault(key, []).append(p)
 
-            if C.max_n_tiles_train > 0:                 # the reference gates tiling on this training knob (RADNet.py:511)
-                h, w = img.shape[:2]
-                spans = [(tx0, ty0, tx1, ty1) for (ty0, ty1) in _spans(h, C.tile_size, C.tile_overlap) for (tx0, tx1) in _spans(w, C.tile_size, C.tile_overlap)]
+            if _is_device_image(img) and not self._takes_device_images():
+                img = img.cpu().numpy()             # one download, then the host path
+            if _is_device_image(img):
+                dets_img, offs = self._detect_device_image(img)
             else:
-                spans = []
-            work = [np.copy(img[ty0:ty1, tx0:tx1, :]) for (tx0, ty0, tx1, ty1) in spans] + ([img] if C.include_full_img else [])
-            offs = [(tx0, ty0) for (tx0, ty0, tx1, ty1) in spans] + ([(0, 0)] if C.include_full_img else [])
-            for det, (ox, oy) in zip(self._detect_sharded(work), offs):
+                if C.max_n_tiles_train > 0:                 # the reference gates tiling on this training knob (RADNet.py:511)
+                    h, w = img.shape[:2]
+                    spans = [(tx0, ty0, tx1, ty1) for (ty0, ty1) in _spans(h, C.tile_size, C.tile_overlap) for (tx0, tx1) in _spans(w, C.tile_size, C.tile_overlap)]
+                else:
+                    spans = []
+                work = [np.copy(img[ty0:ty1, tx0:tx1, :]) for (tx0, ty0, tx1, ty1) in spans] + ([img] if C.include_full_img else [])
+                offs = [(tx0, ty0) for (tx0, ty0, tx1, ty1) in spans] + ([(0, 0)] if C.include_full_img else [])
+                dets_img = self._detect_sharded(work)
+            for det, (ox, oy) in zip(dets_img, offs):
                 collect(det, ox, oy)
             for key in boxes_img:
                 nb, npr = self.final_nms(np.array(boxes_img[key]), np.array(probs_img[key]), obj_avg_threshold=0.2,
@@ -350,13 +451,15 @@ class RADNet():
 
     def predict_from_path(self, img_path):
         """RADNet.py:482-500: one image per type of C.img_types when C.use_img_type, else the first type's, each read by
-        utils_io.get_image (faster_rcnn/png.py decodes; no OpenCV), then predict on the host arrays."""
+        utils_io.get_image (faster_rcnn/png.py decodes; no OpenCV), then predict.  With the engine-backed models and
+        `device_resident` the decoded images stay on the device (get_image(..., to_host=False)); otherwise they are host arrays."""
         from . import utils_io
         C = self.C
+        to_host = not self._takes_device_images()
         if C.use_img_type:
-            images = [utils_io.get_image(img_path, [img_type], random_type=False) for img_type in C.img_types]
+            images = [utils_io.get_image(img_path, [img_type], random_type=False, to_host=to_host) for img_type in C.img_types]
         else:
-            images = [utils_io.get_image(img_path, C.img_types, random_type=False)]
+            images = [utils_io.get_image(img_path, C.img_types, random_type=False, to_host=to_host)]
         return self.predict(images)
 
 
@@ -382,6 +485,30 @@ def resize_cubic(img, new_w, new_h, to_host=True, ctx=None):
         # a device result made on the worker's stream: its consumer's stream waits, and the caching allocator is told that the
         # memory is in use there too (it was allocated under `side`; without this it could be handed out again while the
         # consumer still reads it)
+        torch.cuda.current_stream().wait_stream(side)
+        out.record_stream(torch.cuda.current_stream())
+    return out
+
+
+def resize_cubic_window(img_dev, x0, y0, ww, wh, new_w, new_h, ctx=None):
+    """cv2.resize(np.copy(img[y0:y0+wh, x0:x0+ww, :]), (new_w, new_h), interpolation=cv2.INTER_CUBIC) for an image that is on the
+    device, in one launch (radnet_resize_bicubic_window_u8): the taps replicate at the window's edges.  uint8 HWC contiguous cuda
+    tensor in, uint8 cuda tensor out; ctx and streams as resize_cubic(..., to_host=False, ctx=...)."""
+    import contextlib
+    import torch
+    from radnet_hip import runtime as rt
+    if not (isinstance(img_dev, torch.Tensor) and img_dev.is_cuda and img_dev.dtype == torch.uint8 and img_dev.dim() == 3 and img_dev.is_contiguous()):
+        raise TypeError("resize_cubic_window takes a contiguous uint8 HWC cuda tensor")
+    own = ctx is None
+    ctx = rt.default_context() if own else ctx                  # a lane's context: the kernel goes to that lane's stream
+    side = rt.thread_stream() if own else None                  # a worker thread resizes on its own stream (BackgroundFeed)
+    sh, sw, ch = (int(v) for v in img_dev.shape)
+    if side is not None:
+        side.wait_stream(torch.cuda.current_stream())           # the image was made on (or handed over to) the caller's stream
+    with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+        out = torch.empty((int(new_h), int(new_w), ch), dtype=torch.uint8, device=img_dev.device)
+        ctx.call("radnet_resize_bicubic_window_u8", img_dev, sh, sw, int(y0), int(x0), int(wh), int(ww), out, int(new_h), int(new_w), ch)
+    if side is not None:                                        # as resize_cubic: the consumer's stream waits, the allocator is told
         torch.cuda.current_stream().wait_stream(side)
         out.record_stream(torch.cuda.current_stream())
     return out

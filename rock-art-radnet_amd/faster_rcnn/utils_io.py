@@ -50,7 +50,8 @@ class DeviceImageLoader:
     by (path, type, file size, mtime) and bounded by cache_bytes of device memory.  A feed draws up to C.max_n_tiles_train tiles
     from one image back to back and decodes the image for each (utils.py:390), so a cache of a few images removes most decodes.
     cache_bytes=0 disables it; an image larger than the bound is decoded and not kept.  hits / misses count the calls.  The cached
-    tensors are handed out as they are: the feed reads them (tile gather) and never writes them."""
+    tensors are handed out as they are: the feed reads them (tile gather) and never writes them.  The images can also be passed to
+    RADNet.predict directly: with the engine-backed models it cuts and resizes every tile on the device (RADNet.ImageWindow)."""
 
     def __init__(self, cache_bytes=1 << 30, decode=None):
         self.cache_bytes = int(cache_bytes)

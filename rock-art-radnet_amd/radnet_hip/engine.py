@@ -189,6 +189,7 @@ class FasterRCNNEngine:
         self.C = C_cfg
         self.dev = torch.device("cuda", device_index)
         torch.cuda.set_device(self.dev)
+        self.main_stream = torch.cuda.current_stream(self.dev)      # the stream the main context launches on
         self.ctx = L.Context(device_index)
         self.lib = self.ctx.lib
         self.A = len(C_cfg.anchor_box_scales) * len(C_cfg.anchor_box_ratios)

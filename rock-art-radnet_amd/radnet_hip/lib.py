@@ -254,6 +254,7 @@ def load_library():
         "radnet_host_choice_round": (i64, [vp, vp, vp, vp, i64, vp, i64, vp, vp]),
         "radnet_preprocess_bgr": (C.c_int, [vp, vp, i32, i32, i32, vp]),
         "radnet_resize_bicubic_u8": (C.c_int, [vp, vp, i32, i32, vp, i32, i32, i32]),
+        "radnet_resize_bicubic_window_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32]),
         "radnet_warp_affine_u8": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
         "radnet_aug_gather_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "radnet_aug_extent_u8": (C.c_int, [vp, vp, i32, i32, vp]),
