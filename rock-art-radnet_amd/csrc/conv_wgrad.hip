@@ -134,7 +134,11 @@ static int run_wgrad(radnet_ctx* ctx, const radnet_conv_desc* d, int batch, long
       g.atomic = 0;
       wgrad_slab_bytes = need + 256;
     } else if (splits > 1 && d->dw_accumulate == 0) {  // atomics need a zeroed destination
-      RADNET_CHECK_HIP(ctx, hipMemsetAsync(d->dw, 0, (batch > 1 ? (size_t)batch * dw_bs : (size_t)g.K * g.ldw) * sizeof(float), ctx->stream));
+      // a pitched dw (a column block of a wider tensor): only the n columns of each row are this layer's to clear
+      if (batch <= 1 && g.ldw != g.N)
+        RADNET_CHECK_HIP(ctx, hipMemset2DAsync(d->dw, (size_t)g.ldw * sizeof(float), 0, (size_t)g.N * sizeof(float), (size_t)g.K, ctx->stream));
+      else
+        RADNET_CHECK_HIP(ctx, hipMemsetAsync(d->dw, 0, (batch > 1 ? (size_t)batch * dw_bs : (size_t)g.K * g.ldw) * sizeof(float), ctx->stream));
     }
     if (ctx->pair_capture != nullptr) {
       PairCapture* pc = (PairCapture*)ctx->pair_capture;
@@ -203,7 +207,7 @@ static int run_wgrad(radnet_ctx* ctx, const radnet_conv_desc* d, int batch, long
       fprintf(stderr, "radnet tune: wgrad M=%d N=%d K=%d C=%d -> tile %dx%d slices %d : %.1f us (%.1f TFLOP/s)\n", g.M, g.N, g.K, g.C,
               bmk, bn, splits, best * 1e3, 2.0 * g.M * g.N * g.K / (best * 1e9));
     if (d->dw_accumulate == 2)               // the trial launches added into the pre-zeroed buffer: restore it
-      RADNET_CHECK_HIP(ctx, hipMemsetAsync(d->dw, 0, (size_t)g.K * g.ldw * sizeof(float), ctx->stream));
+      RADNET_CHECK_HIP(ctx, hipMemset2DAsync(d->dw, (size_t)g.ldw * sizeof(float), 0, (size_t)g.N * sizeof(float), (size_t)g.K, ctx->stream));
   } else {
     // accumulate mode reuses the overwrite-mode measurement when there is one
     const radnet_shape_key k0{2, g.M, g.N, g.K, g.C, d->kh * d->kw, g.stride};
