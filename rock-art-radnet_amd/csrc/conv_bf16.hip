@@ -2,7 +2,8 @@
 //
 // The predict-only twin of the fp32 forward kernel (conv_igemm_body.h, conv_mfma.hip) (keras Conv2D + FixedBatchNormalization + Add + Activation,
 // base_models/resnet50.py:41-147,183-186; rpn.py:41-64) for frozen weights: bf16 MFMA runs at 16x the fp32 MFMA rate on
-// gfx950 (no TF32 there), and at inference nothing accumulates the rounding over steps.
+// gfx950 (no TF32 there), and at inference nothing accumulates the rounding over steps.  Tile, waves, LDS layout, the reduction loop
+// and the ordered split are conv_bf16_body.h's; rows = output pixels m, columns = output channels n, reduction = k = (tap, c).
 //
 //   * Weights are cast ONCE per weight load (radnet_weights_to_bf16) into bf16 [N][Kp], Kp = K rounded up to the 32-deep K
 //     tile, zero padded: a lane of the 32x32x16 MFMA holds B[k = 8h + j][col r], j = 0..7, so it reads its 8 k values of
@@ -10,32 +11,12 @@
 //   * Activations stay NHWC fp32 in HBM (RoI crop-resize, the head tail, proposals and NMS are untouched).  Each
 //     workgroup gathers its A tile (BM output pixels x 32 k) straight from the activation tensor with 32-byte buffer loads
 //     (8 consecutive channels of one tap: C % 8 == 0), rounds it to bf16 (round to nearest, ties to even) and writes it to
-//     LDS.  Padding taps, ragged rows / columns and K past the end are the out-of-range offset kOOB that the hardware
-//     answers with zeros -- no branch in the K loop.
-//   * 4 wavefronts in a 2x2 arrangement; each wave owns (BM/2)x(BN/2) of the output as 32x32 accumulator tiles.  Both
-//     operands are row-major [row][32 k + 8 pad] bf16 in LDS (80-byte rows), read as one ds_read_b128 per fragment.  Two
-//     LDS buffers, the global loads of tile t+1 in registers while tile t is multiplied: one barrier per K tile.
+//     LDS.
 //   * Fused epilogue as in conv_igemm_body.h: per-column scale / shift, residual addend, ReLU or sigmoid on [0, act_cols).
-//   * Ordered K split (bf16-mixed training: small M, deep K -- radnet_conv_bf16_pick_split): blockIdx.z = slice of the K
-//     tiles.  conv_igemm_body.h's in-launch protocol: every slice writes its partial tile as a write-through (sc1) slab, drains
-//     it, takes a ticket from the tile's arrival counter; the last arrival sums ALL slabs in slice order (its own read back
-//     too, with sc1 loads), so the result does not depend on arrival order, then runs the epilogue and leaves the counter
-//     at zero.  Slabs live in the context's workspace, counters in its aux block: each lane has its own.  No float atomics:
-//     two runs give the same bits.  ksplit <= 1 is the single-pass launch, unchanged.
-#include "radnet_internal.h"
-#include <hip/hip_ext.h>
+//   * K split (bf16-mixed training: small M, deep K -- radnet_conv_bf16_pick_split); ksplit <= 1 is the single-pass launch.
+#include "conv_bf16_body.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int BK = 32;          // reduction depth per LDS tile (two MFMA steps of 16)
-constexpr int LDSROW = BK + 8;  // bf16 per LDS row: 80 bytes (16-byte aligned, breaks the power-of-two row stride)
-constexpr int NTHREADS = 256;
-constexpr unsigned kOOB = 0x80000000u;   // every descriptor covers < 2 GiB (checked by the launcher): offset + 16 stays out of range
 
 struct Bf16Args {
   const float* x;            // NHWC fp32 input
@@ -44,48 +25,15 @@ struct Bf16Args {
   const float* scale;        // per-column scale or null
   const float* shift;        // per-column shift or null
   const float* addend;       // residual [M][ld_add] or null
-  float* partial;            // K split: slabs [tile][slice][BM*BN] (context workspace)
-  unsigned* counters;        // K split: arrival counter per output tile (context aux block, zero outside a launch)
-  int ksplit;
+  float* partial;            // split: slabs [tile][slice][BM*BN] (context workspace)
+  unsigned* counters;        // split: arrival counter per output tile (context aux block, zero outside a launch)
+  int split;
   int H, W, C, OW, KW, stride, pad_t, pad_l;
   int M, N, K, nkt, ldk, ldy, ld_add, act, act_cols;
   int OHOW;
   unsigned long long magic_ohow, magic_ow, magic_c, magic_kw;
   unsigned x_bytes, w_bytes, y_bytes, add_bytes;
 };
-
-__device__ __forceinline__ int div_magic(int m, unsigned long long magic) {
-  return (int)(((unsigned long long)(unsigned)m * magic) >> 40);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ u32x4 buf_load4u(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-}
-__device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
-}
-// sc1 (aux 16): write-through store / L1-bypassing agent-coherent load, for the slabs handed to the last slice in-launch
-__device__ __forceinline__ f32x4 buf_load4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 16));
-}
-__device__ __forceinline__ void buf_store4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off, const f32x4& v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, 16);
-}
-
-// fp32 -> bf16, round to nearest, ties to even (v_cvt_pk_bf16_f32 on gfx950)
-__device__ __forceinline__ uint16_t to_bf16_bits(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
-__device__ __forceinline__ u32x4 pack8_bf16(const f32x4& lo, const f32x4& hi) {
-  const bf16x8 b = {(__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w, (__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w};
-  return __builtin_bit_cast(u32x4, b);
-}
 
 // wt[n][k] = bf16(w[k][n]) for k < K, 0 for K <= k < ldk
 __global__ void __launch_bounds__(256) weights_to_bf16_kernel(const float* __restrict__ w, int K, int N, int ldw, uint16_t* __restrict__ wt,
@@ -103,9 +51,8 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
   __shared__ __attribute__((aligned(16))) uint16_t sa[2][BM * LDSROW];
   __shared__ __attribute__((aligned(16))) uint16_t sb[2][BN * LDSROW];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, hi = lane >> 5;
+  const int tid = threadIdx.x;
+  const Bf16Lane ln = bf16_lane();
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(g.x, g.x_bytes);
   const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.wt, g.w_bytes);
@@ -159,87 +106,10 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // K tiles [kt0, kt1) of this slice (ksplit <= nkt: none is empty)
-  const int kt0 = SPLIT ? (int)(((long long)g.nkt * blockIdx.z) / g.ksplit) : 0;
-  const int kt1 = SPLIT ? (int)(((long long)g.nkt * (blockIdx.z + 1)) / g.ksplit) : g.nkt;
-  gload(kt0);
-  lstore(0);
-  __syncthreads();
-  for (int kt = kt0; kt < kt1; ++kt) {
-    const int cur = (kt - kt0) & 1;
-    gload(kt + 1 < kt1 ? kt + 1 : kt);               // the last iteration re-loads its own tile (never stored): no branch
-#pragma unroll
-    for (int s = 0; s < BK / 16; ++s) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        af[i] = *reinterpret_cast<const bf16x8*>(&sa[cur][(wm * (BM / 2) + i * 32 + l31) * LDSROW + 16 * s + 8 * hi]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        bfr[j] = *reinterpret_cast<const bf16x8*>(&sb[cur][(wn * (BN / 2) + j * 32 + l31) * LDSROW + 16 * s + 8 * hi]);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    lstore(cur ^ 1);
-    __syncthreads();
-  }
-
+  const int2 kt = SPLIT ? bf16_slice_tiles(g.nkt, g.split, blockIdx.z) : make_int2(0, g.nkt);
+  bf16_gemm_tiles<BM, BN>(sa, sb, kt.x, kt.y, gload, lstore, ln, acc);
   if constexpr (SPLIT) {
-    // slab layout private to this kernel: the 16 registers of a lane's 32x32 accumulator contiguous (four 16-byte accesses)
-    __shared__ int s_last;
-    const unsigned tile_id = blockIdx.x + gridDim.x * blockIdx.y;
-    const unsigned lane_off = (unsigned)((wave * TM * TN * 64 + lane) * 16) * 4u;
-    const __amdgpu_buffer_rsrc_t rslab = make_rsrc(g.partial + ((size_t)tile_id * g.ksplit + blockIdx.z) * (BM * BN), BM * BN * 4u);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-          buf_store4_sc1(rslab, lane_off + (unsigned)(((i * TN + j) * 64 * 16 + q * 4) * 4), v);
-        }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned ticket = __hip_atomic_fetch_add(g.counters + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = ticket == (unsigned)(g.ksplit - 1);
-      if (last) __hip_atomic_store(g.counters + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-      s_last = last;
-    }
-    __syncthreads();
-    if (s_last == 0) return;                         // uniform for the workgroup
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // compiler-only: keeps the slab loads below the ticket
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    for (int s = 0; s < g.ksplit; ++s) {             // slices ADDED in slice (= k) order
-      const __amdgpu_buffer_rsrc_t rs = make_rsrc(g.partial + ((size_t)tile_id * g.ksplit + s) * (BM * BN), BM * BN * 4u);
-      f32x4 v[TM * TN * 4];
-#pragma unroll
-      for (int t = 0; t < TM * TN * 4; ++t) v[t] = buf_load4_sc1(rs, lane_off + (unsigned)(((t >> 2) * 64 * 16 + (t & 3) * 4) * 4));
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 w = v[(i * TN + j) * 4 + q];
-            acc[i][j][4 * q] += w.x; acc[i][j][4 * q + 1] += w.y; acc[i][j][4 * q + 2] += w.z; acc[i][j][4 * q + 3] += w.w;
-          }
-    }
+    if (!bf16_ordered_split<BM, BN>(g.partial, g.counters, g.split, acc)) return;
   }
 
   // epilogue: D[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -250,14 +120,14 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
   const bool has_scale = g.scale != nullptr, relu = g.act == 1, sig = g.act == 2;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * (BN / 2) + j * 32 + l31;
+    const int n = n0 + ln.wn * (BN / 2) + j * 32 + ln.l31;
     const bool nv = n < g.N;
     const unsigned noff = nv ? (unsigned)n * 4u : kOOB;
     const float sc = has_scale ? buf_load1(rsc, noff) : 1.f, sh = buf_load1(rsh, noff);
     const bool sig_col = sig & (n < g.act_cols);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      const int mb = m0 + wm * (BM / 2) + i * 32 + 4 * hi;
+      const int mb = m0 + ln.wm * (BM / 2) + i * 32 + 4 * ln.hi;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = mb + (r & 3) + 8 * (r >> 2);
@@ -272,29 +142,14 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_fwd_kernel(Bf16Args g) {
   }
 }
 
-template <int BM, int BN>
-int launch_bf16(radnet_ctx* ctx, Bf16Args g) {
-  const dim3 grid(radnet_cdiv(g.M, BM), radnet_cdiv(g.N, BN), g.ksplit > 1 ? g.ksplit : 1);
-  if (g.ksplit > 1) {
-    const unsigned long long tiles = (unsigned long long)grid.x * grid.y;
-    if (tiles > kAuxBf16SplitCounterCount)
-      RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_fwd_bf16: %llu output tiles exceed the %zu split counters", tiles, kAuxBf16SplitCounterCount);
-    const unsigned long long need = tiles * (unsigned long long)g.ksplit * BM * BN * 4ull;
-    if (!ctx->ws || ctx->ws_bytes < need)
-      RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: K split %d needs %llu bytes of workspace (radnet_set_workspace: %llu)", g.ksplit, need,
-                  (unsigned long long)ctx->ws_bytes);
-    g.partial = (float*)ctx->ws;
-    g.counters = reinterpret_cast<unsigned*>(ctx->aux + kAuxBf16SplitCounters);
-  }
-  const bool timed = ctx->timing != 0;
-  if (timed) radnet_timing_arm(ctx);
-  auto kernel = g.ksplit > 1 ? conv_bf16_fwd_kernel<BM, BN, true> : conv_bf16_fwd_kernel<BM, BN, false>;
-  if (ctx->arm0) hipExtLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, ctx->arm0, ctx->arm1, 0, g);
-  else hipLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, g);
-  RADNET_CHECK_LAUNCH(ctx, "conv_bf16_fwd_kernel");
-  if (timed) radnet_timing_end_armed(ctx, 0, 2.0 * g.M * (double)g.N * g.K);
-  return RADNET_OK;
-}
+struct FwdLaunch {
+  static constexpr const char* what = "conv_fwd_bf16";
+  static constexpr const char* launch_name = "conv_bf16_fwd_kernel";
+  static constexpr bool halve_split = false;
+  static constexpr int timing_slot = 0;
+  template <int BM, int BN, bool SPLIT>
+  static auto kernel() { return conv_bf16_fwd_kernel<BM, BN, SPLIT>; }
+};
 
 }  // namespace
 
@@ -309,7 +164,7 @@ extern "C" int radnet_weights_to_bf16(radnet_ctx* ctx, const float* w, int32_t k
 }
 
 // output tile of the launch: a fixed rule of (rows, cols) -- the largest tile that still gives every CU a workgroup (0: 128x128, 1: 128x64,
-// 2: 64x64).  The ONE copy of the rule: the forward, both backward launchers (conv_bf16_bwd.hip) and radnet_conv_bf16_tile_shape use it.
+// 2: 64x64).  The ONE copy of the rule: every launch (conv_bf16_body.h: bf16_launch_by_shape) and radnet_conv_bf16_tile_shape use it.
 int radnet_bf16_tile_shape(long long rows, int cols, long long* tiles) {
   const long long t128 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 128), t128x64 = (long long)radnet_cdiv(rows, 128) * radnet_cdiv(cols, 64);
   if (cols > 64 && t128 >= 256) { *tiles = t128; return 0; }
@@ -345,10 +200,7 @@ extern "C" int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_des
   if (!ctx || !d) return RADNET_ERR_ARG;
   if (!d->x || !wt || !d->y) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: null tensor");
   if (d->c % 8 != 0) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_fwd_bf16: %d input channels (needs a multiple of 8)", d->c);
-  if (d->nb <= 0 || d->h <= 0 || d->w_ <= 0 || d->oh <= 0 || d->ow <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->n <= 0)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: bad geometry");
-  if ((d->oh - 1) * d->stride - d->pad_t >= d->h || (d->ow - 1) * d->stride - d->pad_l >= d->w_)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: output %dx%d inconsistent with input %dx%d", d->oh, d->ow, d->h, d->w_);
+  if (int rc = bf16_check_geometry(ctx, d, "conv_fwd_bf16")) return rc;
   const long long K = (long long)d->kh * d->kw * d->c, Kp = (K + BK - 1) / BK * BK;
   if (ldk < Kp || ldk % 8 != 0 || ((uintptr_t)wt & 15) || ((uintptr_t)d->x & 15))
     RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: ldk=%d (needs >= %lld, a multiple of 8, 16-byte aligned operands)", ldk, Kp);
@@ -357,8 +209,7 @@ extern "C" int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_des
     RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: ldy=%d ld_add=%d for %d columns", d->ldy, d->ld_add, d->n);
   const long long x_bytes = (long long)d->nb * d->h * d->w_ * d->c * 4, w_bytes = (long long)d->n * ldk * 2;
   const long long y_bytes = ((M - 1) * d->ldy + d->n) * 4, add_bytes = d->addend ? ((M - 1) * d->ld_add + d->n) * 4 : 0;
-  const long long lim = 1ll << 31;
-  if (x_bytes >= lim || w_bytes >= lim || y_bytes >= lim || add_bytes >= lim || M >= (1 << 20) || K >= (1 << 20))
+  if (bf16_too_large({x_bytes, w_bytes, y_bytes, add_bytes}, {M, K}))
     RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_fwd_bf16: problem too large (M=%lld K=%lld)", M, K);
   Bf16Args g{};
   g.x = d->x; g.wt = wt; g.y = d->y; g.scale = d->scale; g.shift = d->shift; g.addend = d->addend;
@@ -370,10 +221,6 @@ extern "C" int radnet_conv_fwd_bf16_split(radnet_ctx* ctx, const radnet_conv_des
   g.x_bytes = (unsigned)x_bytes; g.w_bytes = (unsigned)w_bytes; g.y_bytes = (unsigned)y_bytes; g.add_bytes = (unsigned)add_bytes;
   if (ksplit > 64 || ksplit > g.nkt)
     RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_fwd_bf16: K split %d (at most 64 and the %d K tiles)", ksplit, g.nkt);
-  g.ksplit = ksplit > 1 ? ksplit : 1;
-  long long tiles = 0;
-  const int shape = radnet_bf16_tile_shape(M, d->n, &tiles);
-  if (shape == 0) return launch_bf16<128, 128>(ctx, g);
-  if (shape == 1) return launch_bf16<128, 64>(ctx, g);
-  return launch_bf16<64, 64>(ctx, g);
+  g.split = ksplit > 1 ? ksplit : 1;
+  return bf16_launch_by_shape<FwdLaunch>(ctx, g, M, d->n, 2.0 * g.M * (double)g.N * g.K);
 }

@@ -4,9 +4,8 @@
 // With g[m][n] = dy[m][n] * gscale[n] as ONE fp32 multiply (g = dy without gscale) and bf16() = round to nearest, ties to even:
 //   dgrad  dx[p][c] = mask( (sum_{ky,kx,n} bf16(g)[q(p,ky,kx)][n] * bf16(w)[(ky,kx,c)][n]) + dx_add[p][c] )      stride 1
 //   wgrad  dw[k][n] (+)= sum_m bf16(im2col(x))[m][k] * bf16(g)[m][n]
-// Both are ONE kernel template: an output tile of rows x cols, a reduction in 32-deep tiles, conv_bf16.hip's 2x2 waves, its two
-// LDS buffers of [row][32 + 8] bf16 and its ordered in-launch split of the reduction.  They differ in what a row, a column and
-// the reduction are, i.e. in the gather and the epilogue:
+// Both are ONE kernel template on conv_bf16_body.h's tile, LDS layout, reduction loop and ordered split (the forward's slabs and
+// counters).  They differ in what a row, a column and the reduction are, i.e. in the gather and the epilogue:
 //   * dgrad: rows = input pixels p, columns = input channels c, reduction = (tap, n), n innermost.  The A tile is gathered from
 //     dy like the forward gathers x (8 consecutive n of one tap as two 16-byte buffer loads, out-of-range offset for taps that
 //     fall off the output grid, ragged rows and the reduction's padding), multiplied by gscale and rounded on its way to LDS.
@@ -19,23 +18,10 @@
 //     fragments are then the same 16-byte row reads as everywhere else.  Lanes of a wave hold 32 consecutive m of two channel
 //     groups, so the eight stores of a wave spread over 32 banks.  im2col (3x3 padding, stride 2) is the forward's
 //     out-of-range-offset gather with the tap fixed per thread and the pixel moving.
-//   * Split of the reduction (blockIdx.z): conv_bf16.hip's protocol -- sc1 slabs in the context workspace, one arrival counter per
-//     output tile in the aux block (the forward's counters: launches of one context are ordered), the last arrival sums ALL slabs
-//     in slice order and leaves the counter at zero.  No float atomics.
-#include "radnet_internal.h"
-#include <hip/hip_ext.h>
+#include "conv_bf16_body.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int BK = 32;          // reduction depth per LDS tile (two MFMA steps of 16)
-constexpr int LDSROW = BK + 8;  // bf16 per LDS row: 80 bytes
-constexpr int NTHREADS = 256;
-constexpr unsigned kOOB = 0x80000000u;   // every descriptor covers < 2 GiB (checked by the launchers)
 constexpr int MODE_DGRAD = 0, MODE_WGRAD = 1;
 
 struct BwdArgs {
@@ -58,39 +44,6 @@ struct BwdArgs {
   unsigned long long magic_hw, magic_w, magic_ohow, magic_ow, magic_c, magic_kw, magic_n8;
   unsigned x_bytes, dy_bytes, w_bytes, out_bytes, add_bytes, mask_bytes;
 };
-
-__device__ __forceinline__ int div_magic(int m, unsigned long long magic) {
-  return (int)(((unsigned long long)(unsigned)m * magic) >> 40);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ u32x4 buf_load4u(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-}
-__device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
-}
-// sc1 (aux 16): write-through store / L1-bypassing agent-coherent load, for the slabs handed to the last slice in-launch
-__device__ __forceinline__ f32x4 buf_load4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 16));
-}
-__device__ __forceinline__ void buf_store4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off, const f32x4& v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, 16);
-}
-
-// fp32 -> bf16, round to nearest, ties to even (v_cvt_pk_bf16_f32 on gfx950)
-__device__ __forceinline__ uint16_t to_bf16_bits(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
-__device__ __forceinline__ u32x4 pack8_bf16(const f32x4& lo, const f32x4& hi) {
-  const bf16x8 b = {(__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w, (__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w};
-  return __builtin_bit_cast(u32x4, b);
-}
 
 // ---- dgrad images of the weights -------------------------------------------------------------------------------------------
 struct DgradImage {
@@ -121,9 +74,8 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_bwd_kernel(BwdArgs g) {
   __shared__ __attribute__((aligned(16))) uint16_t sa[2][BM * LDSROW];
   __shared__ __attribute__((aligned(16))) uint16_t sb[2][BN * LDSROW];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, hi = lane >> 5;
+  const int tid = threadIdx.x;
+  const Bf16Lane ln = bf16_lane();
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(g.x, g.x_bytes);
   const __amdgpu_buffer_rsrc_t rdy = make_rsrc(g.dy, g.dy_bytes);
@@ -265,87 +217,10 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_bwd_kernel(BwdArgs g) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // reduction tiles [t0, t1) of this slice (split <= nrt: none is empty)
-  const int t0 = SPLIT ? (int)(((long long)g.nrt * blockIdx.z) / g.split) : 0;
-  const int t1 = SPLIT ? (int)(((long long)g.nrt * (blockIdx.z + 1)) / g.split) : g.nrt;
-  gload(t0);
-  lstore(0);
-  __syncthreads();
-  for (int t = t0; t < t1; ++t) {
-    const int cur = (t - t0) & 1;
-    gload(t + 1 < t1 ? t + 1 : t);                   // the last iteration re-loads its own tile (never stored): no branch
-#pragma unroll
-    for (int s = 0; s < BK / 16; ++s) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        af[i] = *reinterpret_cast<const bf16x8*>(&sa[cur][(wm * (BM / 2) + i * 32 + l31) * LDSROW + 16 * s + 8 * hi]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        bfr[j] = *reinterpret_cast<const bf16x8*>(&sb[cur][(wn * (BN / 2) + j * 32 + l31) * LDSROW + 16 * s + 8 * hi]);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    lstore(cur ^ 1);
-    __syncthreads();
-  }
-
+  const int2 tr = SPLIT ? bf16_slice_tiles(g.nrt, g.split, blockIdx.z) : make_int2(0, g.nrt);
+  bf16_gemm_tiles<BM, BN>(sa, sb, tr.x, tr.y, gload, lstore, ln, acc);
   if constexpr (SPLIT) {
-    // slab layout private to this kernel: the 16 registers of a lane's 32x32 accumulator contiguous (four 16-byte accesses)
-    __shared__ int s_last;
-    const unsigned tile_id = blockIdx.x + gridDim.x * blockIdx.y;
-    const unsigned lane_off = (unsigned)((wave * TM * TN * 64 + lane) * 16) * 4u;
-    const __amdgpu_buffer_rsrc_t rslab = make_rsrc(g.partial + ((size_t)tile_id * g.split + blockIdx.z) * (BM * BN), BM * BN * 4u);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-          buf_store4_sc1(rslab, lane_off + (unsigned)(((i * TN + j) * 64 * 16 + q * 4) * 4), v);
-        }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned ticket = __hip_atomic_fetch_add(g.counters + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = ticket == (unsigned)(g.split - 1);
-      if (last) __hip_atomic_store(g.counters + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-      s_last = last;
-    }
-    __syncthreads();
-    if (s_last == 0) return;                         // uniform for the workgroup
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // compiler-only: keeps the slab loads below the ticket
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    for (int s = 0; s < g.split; ++s) {              // slices ADDED in slice order
-      const __amdgpu_buffer_rsrc_t rs = make_rsrc(g.partial + ((size_t)tile_id * g.split + s) * (BM * BN), BM * BN * 4u);
-      f32x4 v[TM * TN * 4];
-#pragma unroll
-      for (int t = 0; t < TM * TN * 4; ++t) v[t] = buf_load4_sc1(rs, lane_off + (unsigned)(((t >> 2) * 64 * 16 + (t & 3) * 4) * 4));
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 w = v[(i * TN + j) * 4 + q];
-            acc[i][j][4 * q] += w.x; acc[i][j][4 * q + 1] += w.y; acc[i][j][4 * q + 2] += w.z; acc[i][j][4 * q + 3] += w.w;
-          }
-    }
+    if (!bf16_ordered_split<BM, BN>(g.partial, g.counters, g.split, acc)) return;
   }
 
   // epilogue: D[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -356,11 +231,11 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_bwd_kernel(BwdArgs g) {
   const bool has_mask = (MODE == MODE_DGRAD) && g.mask != nullptr;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * (BN / 2) + j * 32 + l31;
+    const int n = n0 + ln.wn * (BN / 2) + j * 32 + ln.l31;
     const bool nv = n < g.cols;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      const int mb = m0 + wm * (BM / 2) + i * 32 + 4 * hi;
+      const int mb = m0 + ln.wm * (BM / 2) + i * 32 + 4 * ln.hi;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = mb + (r & 3) + 8 * (r >> 2);
@@ -377,36 +252,15 @@ __global__ void __launch_bounds__(NTHREADS) conv_bf16_bwd_kernel(BwdArgs g) {
   }
 }
 
-template <int BM, int BN, int MODE>
-int launch_bwd(radnet_ctx* ctx, BwdArgs g, double flops) {
-  const char* what = MODE == MODE_DGRAD ? "conv_dgrad_bf16" : "conv_wgrad_bf16";
-  const dim3 grid0(radnet_cdiv(g.rows, BM), radnet_cdiv(g.cols, BN), 1);
-  const unsigned long long tiles = (unsigned long long)grid0.x * grid0.y;
-  // by rule, never by timing: halve the split until its counters and slabs fit the context (one pass needs neither)
-  while (g.split > 1 && (tiles > kAuxBf16SplitCounterCount || !ctx->ws || tiles * (unsigned long long)g.split * BM * BN * 4ull > ctx->ws_bytes)) g.split /= 2;
-  if (g.split > 1) {
-    g.partial = (float*)ctx->ws;
-    g.counters = reinterpret_cast<unsigned*>(ctx->aux + kAuxBf16SplitCounters);
-  }
-  const dim3 grid(grid0.x, grid0.y, g.split > 1 ? g.split : 1);
-  const bool timed = ctx->timing != 0;
-  if (timed) radnet_timing_arm(ctx);
-  auto kernel = g.split > 1 ? conv_bf16_bwd_kernel<BM, BN, MODE, true> : conv_bf16_bwd_kernel<BM, BN, MODE, false>;
-  if (ctx->arm0) hipExtLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, ctx->arm0, ctx->arm1, 0, g);
-  else hipLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, ctx->stream, g);
-  RADNET_CHECK_LAUNCH(ctx, what);
-  if (timed) radnet_timing_end_armed(ctx, MODE == MODE_DGRAD ? 1 : 2, flops);
-  return RADNET_OK;
-}
-
 template <int MODE>
-int launch_by_shape(radnet_ctx* ctx, const BwdArgs& g, double flops) {
-  long long tiles = 0;
-  const int shape = radnet_bf16_tile_shape(g.rows, g.cols, &tiles);      // conv_bf16.hip: the forward's fixed rule on (rows, cols)
-  if (shape == 0) return launch_bwd<128, 128, MODE>(ctx, g, flops);
-  if (shape == 1) return launch_bwd<128, 64, MODE>(ctx, g, flops);
-  return launch_bwd<64, 64, MODE>(ctx, g, flops);
-}
+struct BwdLaunch {
+  static constexpr const char* what = MODE == MODE_DGRAD ? "conv_dgrad_bf16" : "conv_wgrad_bf16";
+  static constexpr const char* launch_name = what;
+  static constexpr bool halve_split = true;
+  static constexpr int timing_slot = MODE == MODE_DGRAD ? 1 : 2;
+  template <int BM, int BN, bool SPLIT>
+  static auto kernel() { return conv_bf16_bwd_kernel<BM, BN, MODE, SPLIT>; }
+};
 
 int cast_images(radnet_ctx* ctx, const DgradImages& L, int n_layers) {
   hipLaunchKernelGGL(weights_to_bf16_dgrad_kernel, dim3(512, (unsigned)n_layers), dim3(256), 0, ctx->stream, L);
@@ -459,14 +313,6 @@ extern "C" int32_t radnet_wgrad_bf16_pick_split(int64_t m, int32_t n, int32_t k)
   return radnet_conv_bf16_pick_split(k, n, (int32_t)std::min<int64_t>(m, 1 << 30));
 }
 
-static int check_geometry(radnet_ctx* ctx, const radnet_conv_desc* d, const char* what) {
-  if (d->nb <= 0 || d->h <= 0 || d->w_ <= 0 || d->oh <= 0 || d->ow <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->n <= 0 || d->c <= 0)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: bad geometry", what);
-  if ((d->oh - 1) * d->stride - d->pad_t >= d->h || (d->ow - 1) * d->stride - d->pad_l >= d->w_)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: output %dx%d inconsistent with input %dx%d", what, d->oh, d->ow, d->h, d->w_);
-  return RADNET_OK;
-}
-
 extern "C" int radnet_conv_dgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, const uint16_t* wd, int32_t ldkd) {
   return radnet_conv_dgrad_bf16_split(ctx, d, wd, ldkd, 1);
 }
@@ -475,7 +321,7 @@ extern "C" int radnet_conv_dgrad_bf16_split(radnet_ctx* ctx, const radnet_conv_d
   if (!ctx || !d) return RADNET_ERR_ARG;
   if (!d->dy || !wd || !d->dx) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_dgrad_bf16: null tensor");
   if (d->stride != 1) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_dgrad_bf16: stride %d (stride 1 only, as radnet_conv_dgrad)", d->stride);
-  if (int rc = check_geometry(ctx, d, "conv_dgrad_bf16")) return rc;
+  if (int rc = bf16_check_geometry(ctx, d, "conv_dgrad_bf16")) return rc;
   const int n8 = (d->n + 7) / 8 * 8;
   if (d->n % 4 != 0 || d->ld_dy % 4 != 0 || d->ld_dy < n8)
     RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_dgrad_bf16: n=%d ld_dy=%d (n and ld_dy multiples of 4, ld_dy >= n rounded up to 8)", d->n, d->ld_dy);
@@ -488,8 +334,7 @@ extern "C" int radnet_conv_dgrad_bf16_split(radnet_ctx* ctx, const radnet_conv_d
   const long long P = (long long)d->nb * d->h * d->w_, M = (long long)d->nb * d->oh * d->ow;
   const long long dy_bytes = M * d->ld_dy * 4, w_bytes = (long long)d->c * ldkd * 2, out_bytes = ((P - 1) * d->ld_dx + d->c) * 4;
   const long long add_bytes = d->dx_add ? ((P - 1) * d->ld_dx_add + d->c) * 4 : 0, mask_bytes = d->dx_mask ? ((P - 1) * d->ld_dx_mask + d->c) * 4 : 0;
-  const long long lim = 1ll << 31;
-  if (dy_bytes >= lim || w_bytes >= lim || out_bytes >= lim || add_bytes >= lim || mask_bytes >= lim || P >= (1 << 20) || M >= (1 << 20) || kdp >= (1 << 20))
+  if (bf16_too_large({dy_bytes, w_bytes, out_bytes, add_bytes, mask_bytes}, {P, M, kdp}))
     RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_dgrad_bf16: problem too large (P=%lld kd=%lld)", P, kd);
   BwdArgs g{};
   g.dy = d->dy; g.gscale = d->gscale; g.wd = wd; g.out = d->dx; g.add = d->dx_add; g.mask = d->dx_mask;
@@ -503,13 +348,13 @@ extern "C" int radnet_conv_dgrad_bf16_split(radnet_ctx* ctx, const radnet_conv_d
   g.mask_bytes = (unsigned)mask_bytes;
   if (ksplit > 64 || ksplit > g.nrt) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_dgrad_bf16: split %d (at most 64 and the %d reduction tiles)", ksplit, g.nrt);
   g.split = ksplit > 1 ? ksplit : 1;
-  return launch_by_shape<MODE_DGRAD>(ctx, g, 2.0 * P * (double)d->c * d->kh * d->kw * d->n);
+  return bf16_launch_by_shape<BwdLaunch<MODE_DGRAD>>(ctx, g, g.rows, g.cols, 2.0 * P * (double)d->c * d->kh * d->kw * d->n);
 }
 
 extern "C" int radnet_conv_wgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, int32_t msplit) {
   if (!ctx || !d) return RADNET_ERR_ARG;
   if (!d->x || !d->dy || !d->dw) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_bf16: null tensor");
-  if (int rc = check_geometry(ctx, d, "conv_wgrad_bf16")) return rc;
+  if (int rc = bf16_check_geometry(ctx, d, "conv_wgrad_bf16")) return rc;
   if (d->c % 8 != 0 || d->n % 8 != 0 || d->ld_dy % 4 != 0)
     RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_bf16: c=%d n=%d ld_dy=%d (channel counts multiples of 8, ld_dy of 4)", d->c, d->n, d->ld_dy);
   if (((uintptr_t)d->x & 15) || ((uintptr_t)d->dy & 15) || (d->gscale && ((uintptr_t)d->gscale & 15)))
@@ -518,8 +363,7 @@ extern "C" int radnet_conv_wgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d
     RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_bf16: ldw=%d ld_dy=%d dw_accumulate=%d for %d columns", d->ldw, d->ld_dy, d->dw_accumulate, d->n);
   const long long M = (long long)d->nb * d->oh * d->ow, K = (long long)d->kh * d->kw * d->c;
   const long long x_bytes = (long long)d->nb * d->h * d->w_ * d->c * 4, dy_bytes = ((M - 1) * d->ld_dy + d->n) * 4, out_bytes = ((K - 1) * d->ldw + d->n) * 4;
-  const long long lim = 1ll << 31;
-  if (x_bytes >= lim || dy_bytes >= lim || out_bytes >= lim || M >= (1 << 20) || K >= (1 << 20))
+  if (bf16_too_large({x_bytes, dy_bytes, out_bytes}, {M, K}))
     RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_bf16: problem too large (M=%lld K=%lld)", M, K);
   BwdArgs g{};
   g.x = d->x; g.dy = d->dy; g.gscale = d->gscale; g.out = d->dw;
@@ -533,7 +377,7 @@ extern "C" int radnet_conv_wgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d
   g.x_bytes = (unsigned)x_bytes; g.dy_bytes = (unsigned)dy_bytes; g.out_bytes = (unsigned)out_bytes; g.add_bytes = (unsigned)out_bytes;
   if (msplit > 64 || msplit > g.nrt) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_bf16: split %d (at most 64 and the %d reduction tiles)", msplit, g.nrt);
   g.split = msplit > 1 ? msplit : 1;
-  int rc = launch_by_shape<MODE_WGRAD>(ctx, g, 2.0 * M * (double)d->n * K);
+  int rc = bf16_launch_by_shape<BwdLaunch<MODE_WGRAD>>(ctx, g, g.rows, g.cols, 2.0 * M * (double)d->n * K);
   // bias gradient: the exact fp32 column sum of the UNROUNDED dy * gscale, added in index order
   if (rc == RADNET_OK && d->db) rc = radnet_colsum(ctx, d->dy, (int32_t)M, d->n, d->ld_dy, d->gscale, d->db, d->dw_accumulate != 0 ? 1 : 0);
   return rc;

@@ -116,8 +116,8 @@ constexpr size_t kAuxLossBlocks = 1024;
 constexpr size_t kAuxColsumScratch = kAuxLossPartials + kAuxLossBlocks * 4 * 8;           // kAuxColsumRows x 65536 floats
 constexpr size_t kAuxColsumRows = 32;
 constexpr size_t kAuxColsumCols = 65536;
-constexpr size_t kAuxBf16SplitCounters = kAuxColsumScratch + kAuxColsumRows * kAuxColsumCols * 4;   // 8192 x u32: one per output tile of a
-constexpr size_t kAuxBf16SplitCounterCount = 8192;                                                  // K-split bf16 forward launch
+constexpr size_t kAuxBf16SplitCounters = kAuxColsumScratch + kAuxColsumRows * kAuxColsumCols * 4;   // 8192 x u32: one per output tile of a split
+constexpr size_t kAuxBf16SplitCounterCount = 8192;                                                  // bf16 launch: forward, dgrad and wgrad (conv_bf16_body.h)
 constexpr size_t kAuxBytes = kAuxBf16SplitCounters + kAuxBf16SplitCounterCount * 4;
 
 #define RADNET_CHECK_HIP(ctx, expr)                                                              \
