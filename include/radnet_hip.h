@@ -499,10 +499,49 @@ int radnet_aug_pointwise_u8(radnet_ctx* ctx, const uint8_t* src, uint8_t* dst, i
  * to refuse (png.py checks the column on the host); the kernel treats it as None.  One workgroup walks the pass in bands of
  * RADNET_PNG_UNFILTER_BAND_ROWS rows, one lane per row, each row one pixel behind the row above, and moves row data between global
  * memory and LDS in chunks of RADNET_PNG_UNFILTER_CHUNK_BYTES per row: the seams tests/test_gpu_png.py straddles.  Nothing waits
- * on another workgroup; the loop bounds depend on (rows, rowbytes, bpp) alone. */
+ * on another workgroup; the loop bounds depend on (rows, rowbytes, bpp) alone.  One workgroup is one CU: for whole files, and for
+ * many at once, radnet_png_unfilter_segments_u8 below spreads the same walk over the device. */
 #define RADNET_PNG_UNFILTER_BAND_ROWS 512
 #define RADNET_PNG_UNFILTER_CHUNK_BYTES 96
 int radnet_png_unfilter_u8(radnet_ctx* ctx, uint8_t* stream, int32_t rows, int32_t rowbytes, int32_t bpp);
+/* ---- many passes in one launch: segments ----
+ * The only bytes a scanline takes from the row above are its b and c, and filter types 0 (None) and 1 (Sub) use neither.  So a row
+ * of type 0 or 1 reconstructs to the same bytes whatever stands above it, and the rows from it up to the next such row form a run
+ * that can be reconstructed on its own, the row above its first row counting as zeros, exactly as above row 0 of a pass.  A segment
+ * is one or more adjacent runs of one pass.  A file whose rows are all Up / Average / Paeth has one segment per pass. */
+typedef struct radnet_png_segment {
+  int64_t offset;   /* of the filter-type byte of the segment's first scanline in the uploaded buffer */
+  int32_t rows;     /* scanlines in the segment */
+  int32_t rowbytes; /* of its pass: a scanline is 1 + rowbytes bytes */
+} radnet_png_segment;
+/* the planner's default target_rows: the reconstruction runs one lane per row, so 64 rows fill one wave */
+#define RADNET_PNG_SEGMENT_TARGET_ROWS 64
+/* Host only (csrc/png_plan.cpp; no context, no device, like radnet_chain_check): cuts one pass into segments.  `stream` points at
+ * the pass's first scanline in HOST memory (rows x (1 + rowbytes) bytes, of which only the filter-type bytes are read);
+ * stream_offset is where that byte will stand in the uploaded buffer, so out[0].offset == stream_offset and a segment that starts at
+ * row r has offset stream_offset + r * (1 + rowbytes).  A legal cut is in front of row 0 or of a row of type 0 or 1.  Greedy: a
+ * segment ends at the last legal cut that keeps it within target_rows rows (0 = RADNET_PNG_SEGMENT_TARGET_ROWS), at the end of the
+ * pass if that is within target_rows, else at the next legal cut (or the end of the pass).  The segments tile the pass in row
+ * order.  If that makes more than cap segments, adjacent ones are merged, evenly by count, into exactly cap: never an error.
+ * Returns the number of segments written, or RADNET_ERR_ARG for a null pointer, rows / rowbytes / cap < 1, a negative
+ * stream_offset or target_rows, or a filter-type byte above 4 (nothing is written then). */
+int radnet_png_plan_segments(const uint8_t* stream, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
+                             radnet_png_segment* out, int32_t cap);
+/* radnet_png_unfilter_u8 on `count` segments of the buffer base[0 .. base_len) (device), which may come from any passes of any
+ * images that share bpp: the same bytes as one radnet_png_unfilter_u8 per pass when every segment starts at a legal cut (the
+ * caller's to ensure, with the planner; the filter-type bytes above 4 likewise).  segs_host and segs_dev hold the SAME table, on the
+ * host and on the device; the caller uploads it (png.py: behind the streams in the one staging buffer, as the palette) and this
+ * entry copies nothing.  The host table is validated before anything is launched: rows > 0, rowbytes > 0, rowbytes % bpp == 0,
+ * offset >= 0, offset + rows * (1 + rowbytes) <= base_len; a violation is RADNET_ERR_ARG naming the segment's index and nothing
+ * is modified.  Segments must not overlap (not checked; overlapping ones race on bytes inside the buffer).  count == 0 is
+ * RADNET_OK without a launch, whatever the pointers.
+ * The table may be in any order.  At most two launches, one workgroup per table entry, nothing waits on another workgroup:
+ * segments of at most 64 rows run as one wave with a 6.5 KB LDS tile (many per CU), longer ones as the band-sized workgroup of
+ * radnet_png_unfilter_u8.  Each launch spans the index range from the first to the last entry of its kind and a workgroup that
+ * finds an entry of the other kind returns at once, so a table with the short segments first and the long ones last starts no
+ * idle workgroup. */
+int radnet_png_unfilter_segments_u8(radnet_ctx* ctx, uint8_t* base, int64_t base_len, const radnet_png_segment* segs_host,
+                                    const radnet_png_segment* segs_dev, int32_t count, int32_t bpp);
 /* Expansion of one reconstructed pass: pixel (r, c) of the pass_h x pass_w pass goes to dst[y0 + r * dy][x0 + c * dx] (a
  * non-interlaced image: y0 = x0 = 0, dy = dx = 1; Adam7: the pass's origin and spacing).  colour types 0 (grey; depth 1, 2, 4, 8, 16),
  * 2 (RGB; 8, 16), 3 (palette; 1, 2, 4, 8), 4 (grey + alpha; 8, 16), 6 (RGBA; 8, 16).  Sub-byte samples unpack MSB first; grey is

@@ -10,7 +10,9 @@
 // (lane offset w * (63 + T) + l pixels, T = pixels per chunk): the row above a wave's first row is complete, in global memory,
 // one chunk behind, and is staged beside the wave's own 64 row segments.  Row data moves between global memory and LDS in
 // chunks of RADNET_PNG_UNFILTER_CHUNK_BYTES per row, consecutive lanes on consecutive bytes.  Every loop bound is a function of
-// (rows, rowbytes, bpp); workgroups never wait for each other (there is one).
+// (rows, rowbytes, bpp); workgroups never wait for each other: radnet_png_unfilter_u8 launches one, and
+// radnet_png_unfilter_segments_u8 one per segment, where a segment (csrc/png_plan.cpp) is a run of rows whose first row does not
+// read the row above it (row 0 of a pass, or filter type 0 / 1), so no segment reads a byte another one writes.
 #include "radnet_internal.h"
 
 namespace {
@@ -37,18 +39,20 @@ __device__ __forceinline__ int predictor(int ft, int a, int b, int c) {
   return p;
 }
 
-template <int BPP>
-__global__ void __launch_bounds__(kWaves * 64) png_unfilter_kernel(uint8_t* stream, int rows, int rowbytes) {
+// The walk of one independent run of scanlines: `rows` rows of 1 + rowbytes bytes at `stream`, the row above row 0 counting as
+// zeros.  A whole pass is such a run, and so is a segment of one that starts on a row of filter type 0 or 1 (png_plan.cpp).
+// WAVES waves of one workgroup, lds[WAVES][65][kLdsStride]; every thread of the workgroup calls it with the same arguments.
+template <int BPP, int WAVES>
+__device__ __forceinline__ void unfilter_rows(uint8_t (*lds)[65][kLdsStride], uint8_t* stream, int rows, int rowbytes) {
   constexpr int T = kChunk / BPP;                  // pixels per chunk
   constexpr int kWaveLag = 63 + T;                 // pixels wave w lags wave w - 1
-  __shared__ uint8_t lds[kWaves][65][kLdsStride];  // per wave: 64 row segments, then the segment of the row above lane 0
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long pitch = 1 + (long long)rowbytes;
   const int P = rowbytes / BPP;
-  const int waves_used = min(kWaves, (rows + 63) / 64);
+  const int waves_used = min(WAVES, (rows + 63) / 64);
   const int n_iter = (P + (waves_used - 1) * kWaveLag + 63 + T - 1) / T;      // until the last lane of the last wave is through
 
-  for (int band = 0; band < rows; band += kWaves * 64) {
+  for (int band = 0; band < rows; band += WAVES * 64) {
     const int wave_r0 = band + w * 64;
     const int r = wave_r0 + lane;
     const bool valid = r < rows;
@@ -114,6 +118,23 @@ __global__ void __launch_bounds__(kWaves * 64) png_unfilter_kernel(uint8_t* stre
       __syncthreads();                             // the next chunk of the wave below reads these rows from global memory
     }
   }
+}
+
+template <int BPP>
+__global__ void __launch_bounds__(kWaves * 64) png_unfilter_kernel(uint8_t* stream, int rows, int rowbytes) {
+  __shared__ uint8_t lds[kWaves][65][kLdsStride];  // per wave: 64 row segments, then the segment of the row above lane 0
+  unfilter_rows<BPP, kWaves>(lds, stream, rows, rowbytes);
+}
+
+// One workgroup per table entry first + blockIdx.x: WAVES == 1 takes the segments of at most 64 rows (one wave, a 6.5 KB tile, so
+// many workgroups share a CU), WAVES == kWaves the longer ones; an entry of the other kind is left to the other launch.  The
+// branch is uniform over the workgroup, so every thread that enters unfilter_rows reaches its barriers.
+template <int BPP, int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) png_unfilter_segments_kernel(uint8_t* base, const radnet_png_segment* __restrict__ segs, int first) {
+  __shared__ uint8_t lds[WAVES][65][kLdsStride];
+  const radnet_png_segment seg = segs[first + (int)blockIdx.x];
+  if ((seg.rows <= 64) != (WAVES == 1)) return;
+  unfilter_rows<BPP, WAVES>(lds, base + seg.offset, seg.rows, seg.rowbytes);
 }
 
 // ---- expansion to BGR ----------------------------------------------------------------------------------------------------------
@@ -188,6 +209,59 @@ extern "C" int radnet_png_unfilter_u8(radnet_ctx* ctx, uint8_t* stream, int32_t 
     default: hipLaunchKernelGGL(png_unfilter_kernel<8>, grid, block, 0, ctx->stream, stream, rows, rowbytes); break;
   }
   RADNET_CHECK_LAUNCH(ctx, "png_unfilter_u8");
+  return RADNET_OK;
+}
+
+namespace {
+
+template <int WAVES>
+void launch_segments(radnet_ctx* ctx, uint8_t* base, const radnet_png_segment* segs, int first, int n, int bpp) {
+  const dim3 grid((unsigned)n), block(WAVES * 64);
+  switch (bpp) {
+    case 1: hipLaunchKernelGGL((png_unfilter_segments_kernel<1, WAVES>), grid, block, 0, ctx->stream, base, segs, first); break;
+    case 2: hipLaunchKernelGGL((png_unfilter_segments_kernel<2, WAVES>), grid, block, 0, ctx->stream, base, segs, first); break;
+    case 3: hipLaunchKernelGGL((png_unfilter_segments_kernel<3, WAVES>), grid, block, 0, ctx->stream, base, segs, first); break;
+    case 4: hipLaunchKernelGGL((png_unfilter_segments_kernel<4, WAVES>), grid, block, 0, ctx->stream, base, segs, first); break;
+    case 6: hipLaunchKernelGGL((png_unfilter_segments_kernel<6, WAVES>), grid, block, 0, ctx->stream, base, segs, first); break;
+    default: hipLaunchKernelGGL((png_unfilter_segments_kernel<8, WAVES>), grid, block, 0, ctx->stream, base, segs, first); break;
+  }
+}
+
+}  // namespace
+
+extern "C" int radnet_png_unfilter_segments_u8(radnet_ctx* ctx, uint8_t* base, int64_t base_len, const radnet_png_segment* segs_host,
+                                               const radnet_png_segment* segs_dev, int32_t count, int32_t bpp) {
+  if (!ctx) return RADNET_ERR_ARG;
+  if (count < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_unfilter_segments: %d segments", count);
+  if (count == 0) return RADNET_OK;
+  if (!base || !segs_host || !segs_dev || base_len <= 0)
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_unfilter_segments: null buffer or table (base %p of %lld bytes, host table %p, device table %p)", (void*)base,
+                (long long)base_len, (const void*)segs_host, (const void*)segs_dev);
+  if (!(bpp == 1 || bpp == 2 || bpp == 3 || bpp == 4 || bpp == 6 || bpp == 8))
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_unfilter_segments: %d bytes per pixel", bpp);
+  // the index range each launch has to span: [lo, hi) of the segments of at most 64 rows and of the longer ones
+  int lo[2] = {count, count}, hi[2] = {0, 0};
+  for (int i = 0; i < count; ++i) {
+    const radnet_png_segment& s = segs_host[i];
+    if (s.rows <= 0 || s.rowbytes <= 0 || s.rowbytes % bpp != 0)
+      RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_unfilter_segments: segment %d has %d rows of %d bytes at %d bytes per pixel", i, s.rows, s.rowbytes, bpp);
+    if (s.rowbytes > (1 << 30)) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "png_unfilter_segments: segment %d has %d bytes per row", i, s.rowbytes);
+    const int64_t bytes = (int64_t)s.rows * (1 + (int64_t)s.rowbytes);       // below 2^62
+    if (s.offset < 0 || s.offset > base_len || bytes > base_len - s.offset)
+      RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_unfilter_segments: segment %d (%lld bytes at offset %lld) leaves the buffer of %lld bytes", i, (long long)bytes,
+                  (long long)s.offset, (long long)base_len);
+    const int k = s.rows <= 64 ? 0 : 1;
+    lo[k] = i < lo[k] ? i : lo[k];
+    hi[k] = i + 1;
+  }
+  if (hi[0] > lo[0]) {
+    launch_segments<1>(ctx, base, segs_dev, lo[0], hi[0] - lo[0], bpp);
+    RADNET_CHECK_LAUNCH(ctx, "png_unfilter_segments_u8 (one-wave segments)");
+  }
+  if (hi[1] > lo[1]) {
+    launch_segments<kWaves>(ctx, base, segs_dev, lo[1], hi[1] - lo[1], bpp);
+    RADNET_CHECK_LAUNCH(ctx, "png_unfilter_segments_u8 (band-sized segments)");
+  }
   return RADNET_OK;
 }
 

@@ -1,0 +1,45 @@
+// ---- host side of the segmented PNG reconstruction (png.hip): one pass -> independent segments ---------------------------
+// No device call and no HIP header: compiled by g++, runs without a GPU (contract: include/radnet_hip.h).
+#include "radnet_hip.h"
+
+namespace {
+
+struct Column {
+  const uint8_t* stream;
+  int64_t pitch;
+  int32_t rows, target;
+  bool legal(int64_t r) const { return stream[r * pitch] <= 1; }      // None and Sub do not read the row above
+  // the end (one past the last row) of the greedy segment that starts at row s
+  int64_t end_of(int64_t s) const {
+    const int64_t limit = s + target;
+    if (limit >= rows) return rows;
+    for (int64_t c = limit; c > s; --c)
+      if (legal(c)) return c;
+    for (int64_t c = limit + 1; c < rows; ++c)
+      if (legal(c)) return c;
+    return rows;
+  }
+};
+
+}  // namespace
+
+extern "C" int radnet_png_plan_segments(const uint8_t* stream, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
+                                        radnet_png_segment* out, int32_t cap) {
+  if (!stream || !out || rows <= 0 || rowbytes <= 0 || cap <= 0 || stream_offset < 0 || target_rows < 0) return RADNET_ERR_ARG;
+  const Column col{stream, 1 + (int64_t)rowbytes, rows, target_rows ? target_rows : RADNET_PNG_SEGMENT_TARGET_ROWS};
+  for (int64_t r = 0; r < rows; ++r)
+    if (stream[r * col.pitch] > 4) return RADNET_ERR_ARG;
+  int64_t n = 0;
+  for (int64_t s = 0; s < rows; s = col.end_of(s)) ++n;
+  // greedy segment i goes to out[i], or with more than cap of them to out[i * cap / n]: every entry gets one at least
+  const bool merge = n > cap;
+  int64_t i = 0, last = -1;
+  for (int64_t s = 0; s < rows; ++i) {
+    const int64_t e = col.end_of(s), slot = merge ? i * cap / n : i;
+    if (slot != last) out[slot] = radnet_png_segment{stream_offset + s * col.pitch, 0, rowbytes};
+    out[slot].rows += (int32_t)(e - s);
+    last = slot;
+    s = e;
+  }
+  return (int)(last + 1);
+}

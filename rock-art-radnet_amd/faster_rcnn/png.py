@@ -8,6 +8,10 @@ geometry (one pass, or Adam7's up to seven) and the check that every filter-type
 Device (csrc/png.hip through the C ABI, include/radnet_hip.h): scanline reconstruction in place on the uploaded stream
 (radnet_png_unfilter_u8) and expansion to BGR (radnet_png_expand_bgr_u8), one launch of each per pass.  The file becomes a device
 image after one upload; nothing comes back unless the caller asks for a NumPy array.  There is no CPU reconstruction.
+Many files at once (decode_device_many): the files inflate on host threads (zlib releases the GIL), ONE upload carries every
+stream, every palette and a table of segments -- runs of scanlines that start on a row of filter type 0 or 1 and so do not read the
+row above them (radnet_png_plan_segments cuts each pass on the host) -- and one radnet_png_unfilter_segments_u8 per distinct bpp
+reconstructs all passes of all files, one workgroup per segment; the bytes are decode_device's.
 
 Formats: colour types 0, 2, 3, 4, 6 with the bit depths 1, 2, 4, 8, 16 the PNG specification allows for each; non-interlaced and
 Adam7.  Output rules: grey is replicated to three channels, depths 1 / 2 / 4 scaled by 255 / 85 / 17; palette entries are looked up
@@ -169,6 +173,100 @@ def decode_device(data, ctx=None):
             ctx.call("radnet_png_expand_bgr_u8", base + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, img.header.color_type, img.header.bit_depth,
                      base + n, out, img.header.height, img.header.width, p.y0, p.x0, p.dy, p.dx)
     return AD.hand_over(out, side)
+
+
+SEGMENT = np.dtype([("offset", np.int64), ("rows", np.int32), ("rowbytes", np.int32)])      # radnet_png_segment, 16 bytes
+MANY_DEFAULT_WORKERS, MANY_MAX_WORKERS = 8, 16      # host threads of decode_device_many; fixed, not read off the machine
+
+
+def _parse_indexed(item):
+    index, data = item
+    try:
+        return parse(data)
+    except ValueError as e:
+        raise ValueError("file %d: %s" % (index, e)) from e
+
+
+def plan_segments(img, base_offset=0, target_rows=0):
+    """The segment table of one parsed image whose stream will stand at base_offset of the uploaded buffer: a structured array
+    (offset int64, rows int32, rowbytes int32; radnet_png_segment) from radnet_png_plan_segments, pass after pass."""
+    import ctypes
+    from radnet_hip import lib as L
+    lib = L.load_library()
+    column = np.frombuffer(img.stream, np.uint8)
+    target = target_rows or L.header_constant("RADNET_PNG_SEGMENT_TARGET_ROWS")
+    tables = []
+    for p in img.passes:
+        cap = min(p.pass_h, 2 * (p.pass_h // target) + 2)      # two neighbours of the greedy rule together exceed target_rows
+        table = np.zeros(cap, SEGMENT)
+        n = lib.radnet_png_plan_segments(column.ctypes.data + p.stream_offset, base_offset + p.stream_offset, p.pass_h, p.rowbytes, target_rows,
+                                         table.ctypes.data_as(ctypes.c_void_p), cap)
+        if n < 0:
+            raise ValueError("PNG: radnet_png_plan_segments failed (%d) on the pass at (%d, %d)" % (n, p.x0, p.y0))
+        tables.append(table[:n])
+    return np.concatenate(tables)
+
+
+def decode_device_many(datas, ctx=None, workers=None):
+    """decode_device for a list of files in one pass: a list of uint8 [H][W][3] (B, G, R) cuda tensors, byte for byte what
+    [decode_device(d) for d in datas] returns.  The files are parsed (CRC, inflate) on `workers` host threads (default
+    min(len(datas), 8), at most 16); a file that fails raises its ValueError prefixed with "file <index>: " before any device
+    work.  Then ONE pinned staging buffer and ONE upload: the streams, the palettes, the segment table (8-byte aligned, short
+    segments first inside each bpp); one radnet_png_unfilter_segments_u8 per distinct bpp; one radnet_png_expand_bgr_u8 per pass.
+    ctx and the stream rules are decode_device's."""
+    import concurrent.futures
+    import torch
+    from . import augmentation_device as AD
+    datas = list(datas)
+    if not datas:
+        return []
+    workers = min(len(datas), MANY_DEFAULT_WORKERS) if workers is None else int(workers)
+    workers = max(1, min(workers, MANY_MAX_WORKERS))
+    pool = concurrent.futures.ThreadPoolExecutor(max_workers=workers)
+    try:
+        futures = [pool.submit(_parse_indexed, item) for item in enumerate(datas)]
+        try:
+            imgs = [f.result() for f in futures]                          # the first failure, in index order, is raised here
+        except BaseException:
+            pool.shutdown(wait=True, cancel_futures=True)                 # files not yet started are not inflated for nothing
+            raise
+        starts = np.concatenate([[0], np.cumsum([len(im.stream) for im in imgs])]).astype(np.int64)
+        n_streams = int(starts[-1])
+        tables = list(pool.map(lambda k: plan_segments(imgs[k], int(starts[k])), range(len(imgs))))
+        # one table: grouped by bpp, inside a group the segments of at most 64 rows first (the one-wave launch), then the long ones
+        bpps = np.concatenate([np.full(len(t), im.bpp, np.int64) for t, im in zip(tables, imgs)])
+        table = np.concatenate(tables)
+        order = np.lexsort((table["rows"] > 64, bpps))
+        table, bpps = table[order], bpps[order]
+        pal_at = n_streams
+        seg_at = (pal_at + 768 * len(imgs) + 7) & ~7
+        staged = torch.empty(seg_at + table.nbytes, dtype=torch.uint8, pin_memory=True)
+        host = staged.numpy()
+
+        def stage(k):
+            host[starts[k]:starts[k + 1]] = np.frombuffer(imgs[k].stream, np.uint8)
+            host[pal_at + 768 * k:pal_at + 768 * (k + 1)] = imgs[k].palette.reshape(-1)
+        list(pool.map(stage, range(len(imgs))))
+    finally:
+        pool.shutdown(wait=True)                                          # the host threads are done before any device work
+    host[pal_at + 768 * len(imgs):seg_at] = 0
+    host[seg_at:] = table.view(np.uint8)
+    with AD.feed_stream(ctx) as (ctx, side):
+        dev = staged.cuda(non_blocking=True)
+        base = dev.data_ptr()
+        first = 0
+        for bpp, n in zip(*np.unique(bpps, return_counts=True)):
+            ctx.call("radnet_png_unfilter_segments_u8", base, n_streams, host.ctypes.data + seg_at + 16 * first, base + seg_at + 16 * first,
+                     int(n), int(bpp))
+            first += int(n)
+        outs = []
+        for k, im in enumerate(imgs):
+            out = torch.empty((im.header.height, im.header.width, 3), dtype=torch.uint8, device="cuda")
+            for p in im.passes:
+                ctx.call("radnet_png_expand_bgr_u8", base + int(starts[k]) + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, im.header.color_type,
+                         im.header.bit_depth, base + pal_at + 768 * k, out, im.header.height, im.header.width, p.y0, p.x0, p.dy, p.dx)
+            outs.append(out)
+    return [AD.hand_over(out, side) for out in outs]
 
 
 def imdecode_color(data):

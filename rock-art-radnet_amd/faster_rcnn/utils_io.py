@@ -51,12 +51,17 @@ class DeviceImageLoader:
     from one image back to back and decodes the image for each (utils.py:390), so a cache of a few images removes most decodes.
     cache_bytes=0 disables it; an image larger than the bound is decoded and not kept.  hits / misses count the calls.  The cached
     tensors are handed out as they are: the feed reads them (tile gather) and never writes them.  The images can also be passed to
-    RADNet.predict directly: with the engine-backed models it cuts and resizes every tile on the device (RADNet.ImageWindow)."""
+    RADNet.predict directly: with the engine-backed models it cuts and resizes every tile on the device (RADNet.ImageWindow).
+    prefetch() fills the cache ahead of the calls, many files per decode (png.decode_device_many): the types of a scan, the next
+    images of a feed.  The cache holds one decoder's images: with decode= set and decode_many= not, prefetch decodes through
+    decode, file by file."""
 
-    def __init__(self, cache_bytes=1 << 30, decode=None):
+    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None):
         self.cache_bytes = int(cache_bytes)
         self.decode = decode                       # (file bytes as uint8 array) -> image; default: png.decode_device
-        self.hits = self.misses = 0
+        # (list of file bytes) -> list of images, for prefetch; default: png.decode_device_many, or `decode` on each file if that is set
+        self.decode_many = decode_many
+        self.hits = self.misses = self.prefetched = 0
         self.used = 0
         self._lru = collections.OrderedDict()      # key -> (image, bytes), least recently used first
 
@@ -64,10 +69,63 @@ class DeviceImageLoader:
     def _nbytes(img):
         return int(np.prod(img.shape))             # uint8
 
-    def __call__(self, img_data, img_type):
+    @staticmethod
+    def _key(img_data, img_type):
         path = image_path(img_data["filepath"], img_type)
         st = os.stat(path)
-        key = (path, img_type, st.st_size, st.st_mtime_ns)
+        return path, (path, img_type, st.st_size, st.st_mtime_ns)
+
+    def _insert(self, key, img):
+        size = self._nbytes(img)
+        if size <= self.cache_bytes:
+            self._lru[key] = (img, size)
+            self.used += size
+            while self.used > self.cache_bytes:
+                _, (_, freed) = self._lru.popitem(last=False)
+                self.used -= freed
+
+    def prefetch(self, pairs):
+        """Decodes the (img_data, img_type) pairs that are not in the cache, many files per decode_many call, and inserts them
+        under the LRU rules, so that the calls that follow are hits.  A pair that is cached already moves to the recent end, as a
+        call would move it.  A batch holds at most cache_bytes of decoded images (judged by the files' headers); a file that alone
+        exceeds the bound is left to __call__; pairs that together exceed cache_bytes evict the least recently used among them, as
+        calls in that order would.  hits / misses do not move.  Returns the number of images decoded (also added to `prefetched`)."""
+        if self.decode_many is not None:
+            decode_many = self.decode_many
+        elif self.decode is not None:
+            decode_many = lambda files: [self.decode(f) for f in files]      # noqa: E731  (one decoder fills the cache)
+        else:
+            decode_many = png.decode_device_many
+        todo, seen = [], set()
+        for img_data, img_type in pairs:
+            path, key = self._key(img_data, img_type)
+            if key in self._lru:
+                self._lru.move_to_end(key)
+                continue
+            if key in seen:
+                continue
+            header = png.read_header(path)
+            size = header.width * header.height * 3
+            if size <= self.cache_bytes:
+                seen.add(key)
+                todo.append((path, key, size))
+        done, batch, held = 0, [], 0
+        for item in todo + [None]:
+            if batch and (item is None or held + item[2] > self.cache_bytes):
+                files = [np.fromfile(path, np.uint8) for path, _, _ in batch]
+                imgs = decode_many(files)
+                for (_, key, _), img in zip(batch, imgs):
+                    self._insert(key, img)
+                done += len(batch)
+                batch, held = [], 0
+            if item is not None:
+                batch.append(item)
+                held += item[2]
+        self.prefetched += done
+        return done
+
+    def __call__(self, img_data, img_type):
+        path, key = self._key(img_data, img_type)
         hit = self._lru.get(key)
         if hit is not None:
             self._lru.move_to_end(key)
@@ -76,11 +134,5 @@ class DeviceImageLoader:
         self.misses += 1
         buf = np.fromfile(path, np.uint8)
         img = png.decode_device(buf) if self.decode is None else self.decode(buf)
-        size = self._nbytes(img)
-        if size <= self.cache_bytes:
-            self._lru[key] = (img, size)
-            self.used += size
-            while self.used > self.cache_bytes:
-                _, (_, freed) = self._lru.popitem(last=False)
-                self.used -= freed
+        self._insert(key, img)
         return img

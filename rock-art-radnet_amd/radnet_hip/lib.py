@@ -261,6 +261,8 @@ def load_library():
         "radnet_aug_histogram_u8": (C.c_int, [vp, vp, i32, i32, i32, vp]),
         "radnet_aug_pointwise_u8": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f64, f64, u64, C.c_uint32]),
         "radnet_png_unfilter_u8": (C.c_int, [vp, vp, i32, i32, i32]),
+        "radnet_png_plan_segments": (C.c_int, [vp, i64, i32, i32, i32, vp, i32]),
+        "radnet_png_unfilter_segments_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32]),
         "radnet_png_expand_bgr_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32]),
         "radnet_fill_zero": (C.c_int, [vp, vp, u64]),
         "radnet_copy_bytes": (C.c_int, [vp, vp, vp, C.c_uint64]),
