@@ -9,8 +9,13 @@
 // write, output transform 4x read + 1 write, filter transform once per weight update).  It pays where K = 9*C is large
 // against the activation size: rpn_conv1 (C = 1024) and the stage-5 3x3 convs (C = 512).
 // Arithmetic: the transforms are exact in the sense of using only additions and multiplications by 1/2 (B and A have
-// entries 0, +-1; G has 1/2); results differ from the direct sum by fp32 rounding (different association), well inside
-// the stated 1e-3 activation tolerance (tests compare against the oracle's direct convolution).
+// entries 0, +-1; G has 1/2); results differ from the direct sum by fp32 rounding (different association).  Stated and
+// tested per STAGE (tests/winograd_edge_cases.py, tests/test_gpu_winograd_edges.py): every element of every transform lies
+// within s * 2^-24 * (|L1| |x| |L2|^T * |scale|) + 2 * 2^-24 * (|shift| + |old|) of the float64 value of that one stage,
+// s counted from the association written here (F(2x2): 2 .. 7, F(4x4): 6 .. 11), and the integer-valued runs are exact.
+// Measured worst err / bound on one MI355X -- F(2x2): filter 0.33, input 0.89, output 0.41, dy 0.88, filter_grad 0.40;
+// F(4x4): filter 0.42, input 0.37, output 0.28, dy 0.34, filter_grad 0.38; the batched GEMMs 0.16 of their
+// (K + 8) * 2^-24 * sum|a*b|.  The composed result is also compared with the oracle's direct convolution (2e-4).
 #include "radnet_internal.h"
 #include "radnet_wino4.h"
 
@@ -427,7 +432,8 @@ __global__ void __launch_bounds__(256) wino4_filter_grad_kernel(const float* __r
 // on its own.  Here a unit's six patch columns (input) / six position columns (output) go to six WAVES of a 384-thread workgroup
 // (role = wave, unit = lane: every access of a wave is 64 consecutive channel quads = 1 KB): role r transforms column r along the
 // rows (6 loads), the 6x6 (6x4) intermediate crosses through LDS, role r then transforms ROW r along the columns and stores it --
-// 6 + 6 memory operations per thread, 4 times the workgroups.  Same operations in the same order as the kernels above: same bits.
+// 6 + 6 memory operations per thread, 4 times the workgroups.  Same operations in the same order as the kernels above: same bits
+// (checked over the edge cases, a child process with RADNET_WINO_V1 against this one: tests/test_gpu_winograd_edges.py).
 __global__ void __launch_bounds__(384) wino4_input_v2_kernel(const float* __restrict__ x, int nb, int H, int W_, int C, int TH, int TW,
                                                              float* __restrict__ V) {
   __shared__ float4 lds[36 * 64];
