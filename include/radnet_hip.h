@@ -315,7 +315,9 @@ int radnet_det_loss(radnet_ctx* ctx, const float* p_cls, const float* p_regr, co
 
 /* ---- optimizer: keras.optimizers.Adam over one flat arena (train.py:236-252) -----------------
  * zero_grad != 0: the gradient arena is cleared in the same pass (each value is read once and overwritten with 0),
- * so the next step's backward can accumulate into it without a separate memset. */
+ * so the next step's backward can accumulate into it without a separate memset.
+ * All four entry points share one argument check: n a multiple of 4, t >= 1, and p, g, m, v 16-byte aligned (every path reads
+ * float4; whole allocations are) -- otherwise a negative code, a message that names the entry point, and nothing is launched. */
 int radnet_adam_step(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr,
                      float beta1, float beta2, float eps, float grad_scale, int32_t zero_grad);
 /* The same step with the folded epilogue shifts of the layers whose biases live in p[bias_off, bias_off + bias_len) refreshed in the

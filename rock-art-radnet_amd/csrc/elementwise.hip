@@ -1,8 +1,7 @@
 // HBM-bound and small kernels of the Faster R-CNN hot path: pooling, RoI crop-resize, classifier
-// dense heads, losses (forward value + gradient in one pass), bias-gradient column sums, Adam.
+// dense heads, losses (forward value + gradient in one pass), bias-gradient column sums.
 // Each stands in for a TensorFlow op the reference graph invokes implicitly; citations inline.
 #include "radnet_internal.h"
-#include "radnet_wino4.h"
 
 namespace {
 
@@ -341,200 +340,6 @@ __global__ void __launch_bounds__(256) colsum_kernel(const float* __restrict__ g
   out[col] += t;                   // this workgroup is the only writer of its 64 columns in the launch
 }
 
-// ---- keras.optimizers.Adam (Keras 2 update rule) over a flat arena ------------------------------------------
-// aff_*: optionally (radnet_adam_step_affine) the folded epilogue shifts of the convs whose biases live in [aff_off4, aff_off4 + aff_n4)
-// float4 chunks of the arena are refreshed from the just-updated biases in the same pass: shift = scale * bias + t0
-// (FixedBatchNormalization.py:59-85 folded; one launch fewer on the classifier lane per step).
-// wz: optionally (radnet_adam_step_fused) 3x3 kernels [3][3][C][N] inside the arena whose Winograd F(4x4,3x3) transform U = G g G^T
-// [36][C][N] is rewritten in the same launch.  Those kernels are taken out of the flat sweep and given to workgroups of their own, behind
-// the sweep's in the grid: a workgroup owns 64 consecutive float4 chunks (c, 4 n) of a layer with all nine taps -- phase 1, every thread:
-// the Adam update of its share of the 9 x 64 chunks, coalesced, new weights also into LDS; phase 2, one thread per chunk: the transform
-// of its nine float4 values, wino4_filter_kernel's code, 36 coalesced 16-byte stores.  The transformed filters cost their own
-// bytes (4x the kernels') and no launch (three launches cost the classifier lane as much as the Winograd forward gives: DESIGN.md 4).
-constexpr int kAdamWinoMax = 12;
-struct AdamWino {
-  long long off4[kAdamWinoMax];   // first float4 of the layer's kernel in the arena
-  int cn4[kAdamWinoMax];          // C * N / 4: float4 chunks per tap (a multiple of 64)
-  int unit0[kAdamWinoMax + 1];    // first workgroup (relative to the first Winograd workgroup) of each layer; [n] = their total
-  float* u[kAdamWinoMax];
-  int n;
-  unsigned sweep_blocks; // workgroups of the flat sweep (the Winograd workgroups follow)
-};
-__device__ __forceinline__ void adam_one(float4& pp, const float4& gg, float4& mm, float4& vv, float lr_t, float b1, float b2, float eps, float gs) {
-#define ADAM1(q)                                         \
-  {                                                      \
-    float gq = gg.q * gs;                                \
-    mm.q = b1 * mm.q + (1.f - b1) * gq;                  \
-    vv.q = b2 * vv.q + (1.f - b2) * gq * gq;             \
-    pp.q = pp.q - lr_t * mm.q / (sqrtf(vv.q) + eps);     \
-  }
-  ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
-#undef ADAM1
-}
-__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long long n4, float lr_t, float b1, float b2, float eps,
-                                                   float gs, int zero_grad, long long aff_off4, long long aff_n4,
-                                                   const float* __restrict__ aff_scale, const float* __restrict__ aff_t0, float* __restrict__ aff_shift,
-                                                   AdamWino wz) {
-  float4* p4 = reinterpret_cast<float4*>(p);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  if (wz.n > 0 && blockIdx.x >= wz.sweep_blocks) {
-    __shared__ float4 taps[9][64];
-    const int unit = (int)(blockIdx.x - wz.sweep_blocks);
-    int layer = 0;
-    for (int l = 1; l < wz.n; ++l)
-      if (unit >= wz.unit0[l]) layer = l;
-    const int cn4 = wz.cn4[layer];
-    const long long j0 = (long long)(unit - wz.unit0[layer]) * 64;
-    for (int it = threadIdx.x; it < 9 * 64; it += 256) {
-      const int tap = it >> 6, jj = it & 63;
-      const long long k = wz.off4[layer] + (long long)tap * cn4 + j0 + jj;
-      float4 pp = p4[k], mm = m4[k], vv = v4[k];
-      adam_one(pp, g4[k], mm, vv, lr_t, b1, b2, eps, gs);
-      p4[k] = pp; m4[k] = mm; v4[k] = vv;
-      if (zero_grad) g4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      taps[tap][jj] = pp;
-    }
-    __syncthreads();
-    // phase 2: wino4_filter_kernel's own code on the same vector type (one thread per float4 chunk), so that both produce the same bits
-    // (dealing the six output rows to three waves changed nothing measurable -- 84 against 85 us -- and the compiler's FMA choices with it)
-    if (threadIdx.x < 64) {
-      float4 t[6][3];
-#pragma unroll
-      for (int bb = 0; bb < 3; ++bb) {
-        float4 col[3], o[6];
-#pragma unroll
-        for (int aa = 0; aa < 3; ++aa) col[aa] = taps[aa * 3 + bb][threadIdx.x];
-        g6(col, o);
-#pragma unroll
-        for (int aa = 0; aa < 6; ++aa) t[aa][bb] = o[aa];
-      }
-      float4* dst = reinterpret_cast<float4*>(wz.u[layer]) + j0 + threadIdx.x;
-#pragma unroll
-      for (int aa = 0; aa < 6; ++aa) {
-        float4 o[6];
-        g6(t[aa], o);
-#pragma unroll
-        for (int bb = 0; bb < 6; ++bb) dst[(long long)(6 * aa + bb) * cn4] = o[bb];
-      }
-    }
-    return;
-  }
-  const long long stride = (long long)(wz.n > 0 ? wz.sweep_blocks : gridDim.x) * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    bool skip = false;
-    for (int l = 0; l < wz.n; ++l) skip |= i >= wz.off4[l] && i < wz.off4[l] + 9ll * wz.cn4[l];
-    if (skip) continue;                          // a Winograd layer's kernel: updated by its own workgroups
-    float4 pp = p4[i], mm = m4[i], vv = v4[i];
-    adam_one(pp, g4[i], mm, vv, lr_t, b1, b2, eps, gs);
-    p4[i] = pp;
-    m4[i] = mm;
-    v4[i] = vv;
-    if (zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (aff_shift != nullptr && i >= aff_off4 && i < aff_off4 + aff_n4) {
-      const long long j = i - aff_off4;
-      const float4 a = reinterpret_cast<const float4*>(aff_scale)[j], c = reinterpret_cast<const float4*>(aff_t0)[j];
-      reinterpret_cast<float4*>(aff_shift)[j] = make_float4(a.x * pp.x + c.x, a.y * pp.y + c.y, a.z * pp.z + c.z, a.w * pp.w + c.w);
-    }
-  }
-}
-
-// bf16-mixed training (radnet_adam_step_bf16): the Adam step of adam_kernel (folded shifts optional) that ALSO rewrites the bf16
-// [n][ldk] images of up to kAdamBf16Max conv kernels [k][ldw] living in the arena -- the operands the bf16 forward convs read
-// (conv_bf16.hip).  The listed kernels leave the flat sweep and go to workgroups of their own behind it (radnet_adam_step_fused's
-// layout): a workgroup owns a 64 k x 64 n tile; phase 1, every thread: the Adam update of four float4 chunks of its rows,
-// coalesced along n, new weights into LDS (zeros for rows k..ldk); phase 2: the tile transposed out of LDS, eight consecutive k
-// of one output column per thread, rounded as weights_to_bf16_kernel rounds (to nearest, ties to even) and written as one
-// 16-byte store -- coalesced along k.  Same adam_one, same conversion: bit-identical to Adam followed by radnet_weights_to_bf16.
-constexpr int kAdamBf16Max = 16;
-constexpr int kAdamBf16Tile = 64;
-struct AdamBf16 {
-  long long off4[kAdamBf16Max];   // first float4 of the layer's kernel in the arena
-  int k[kAdamBf16Max], n[kAdamBf16Max], ldw4[kAdamBf16Max], ldk[kAdamBf16Max];
-  int ntn[kAdamBf16Max];          // n tiles per k tile row: cdiv(ldw, 64)
-  int unit0[kAdamBf16Max + 1];    // first workgroup (relative to the first tile workgroup) of each layer; [n] = their total
-  uint16_t* wt[kAdamBf16Max];
-  int nl;
-  unsigned sweep_blocks;          // workgroups of the flat sweep (the tile workgroups follow)
-  // the flat sweep runs over the arena WITHOUT the listed kernels: its index j lies in gap g when pref[g] <= j < pref[g + 1] and
-  // stands for float4 gap0[g] + j - pref[g] (a sweep over the whole arena that skips the kernels spends its time skipping them)
-  long long gap0[kAdamBf16Max + 1], pref[kAdamBf16Max + 2];
-  int ngap;
-};
-__global__ void __launch_bounds__(256) adam_bf16_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, long long n4, float lr_t, float b1, float b2, float eps,
-                                                        float gs, int zero_grad, long long aff_off4, long long aff_n4,
-                                                        const float* __restrict__ aff_scale, const float* __restrict__ aff_t0,
-                                                        float* __restrict__ aff_shift, AdamBf16 lz) {
-  float4* p4 = reinterpret_cast<float4*>(p);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  if (blockIdx.x >= lz.sweep_blocks) {
-    __shared__ float tile[kAdamBf16Tile][kAdamBf16Tile + 1];     // [k][n], odd pitch: the transposed reads hit 64 different banks
-    const int unit = (int)(blockIdx.x - lz.sweep_blocks);
-    int layer = 0;
-    for (int l = 1; l < lz.nl; ++l)
-      if (unit >= lz.unit0[l]) layer = l;
-    const int u = unit - lz.unit0[layer];
-    const int k0 = (u / lz.ntn[layer]) * kAdamBf16Tile, n0 = (u % lz.ntn[layer]) * kAdamBf16Tile;
-    const int K = lz.k[layer], ldw4 = lz.ldw4[layer];
-    const int c4 = threadIdx.x & 15;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int r = (threadIdx.x >> 4) + 16 * it;
-      const int kk = k0 + r, j4 = n0 / 4 + c4;
-      float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (kk < K && j4 < ldw4) {
-        const long long i = lz.off4[layer] + (long long)kk * ldw4 + j4;
-        float4 mm = m4[i], vv = v4[i];
-        pp = p4[i];
-        adam_one(pp, g4[i], mm, vv, lr_t, b1, b2, eps, gs);
-        p4[i] = pp; m4[i] = mm; v4[i] = vv;
-        if (zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      tile[r][4 * c4] = pp.x; tile[r][4 * c4 + 1] = pp.y; tile[r][4 * c4 + 2] = pp.z; tile[r][4 * c4 + 3] = pp.w;
-    }
-    __syncthreads();
-    const int N = lz.n[layer], ldk = lz.ldk[layer];
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int q = threadIdx.x + 256 * it;           // 64 columns x 8 chunks of 8 k
-      const int c = q >> 3, kc = (q & 7) * 8;
-      const int col = n0 + c, kk = k0 + kc;
-      if (col >= N || kk >= ldk) continue;            // ldk % 8 == 0: a chunk lies wholly inside [0, ldk) or wholly outside
-      uint16_t h[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) h[e] = kk + e < K ? __builtin_bit_cast(uint16_t, (__bf16)tile[kc + e][c]) : (uint16_t)0;
-      uint4 o;
-      o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
-      o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
-      *reinterpret_cast<uint4*>(lz.wt[layer] + (long long)col * ldk + kk) = o;
-    }
-    return;
-  }
-  const long long rest = lz.pref[lz.ngap];
-  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < rest; j += (long long)lz.sweep_blocks * blockDim.x) {
-    int gp = 0;
-    for (int q = 1; q < lz.ngap; ++q)
-      if (j >= lz.pref[q]) gp = q;
-    const long long i = lz.gap0[gp] + (j - lz.pref[gp]);
-    float4 pp = p4[i], mm = m4[i], vv = v4[i];
-    adam_one(pp, g4[i], mm, vv, lr_t, b1, b2, eps, gs);
-    p4[i] = pp;
-    m4[i] = mm;
-    v4[i] = vv;
-    if (zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (aff_shift != nullptr && i >= aff_off4 && i < aff_off4 + aff_n4) {
-      const long long j = i - aff_off4;
-      const float4 a = reinterpret_cast<const float4*>(aff_scale)[j], c = reinterpret_cast<const float4*>(aff_t0)[j];
-      reinterpret_cast<float4*>(aff_shift)[j] = make_float4(a.x * pp.x + c.x, a.y * pp.y + c.y, a.z * pp.z + c.z, a.w * pp.w + c.w);
-    }
-  }
-}
-
 // ---- RPN losses (losses.py:16-66) ------------------------------------------------------------------------------
 // scratch (double): [0] sum valid, [1] sum valid*ce, [2] sum mask, [3] sum mask*smoothL1
 __device__ __forceinline__ float bce_swapped_logit(float t) {
@@ -749,13 +554,6 @@ __global__ void __launch_bounds__(256) affine_vec_kernel(float* __restrict__ out
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = a[i] * b[i] + c[i];
 }
 
-inline int grid_for(long long total, int block = 256, int cap = 4096) {
-  long long b = (total + block - 1) / block;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
-}
-
 }  // namespace
 
 extern "C" int radnet_maxpool_fwd(radnet_ctx* ctx, const float* x, float* y, int32_t nb, int32_t h, int32_t w, int32_t c, int32_t k, int32_t s) {
@@ -843,130 +641,6 @@ extern "C" int radnet_colsum(radnet_ctx* ctx, const float* g, int32_t m, int32_t
   hipLaunchKernelGGL(colsum_kernel, dim3(radnet_cdiv(n, 64), radnet_cdiv(m, rows_per_block)), dim3(256), 0, ctx->stream, g, m, n, ld, gscale,
                      out, rows_per_block, partials, reinterpret_cast<unsigned*>(ctx->aux + kAuxColsumCounters));
   RADNET_CHECK_LAUNCH(ctx, "colsum");
-  return RADNET_OK;
-}
-
-extern "C" int radnet_adam_step(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,
-                                float beta2, float eps, float grad_scale, int32_t zero_grad) {
-  if (!ctx || !p || !g || !m || !v) return RADNET_ERR_ARG;
-  if (n % 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam: arena length must be a multiple of 4");
-  if (t < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam: step counter starts at 1");
-  // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)   (keras.optimizers.Adam.get_updates)
-  const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4, 256, 8192)), dim3(256), 0, ctx->stream, p, g, m, v, (long long)(n / 4), (float)lr_t,
-                     beta1, beta2, eps, grad_scale, (int)zero_grad, 0ll, 0ll, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, AdamWino{});
-  RADNET_CHECK_LAUNCH(ctx, "adam");
-  return RADNET_OK;
-}
-
-extern "C" int radnet_adam_step_affine(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,
-                                       float beta2, float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len,
-                                       const float* scale, const float* t0, float* shift) {
-  if (!ctx || !p || !g || !m || !v || !scale || !t0 || !shift) return RADNET_ERR_ARG;
-  if ((n % 4) || (bias_off % 4) || (bias_len % 4) || bias_off < 0 || bias_len < 0 || bias_off + bias_len > n)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_affine: arena length %lld, bias range [%lld, +%lld) must be multiples of 4 inside the arena", (long long)n,
-                (long long)bias_off, (long long)bias_len);
-  if (((uintptr_t)scale | (uintptr_t)t0 | (uintptr_t)shift) & 15) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_affine: scale / t0 / shift must be 16-byte aligned");
-  if (t < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam: step counter starts at 1");
-  const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4, 256, 8192)), dim3(256), 0, ctx->stream, p, g, m, v, (long long)(n / 4), (float)lr_t,
-                     beta1, beta2, eps, grad_scale, (int)zero_grad, (long long)(bias_off / 4), (long long)(bias_len / 4), scale, t0, shift, AdamWino{});
-  RADNET_CHECK_LAUNCH(ctx, "adam_affine");
-  return RADNET_OK;
-}
-
-extern "C" int radnet_adam_step_fused(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,
-                                      float beta2, float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len,
-                                      const float* scale, const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers) {
-  if (!ctx || !p || !g || !m || !v || n_layers < 0 || n_layers > kAdamWinoMax || (n_layers > 0 && !layers)) return RADNET_ERR_ARG;
-  if (shift != nullptr && (!scale || !t0)) return RADNET_ERR_ARG;
-  if ((n % 4) || (bias_off % 4) || (bias_len % 4) || bias_off < 0 || bias_len < 0 || bias_off + bias_len > n)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_fused: arena length %lld, bias range [%lld, +%lld) must be multiples of 4 inside the arena", (long long)n,
-                (long long)bias_off, (long long)bias_len);
-  if (shift && (((uintptr_t)scale | (uintptr_t)t0 | (uintptr_t)shift) & 15)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_fused: scale / t0 / shift must be 16-byte aligned");
-  if (t < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam: step counter starts at 1");
-  AdamWino wz{};
-  wz.n = n_layers;
-  long long in_layers = 0;
-  for (int l = 0; l < n_layers; ++l) {
-    const radnet_adam_wino& d = layers[l];
-    const int64_t len = 9ll * d.c * d.n;
-    if (!d.u || d.c <= 0 || d.n <= 0 || (d.n & 3) || (d.off & 3) || d.off < 0 || d.off + len > n || ((uintptr_t)d.u & 15) || (int64_t)d.c * d.n / 4 >= (1ll << 28) ||
-        ((int64_t)d.c * d.n / 4) % 64)
-      RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_fused: layer %d (offset %lld, c %d, n %d) does not describe a dense [3][3][c][n] kernel inside the arena with c*n a multiple of 256",
-                  l, (long long)d.off, d.c, d.n);
-    if (shift && d.off < bias_off + bias_len && bias_off < d.off + len) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_fused: layer %d overlaps the bias range", l);
-    for (int k = 0; k < l; ++k)
-      if (d.off < layers[k].off + 9ll * layers[k].c * layers[k].n && layers[k].off < d.off + len) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_fused: layers %d and %d overlap", k, l);
-    wz.off4[l] = d.off / 4;
-    wz.cn4[l] = (int)((int64_t)d.c * d.n / 4);
-    wz.u[l] = d.u;
-    wz.unit0[l] = l == 0 ? 0 : wz.unit0[l - 1] + wz.cn4[l - 1] / 64;
-    in_layers += len / 4;
-  }
-  wz.unit0[n_layers] = n_layers ? wz.unit0[n_layers - 1] + wz.cn4[n_layers - 1] / 64 : 0;
-  const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t));
-  const unsigned sweep = (unsigned)grid_for(std::max<long long>(n / 4 - in_layers, 1), 256, 8192);
-  wz.sweep_blocks = sweep;
-  hipLaunchKernelGGL(adam_kernel, dim3(sweep + (unsigned)wz.unit0[n_layers]), dim3(256), 0, ctx->stream, p, g, m, v, (long long)(n / 4), (float)lr_t,
-                     beta1, beta2, eps, grad_scale, (int)zero_grad, (long long)(bias_off / 4), (long long)(shift ? bias_len / 4 : 0), scale, t0, shift, wz);
-  RADNET_CHECK_LAUNCH(ctx, "adam_fused");
-  return RADNET_OK;
-}
-
-extern "C" int radnet_adam_step_bf16(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,
-                                     float beta2, float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len,
-                                     const float* scale, const float* t0, float* shift, const radnet_adam_bf16* layers, int32_t n_layers) {
-  if (!ctx) return RADNET_ERR_ARG;
-  if (!p || !g || !m || !v || n_layers < 0 || (n_layers > 0 && !layers)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: null tensor");
-  if (n_layers > kAdamBf16Max) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: %d layers (at most %d)", n_layers, kAdamBf16Max);
-  if (shift != nullptr && (!scale || !t0)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: shift without scale / t0");
-  if ((n % 4) || (bias_off % 4) || (bias_len % 4) || bias_off < 0 || bias_len < 0 || bias_off + bias_len > n)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: arena length %lld, bias range [%lld, +%lld) must be multiples of 4 inside the arena", (long long)n,
-                (long long)bias_off, (long long)bias_len);
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: arenas must be 16-byte aligned");
-  if (shift && (((uintptr_t)scale | (uintptr_t)t0 | (uintptr_t)shift) & 15)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: scale / t0 / shift must be 16-byte aligned");
-  if (t < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam: step counter starts at 1");
-  AdamBf16 lz{};
-  lz.nl = n_layers;
-  long long in_layers = 0;
-  for (int l = 0; l < n_layers; ++l) {
-    const radnet_adam_bf16& d = layers[l];
-    if (!d.wt || d.k <= 0 || d.n <= 0 || d.ldw < d.n || (d.ldw & 3) || (d.off & 3) || d.ldk < d.k || (d.ldk & 7) || ((uintptr_t)d.wt & 15) ||
-        d.k >= (1 << 24) || d.ldk >= (1 << 24) || d.ldw >= (1 << 20))
-      RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layer %d (k %d, n %d, ldw %d, ldk %d): needs ldw >= n, ldk >= k, ldw %% 4 == 0, ldk %% 8 == 0, "
-                  "offset %% 4 == 0, a 16-byte aligned image", l, d.k, d.n, d.ldw, d.ldk);
-    const int64_t len = (int64_t)d.k * d.ldw;
-    if (d.off < 0 || d.off + len > n) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layer %d [%lld, +%lld) lies outside the arena", l, (long long)d.off, (long long)len);
-    if (shift && bias_len > 0 && d.off < bias_off + bias_len && bias_off < d.off + len) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layer %d overlaps the bias range", l);
-    for (int k = 0; k < l; ++k)
-      if (d.off < layers[k].off + (int64_t)layers[k].k * layers[k].ldw && layers[k].off < d.off + len) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_bf16: layers %d and %d overlap", k, l);
-    lz.off4[l] = d.off / 4;
-    lz.k[l] = d.k; lz.n[l] = d.n; lz.ldw4[l] = d.ldw / 4; lz.ldk[l] = d.ldk; lz.wt[l] = d.wt;
-    lz.ntn[l] = radnet_cdiv(d.ldw, kAdamBf16Tile);
-    const int units = radnet_cdiv(std::max(d.k, d.ldk), kAdamBf16Tile) * lz.ntn[l];
-    lz.unit0[l + 1] = lz.unit0[l] + units;
-    in_layers += len / 4;
-  }
-  // gaps between the listed kernels, in arena order
-  int order[kAdamBf16Max];
-  for (int l = 0; l < n_layers; ++l) order[l] = l;
-  std::sort(order, order + n_layers, [&](int a, int b) { return layers[a].off < layers[b].off; });
-  long long at4 = 0;
-  for (int q = 0; q <= n_layers; ++q) {
-    const long long end4 = q < n_layers ? layers[order[q]].off / 4 : n / 4;
-    lz.gap0[lz.ngap] = at4;
-    lz.pref[lz.ngap + 1] = lz.pref[lz.ngap] + (end4 - at4);
-    ++lz.ngap;
-    if (q < n_layers) at4 = end4 + (long long)layers[order[q]].k * layers[order[q]].ldw / 4;
-  }
-  const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t));
-  const unsigned sweep = (unsigned)grid_for(std::max<long long>(n / 4 - in_layers, 1), 256, 8192);
-  lz.sweep_blocks = sweep;
-  hipLaunchKernelGGL(adam_bf16_kernel, dim3(sweep + (unsigned)lz.unit0[n_layers]), dim3(256), 0, ctx->stream, p, g, m, v, (long long)(n / 4),
-                     (float)lr_t, beta1, beta2, eps, grad_scale, (int)zero_grad, (long long)(bias_off / 4), (long long)(shift ? bias_len / 4 : 0), scale,
-                     t0, shift, lz);
-  RADNET_CHECK_LAUNCH(ctx, "adam_bf16");
   return RADNET_OK;
 }
 

@@ -27,6 +27,7 @@ from .bf16_images import Bf16Images
 from .program import MIXED_PRECISIONS, PRECISIONS  # noqa: F401  (FasterRCNNEngine(precision=...): see __init__)
 
 BN_EPS = 1e-3        # FixedBatchNormalization.py:8
+ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-7      # keras.optimizers.Adam's defaults (train.py:236-252)
 RES_STAGES = ((2, "abc", (64, 64, 256), 1), (3, "abcd", (128, 128, 512), 2), (4, "abcdef", (256, 256, 1024), 2))
 HEAD_STAGE = (5, "abc", (512, 512, 2048), 2)
 RPN_LD = 64          # fused RPN head GEMM width (A + 4A = 60 for 12 anchors, padded)
@@ -998,17 +999,15 @@ class FasterRCNNEngine:
         fused = (is_head and self.head_bias_len > 0 and self.head_bias_off % 4 == 0
                  and self.head_bias_len % 4 == 0 and os.environ.get("RADNET_NO_ADAM_AFFINE", "0") != "1")
         wino = self._head_adam_wino() if is_head and self.head_train_wino else None
-        if self.precision in MIXED_PRECISIONS:
-            # Adam (+ the folded shifts on the head arena) and the bf16 images of the arena's convs, one launch
-            arr, n_l = self.bf16.adam_layers(arena)
-            self.ctx.check(self.lib.radnet_adam_step_bf16(
-                self.ctx.h, arena.p.data_ptr(), arena.g.data_ptr(), arena.m.data_ptr(), arena.v.data_ptr(), C.c_int64(arena.n), arena.t, C.c_float(self.lr),
-                C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1 if zero_grad else 0,
-                C.c_int64(self.head_bias_off if fused else 0), C.c_int64(self.head_bias_len if fused else 0),
-                self.head_scale.data_ptr() if fused else None, self.head_t0.data_ptr() if fused else None, self.head_shift.data_ptr() if fused else None,
-                arr, n_l), "radnet_adam_step_bf16")
-            if fused:
-                self._head_shift_fresh = True
+        mixed = self.precision in MIXED_PRECISIONS
+        # one launch: Adam, on the head arena the folded shifts (round 4: one launch fewer on the head lane), and either the bf16 images
+        # of the arena's convs (bf16 modes) or the Winograd filters of the classifier's 3x3 convs
+        self._adam_launch(arena, arena.m, arena.v, arena.t, grad_scale, zero_grad,
+                          affine=(self.head_bias_off, self.head_bias_len, self.head_scale, self.head_t0, self.head_shift) if fused else None,
+                          wino=wino, bf16=self.bf16.adam_layers(arena) if mixed else None)
+        if fused:
+            self._head_shift_fresh = True
+        if mixed:
             reg = self.bf16.dgrad_arena.get(id(arena))
             if reg is not None and reg.count:
                 # bf16-train: the dgrad images of this arena's layers, ONE cast launch over the registry behind Adam on the same lane
@@ -1016,25 +1015,8 @@ class FasterRCNNEngine:
                 self.ctx.check(self.lib.radnet_weights_to_bf16_dgrad_arena(self.ctx.h, arena.p.data_ptr(), C.c_int64(arena.n), reg.array, reg.count),
                                "radnet_weights_to_bf16_dgrad_arena")
             return
-        if wino is not None:      # Adam #2 + folded shifts + the Winograd filters of the classifier's 3x3 convs, one launch
-            arr, n_l = wino
-            self.ctx.check(self.lib.radnet_adam_step_fused(
-                self.ctx.h, arena.p.data_ptr(), arena.g.data_ptr(), arena.m.data_ptr(), arena.v.data_ptr(), C.c_int64(arena.n), arena.t, C.c_float(self.lr),
-                C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1 if zero_grad else 0,
-                C.c_int64(self.head_bias_off if fused else 0), C.c_int64(self.head_bias_len if fused else 0),
-                self.head_scale.data_ptr() if fused else None, self.head_t0.data_ptr() if fused else None, self.head_shift.data_ptr() if fused else None,
-                arr, n_l), "radnet_adam_step_fused")
-            if fused:
-                self._head_shift_fresh = True
+        if wino is not None:
             return
-        if fused:       # Adam #2 and the refresh of the classifier convs' folded shifts as one launch (round 4: one launch fewer on the head lane)
-            self.ctx.call("radnet_adam_step_affine", arena.p, arena.g, arena.m, arena.v, C.c_int64(arena.n), arena.t, C.c_float(self.lr),
-                          C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1 if zero_grad else 0,
-                          C.c_int64(self.head_bias_off), C.c_int64(self.head_bias_len), self.head_scale, self.head_t0, self.head_shift)
-            self._head_shift_fresh = True
-        else:
-            self.ctx.call("radnet_adam_step", arena.p, arena.g, arena.m, arena.v, C.c_int64(arena.n), arena.t, C.c_float(self.lr),
-                          C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1 if zero_grad else 0)
         if arena is self.rpn_arena:
             self._refresh_winograd(["rpn_conv1"])          # its forward runs on the transformed filter
         elif arena is self.head_arena:
@@ -1042,6 +1024,21 @@ class FasterRCNNEngine:
             if self.head_train_wino:    # (the fused pass above could not be used: dense-kernel check failed)
                 self._refresh_winograd(list(self.INFERENCE_WINOGRAD_LAYERS))
                 self._inference_filters_stale = False
+
+    def _adam_launch(self, arena, m, v, t, grad_scale, zero_grad, affine=None, wino=None, bf16=None):
+        """The Adam launch over `arena` with the moments m, v at step t (the cont engine keeps two sets per arena).  affine:
+        (bias_off, bias_len, scale, t0, shift), the folded shifts refreshed in the same pass; bf16 / wino: (radnet_adam_bf16[], n) /
+        (radnet_adam_wino[], n), the layers whose bf16 images / Winograd filters are rewritten in it.  They pick the entry point."""
+        layers = bf16 if bf16 is not None else wino
+        args = [arena.p, arena.g, m, v, C.c_int64(arena.n), t, C.c_float(self.lr), C.c_float(ADAM_BETA1), C.c_float(ADAM_BETA2), C.c_float(ADAM_EPS),
+                C.c_float(grad_scale), 1 if zero_grad else 0]
+        if affine is not None or layers is not None:
+            bias_off, bias_len, scale, t0, shift = affine if affine is not None else (0, 0, None, None, None)
+            args += [C.c_int64(bias_off), C.c_int64(bias_len), scale, t0, shift]
+        if layers is not None:
+            args += [layers[0], layers[1]]
+        self.ctx.call("radnet_adam_step_bf16" if bf16 is not None else "radnet_adam_step_fused" if wino is not None
+                      else "radnet_adam_step_affine" if affine is not None else "radnet_adam_step", *args)
 
     def _wino_wgrad_op(self, c, V, dy, ld_dy, nb, h, w, shared):
         """Weight gradient of a Winograd layer in the transformed domain, on the V its forward pass left: dy transform, one batched

@@ -106,13 +106,10 @@ class ContEngine(FasterRCNNEngine):
             m, v, t = ar.m2, ar.v2, ar.t2
         wino = self._s34_adam_wino()
         if wino is not None:          # Adam + folded shifts + the Winograd filters of the ten 3x3 kernels, one launch
-            self.ctx.check(self.lib.radnet_adam_step_fused(
-                self.ctx.h, ar.p.data_ptr(), ar.g.data_ptr(), m.data_ptr(), v.data_ptr(), C.c_int64(ar.n), t, C.c_float(self.lr), C.c_float(0.9),
-                C.c_float(0.999), C.c_float(1e-7), C.c_float(grad_scale), 1, C.c_int64(self.s34_bias_off), C.c_int64(self.s34_bias_len),
-                self.s34_scale.data_ptr(), self.s34_t0.data_ptr(), self.s34_shift.data_ptr(), wino[0], wino[1]), "radnet_adam_step_fused")
+            self._adam_launch(ar, m, v, t, grad_scale, True, wino=wino,
+                              affine=(self.s34_bias_off, self.s34_bias_len, self.s34_scale, self.s34_t0, self.s34_shift))
             return
-        self.ctx.call("radnet_adam_step", ar.p, ar.g, m, v, C.c_int64(ar.n), t, C.c_float(self.lr), C.c_float(0.9), C.c_float(0.999),
-                      C.c_float(1e-7), C.c_float(grad_scale), 1)
+        self._adam_launch(ar, m, v, t, grad_scale, True)
         self.refresh_s34_shift()
         if self.S34_WINOGRAD and self.use_winograd:
             self._refresh_winograd([n for n in self.WINOGRAD_F4_LAYERS if n in self.convs])

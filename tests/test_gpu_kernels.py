@@ -396,44 +396,108 @@ def test_adam(ctx):
     assert np.allclose(md.cpu().numpy(), m, rtol=1e-5, atol=1e-8)
 
 
-def test_adam_fused_equals_adam_then_affine_then_filter_transforms(ctx):
+# (layers (offset, c, n): dense [3][3][c][n] kernels inside the arena, arena length, bias range or None: no shift refresh)
+ADAM_FUSED_LAYOUTS = {
+    "interior": ([(64, 16, 16), (5000, 64, 32)], 5000 + 9 * 64 * 32 + 1024, (5000 + 9 * 64 * 32 + 1024 - 256, 128)),
+    # listed in descending offset, the first at the arena's start, the two adjacent: an empty first gap and an empty gap between them
+    "descending_adjacent": ([(2304, 64, 32), (0, 16, 16)], 20736 + 1024, (20736 + 1024 - 256, 128)),
+    # the last layer ends at the arena's end: the last gap is empty too, nothing is left for the sweep
+    "whole_arena": ([(2304, 64, 32), (0, 16, 16)], 20736, None),
+    # no layers: radnet_adam_step_affine
+    "no_layers": ([], 5000 + 9 * 64 * 32 + 1024, (5000 + 9 * 64 * 32 + 1024 - 256, 128)),
+}
+
+
+@pytest.mark.parametrize("layout", list(ADAM_FUSED_LAYOUTS))
+def test_adam_fused_equals_adam_then_affine_then_filter_transforms(ctx, layout):
     """radnet_adam_step_fused (round 4): one pass = radnet_adam_step over the arena + radnet_affine_vec for the bias range +
-    radnet_winograd4_filter for the 3x3 kernels inside it, BIT FOR BIT (the native train step and the scheduler-driven one use either)."""
+    radnet_winograd4_filter for the 3x3 kernels inside it, BIT FOR BIT (the native train step and the scheduler-driven one use either).
+    Without layers the other side is radnet_adam_step_affine."""
     from radnet_hip import lib as L
     rs = np.random.RandomState(23)
-    layers = [(64, 16, 16), (5000, 64, 32)]                       # (offset, c, n): dense [3][3][c][n] kernels inside the arena
-    n = 5000 + 9 * 64 * 32 + 1024
-    bias_off, bias_len = n - 256, 128
+    layers, n, bias = ADAM_FUSED_LAYOUTS[layout]
+    bias_off, bias_len = bias if bias else (0, 0)
     base = dict(p=rs.standard_normal(n).astype(np.float32), m=(0.01 * rs.standard_normal(n)).astype(np.float32),
                 v=(0.01 * rs.uniform(size=n)).astype(np.float32), g=(0.1 * rs.standard_normal(n)).astype(np.float32))
-    scale, t0 = rs.uniform(0.5, 1.5, bias_len).astype(np.float32), rs.standard_normal(bias_len).astype(np.float32)
+    scale, t0 = rs.uniform(0.5, 1.5, max(bias_len, 4)).astype(np.float32), rs.standard_normal(max(bias_len, 4)).astype(np.float32)
     sd, td = dev(scale), dev(t0)
     args = lambda t: (C.c_int64(n), t, C.c_float(1e-3), C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(0.5), 1)
 
     def run(fused):
         a = {k: dev(v) for k, v in base.items()}
-        shift = torch.zeros(bias_len, device="cuda")
+        shift = torch.zeros(max(bias_len, 4), device="cuda")
+        aff = (C.c_int64(bias_off), C.c_int64(bias_len), sd.data_ptr(), td.data_ptr(), shift.data_ptr()) if bias else (C.c_int64(0), C.c_int64(0), None, None, None)
         us = [torch.full((36, c, nn), float("nan"), device="cuda") for _, c, nn in layers]
         for t in (1, 2):
             a["g"].copy_(dev(base["g"]) * t)
             if fused:
-                arr = (L.AdamWino * len(layers))()
+                arr = (L.AdamWino * max(len(layers), 1))()
                 for k, (off, c, nn) in enumerate(layers):
                     arr[k].off, arr[k].c, arr[k].n, arr[k].u = off, c, nn, us[k].data_ptr()
                 ctx.check(ctx.lib.radnet_adam_step_fused(ctx.h, a["p"].data_ptr(), a["g"].data_ptr(), a["m"].data_ptr(), a["v"].data_ptr(), *args(t),
-                                                         C.c_int64(bias_off), C.c_int64(bias_len), sd.data_ptr(), td.data_ptr(), shift.data_ptr(), arr, len(layers)),
+                                                         *aff, arr, len(layers)),
                           "adam_fused")
+            elif not layers:
+                ctx.check(ctx.lib.radnet_adam_step_affine(ctx.h, a["p"].data_ptr(), a["g"].data_ptr(), a["m"].data_ptr(), a["v"].data_ptr(), *args(t), *aff),
+                          "adam_affine")
             else:
                 ctx.call("radnet_adam_step", a["p"], a["g"], a["m"], a["v"], *args(t))
-                ctx.call("radnet_affine_vec", shift, sd, a["p"][bias_off:], td, C.c_int64(bias_len))
+                if bias:
+                    ctx.call("radnet_affine_vec", shift, sd, a["p"][bias_off:], td, C.c_int64(bias_len))
                 for k, (off, c, nn) in enumerate(layers):
                     ctx.call("radnet_winograd4_filter", a["p"][off:], c, nn, nn, us[k])
         torch.cuda.synchronize()
         return [a[k].cpu().numpy() for k in "pmvg"] + [shift.cpu().numpy()] + [u.cpu().numpy() for u in us]
 
-    for name, x, y in zip(("p", "m", "v", "g", "shift", "u0", "u1"), run(True), run(False)):
+    names = ("p", "m", "v", "g", "shift") + tuple("u%d" % k for k in range(len(layers)))
+    for name, x, y in zip(names, run(True), run(False)):
         assert not np.isnan(x).any(), name
         assert np.array_equal(x, y), (name, int((x != y).sum()), float(np.abs(x - y).max()))
+
+
+def test_adam_fp32_entries_reject_bad_arguments(ctx):
+    """radnet_adam_step / _affine / _fused: a negative code, a message that names the entry point, nothing launched."""
+    from radnet_hip import lib as L
+    rs = np.random.RandomState(29)
+    n, bias_off, bias_len = 5000 + 9 * 64 * 32 + 1024, 5000 + 9 * 64 * 32 + 1024 - 256, 128
+    st = {k: dev(rs.standard_normal(n).astype(np.float32)) for k in "pgmv"}
+    st["v"].abs_()
+    before = {k: x.clone() for k, x in st.items()}
+    sd, td, shift = dev(rs.uniform(0.5, 1.5, bias_len).astype(np.float32)), dev(rs.standard_normal(bias_len).astype(np.float32)), torch.zeros(bias_len, device="cuda")
+    us = [torch.zeros(36, 64, 32, device="cuda") for _ in range(13)]
+    good = [(64, 16, 16, us[0].data_ptr()), (5000, 64, 32, us[1].data_ptr())]
+
+    def attempt(entry, p_shift=0, n_=n, t=1, bias=(bias_off, bias_len), layers=good):
+        ptrs = [st["p"].data_ptr() + p_shift] + [st[k].data_ptr() for k in "gmv"]
+        args = ptrs + [C.c_int64(n_), t, C.c_float(1e-3), C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(0.5), 1]
+        if entry != "radnet_adam_step":
+            args += [C.c_int64(bias[0]), C.c_int64(bias[1]), sd.data_ptr(), td.data_ptr(), shift.data_ptr()]
+        if entry == "radnet_adam_step_fused":
+            arr = (L.AdamWino * max(len(layers), 1))()
+            for k, (off, c, nn, u) in enumerate(layers):
+                arr[k].off, arr[k].c, arr[k].n, arr[k].u = off, c, nn, u
+            args += [arr, len(layers)]
+        rc = getattr(ctx.lib, entry)(ctx.h, *args)
+        msg = ctx.lib.radnet_last_error(ctx.h)
+        assert rc < 0, (entry, rc)
+        assert msg and msg.decode().startswith(entry[len("radnet_"):].replace("_step", "") + ":"), (entry, msg)
+
+    every = ("radnet_adam_step", "radnet_adam_step_affine", "radnet_adam_step_fused")
+    for entry in every:
+        attempt(entry, p_shift=4, n_=n - 4)                       # an arena pointer off by 4 bytes
+        attempt(entry, n_=n - 2)                                  # n % 4 != 0
+        attempt(entry, t=0)                                       # the step counter starts at 1
+    for entry in every[1:]:
+        attempt(entry, bias=(n - 64, 128))                        # a bias range past the arena
+    fused = every[2]
+    attempt(fused, layers=[(2000, 64, 32, us[1].data_ptr()), good[0]])                              # two overlapping layers
+    attempt(fused, layers=[good[0], (bias_off - 9 * 64 * 32 + 64, 64, 32, us[1].data_ptr())])      # a layer over the bias range
+    attempt(fused, layers=[(2304 * k, 16, 16, us[k].data_ptr()) for k in range(13)])                # 13 layers
+    attempt(fused, layers=[(64, 12, 16, us[0].data_ptr())])                                         # c * n = 192: not a multiple of 256
+    attempt(fused, layers=[good[0], (5000, 64, 32, None)])                                          # a null u
+    torch.cuda.synchronize()
+    for k in "pgmv":
+        assert torch.equal(st[k].view(torch.int32), before[k].view(torch.int32)), k
 
 
 # ---- fp64 glue: bit-exact against vectors produced by the reference itself -------------------------------------
