@@ -559,8 +559,9 @@ __global__ void __launch_bounds__(256) affine_vec_kernel(float* __restrict__ out
 extern "C" int radnet_maxpool_fwd(radnet_ctx* ctx, const float* x, float* y, int32_t nb, int32_t h, int32_t w, int32_t c, int32_t k, int32_t s) {
   if (!ctx || !x || !y) return RADNET_ERR_ARG;
   if (c % 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "maxpool: c=%d not a multiple of 4", c);
+  if (nb < 1 || c < 4 || k < 1 || s < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "maxpool: bad nb=%d c=%d k=%d s=%d", nb, c, k, s);
+  if (h < k || w < k) RADNET_FAIL(ctx, RADNET_ERR_ARG, "maxpool: empty output");          // (h - k) / s truncates towards zero: -1 / 2 + 1 == 1
   const int oh = (h - k) / s + 1, ow = (w - k) / s + 1;
-  if (oh <= 0 || ow <= 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "maxpool: empty output");
   const long long total = (long long)nb * oh * ow * (c / 4);
   if (total >= (1ll << 31)) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "maxpool: %lld work items (32-bit index arithmetic)", total);
   hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, y, nb, h, w, c / 4, oh, ow, k, s);
@@ -581,7 +582,9 @@ extern "C" int radnet_roi_resize_fwd(radnet_ctx* ctx, const float* fmap, int32_t
 extern "C" int radnet_roi_resize_bwd(radnet_ctx* ctx, const float* dy, int32_t h, int32_t w, int32_t c, const float* rois, int32_t r,
                                      int32_t ps, float* dfmap) {
   if (!ctx || !dy || !rois || !dfmap) return RADNET_ERR_ARG;
-  if (ctx->deterministic && (c % 4) == 0 && ps <= 32 && (long long)h * w < (1ll << 31))
+  if (c % 4 || c < 4 || r <= 0 || ps <= 0 || h <= 0 || w <= 0)
+    RADNET_FAIL(ctx, RADNET_ERR_ARG, "roi_resize_bwd: bad c=%d r=%d ps=%d map %dx%d", c, r, ps, h, w);
+  if (ctx->deterministic && ps <= 32 && (long long)h * w < (1ll << 31))
     hipLaunchKernelGGL(roi_resize_bwd_ordered_kernel, dim3(h * w), dim3(256), 0, ctx->stream, dy, h, w, c / 4, rois, r, ps, dfmap);
   else
     hipLaunchKernelGGL(roi_resize_bwd_kernel, dim3(r * ps * ps), dim3(256), 0, ctx->stream, dy, h, w, c, rois, ps, dfmap);
@@ -592,6 +595,7 @@ extern "C" int radnet_roi_resize_bwd(radnet_ctx* ctx, const float* dy, int32_t h
 extern "C" int radnet_avgpool_fwd(radnet_ctx* ctx, const float* x, int32_t r, int32_t hw, int32_t c, float* y) {
   if (!ctx || !x || !y) return RADNET_ERR_ARG;
   if (c % 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "avgpool: c %% 4");
+  if (r < 1 || hw < 1 || c < 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "avgpool: bad r=%d hw=%d c=%d", r, hw, c);
   hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(radnet_cdiv((long long)r * (c / 4), 256)), dim3(256), 0, ctx->stream, x, r, hw, c / 4, y);
   RADNET_CHECK_LAUNCH(ctx, "avgpool_fwd");
   return RADNET_OK;
@@ -600,6 +604,7 @@ extern "C" int radnet_avgpool_fwd(radnet_ctx* ctx, const float* x, int32_t r, in
 extern "C" int radnet_avgpool_bwd_relu(radnet_ctx* ctx, const float* dfeat, const float* y_act, int32_t r, int32_t hw, int32_t c, float* dx) {
   if (!ctx || !dfeat || !y_act || !dx) return RADNET_ERR_ARG;
   if (c % 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "avgpool_bwd: c %% 4");
+  if (r < 1 || hw < 1 || c < 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "avgpool_bwd: bad r=%d hw=%d c=%d", r, hw, c);
   if ((long long)r * hw * (c / 4) >= (1ll << 31)) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "avgpool_bwd: too many work items (32-bit index arithmetic)");
   hipLaunchKernelGGL(avgpool_bwd_relu_kernel, dim3(grid_for((long long)r * hw * (c / 4))), dim3(256), 0, ctx->stream, dfeat, y_act, r, hw,
                      c / 4, dx);
@@ -610,6 +615,7 @@ extern "C" int radnet_avgpool_bwd_relu(radnet_ctx* ctx, const float* dfeat, cons
 extern "C" int radnet_dense_heads_fwd(radnet_ctx* ctx, const float* feat, int32_t r, int32_t k, const float* w, int32_t ldw, const float* b,
                                       int32_t nc, int32_t nreg, float* out_cls, float* out_regr) {
   if (!ctx || !feat || !w || !b || !out_cls || !out_regr) return RADNET_ERR_ARG;
+  if (r < 1 || k < 1 || nc < 1 || nreg < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "dense_heads: bad r=%d k=%d nc=%d nreg=%d", r, k, nc, nreg);
   if (nc + nreg > ldw || (ldw != 32 && ldw != 64)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "dense_heads: ldw=%d must be 32 or 64 and >= nc+nreg=%d", ldw, nc + nreg);
   if (ldw == 32) hipLaunchKernelGGL(dense_heads_fwd_kernel<32>, dim3(r), dim3(256), 0, ctx->stream, feat, k, w, b, nc, nreg, out_cls, out_regr);
   else hipLaunchKernelGGL(dense_heads_fwd_kernel<64>, dim3(r), dim3(256), 0, ctx->stream, feat, k, w, b, nc, nreg, out_cls, out_regr);
@@ -620,6 +626,8 @@ extern "C" int radnet_dense_heads_fwd(radnet_ctx* ctx, const float* feat, int32_
 extern "C" int radnet_dense_heads_bwd(radnet_ctx* ctx, const float* feat, const float* dz, int32_t r, int32_t k, const float* w, int32_t ldw,
                                       int32_t nout, float* dw, float* db, float* dfeat, int32_t accumulate) {
   if (!ctx || !feat || !dz || !w || !dw || !db || !dfeat) return RADNET_ERR_ARG;
+  if (r < 1 || k < 1 || nout < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "dense_heads_bwd: bad r=%d k=%d nout=%d", r, k, nout);
+  if (nout > ldw || (ldw != 32 && ldw != 64)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "dense_heads_bwd: ldw=%d must be 32 or 64 and >= nout=%d", ldw, nout);
   const size_t smem = (size_t)r * ldw * sizeof(float);
   if (smem > 64 * 1024) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "dense_heads_bwd: r=%d too large", r);
   hipLaunchKernelGGL(dense_heads_bwd_kernel, dim3(radnet_cdiv(k, 8)), dim3(256), smem, ctx->stream, feat, dz, r, k, w, ldw, nout, dw, db, dfeat, accumulate);
@@ -647,6 +655,7 @@ extern "C" int radnet_colsum(radnet_ctx* ctx, const float* g, int32_t m, int32_t
 extern "C" int radnet_rpn_loss(radnet_ctx* ctx, const float* pred, int32_t ld_pred, const float* y_cls, const float* y_regr, int32_t m,
                                int32_t a, int32_t bce_mode, float* dz, int32_t ld_dz, float* losses, double* scratch8) {
   if (!ctx || !pred || !y_cls || !y_regr || !dz || !losses || !scratch8) return RADNET_ERR_ARG;
+  if (m < 1 || a < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "rpn_loss: bad m=%d a=%d", m, a);
   if (ld_pred < 5 * a || ld_dz < 5 * a) RADNET_FAIL(ctx, RADNET_ERR_ARG, "rpn_loss: leading dims too small");
   RADNET_CHECK_HIP(ctx, hipMemsetAsync(scratch8, 0, 8 * sizeof(double), ctx->stream));
   hipLaunchKernelGGL(rpn_loss_sums_kernel, dim3(grid_for((long long)m * 5 * a, 256, 256)), dim3(256), 0, ctx->stream, pred, ld_pred, y_cls,
@@ -661,6 +670,7 @@ extern "C" int radnet_rpn_loss(radnet_ctx* ctx, const float* pred, int32_t ld_pr
 extern "C" int radnet_det_loss(radnet_ctx* ctx, const float* p_cls, const float* p_regr, const float* y1, const float* y2, int32_t r,
                                int32_t nc, int32_t nreg, float* dz, float* losses) {
   if (!ctx || !p_cls || !p_regr || !y1 || !y2 || !dz || !losses) return RADNET_ERR_ARG;
+  if (r < 1 || nc < 1 || nreg < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "det_loss: bad r=%d nc=%d nreg=%d", r, nc, nreg);
   hipLaunchKernelGGL(det_loss_kernel, dim3(1), dim3(256), 0, ctx->stream, p_cls, p_regr, y1, y2, r, nc, nreg, dz, losses);
   RADNET_CHECK_LAUNCH(ctx, "det_loss");
   return RADNET_OK;

@@ -240,6 +240,7 @@ extern "C" int radnet_head_tail_fwd(radnet_ctx* ctx, const float* y5, int32_t r,
                                     int32_t nc, int32_t nreg, float* feat, float* p_cls, float* p_regr, const float* y1, const float* y2,
                                     float* dz, float* losses, int32_t groups, const int32_t* group_live, void* scratch) {
   if (!ctx || !y5 || !w || !b || !feat || !p_cls || !p_regr) return RADNET_ERR_ARG;
+  if (r < 1 || hw < 1 || nc < 1 || nreg < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "head_tail: bad r=%d hw=%d nc=%d nreg=%d", r, hw, nc, nreg);
   if (nc + nreg > ldw || (ldw != 32 && ldw != 64)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "head_tail: ldw=%d must be 32 or 64 and >= nc+nreg=%d", ldw, nc + nreg);
   if (c % 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "head_tail: c %% 4");
   if (groups < 1 || r % groups || groups > 256) RADNET_FAIL(ctx, RADNET_ERR_ARG, "head_tail: %d RoIs in %d groups", r, groups);
