@@ -555,6 +555,42 @@ int radnet_png_unfilter_segments_u8(radnet_ctx* ctx, uint8_t* base, int64_t base
 int radnet_png_expand_bgr_u8(radnet_ctx* ctx, const uint8_t* stream, int32_t pass_h, int32_t pass_w, int32_t rowbytes, int32_t color_type,
                              int32_t bit_depth, const uint8_t* palette_bgr, uint8_t* dst, int32_t dst_h, int32_t dst_w, int32_t y0,
                              int32_t x0, int32_t dy, int32_t dx);
+/* ---- device images out to PNG files: the forward filter (csrc/png.hip) and rectangles (csrc/draw.hip) ------------------------------
+ * faster_rcnn/png.py writes the container and deflates on host threads; the per-byte work on the image runs here, where the image
+ * already is (RADNet.predict leaves it on the device). */
+/* The forward filter of the PNG specification (section 9), from a device image to the scanline stream radnet_png_unfilter_u8 consumes:
+ * stream receives h rows of 1 + w * channels bytes, the filter-type byte and then Filt(x) = x - predictor modulo 256 with the
+ * predictors stated at radnet_png_unfilter_u8 over the RAW bytes (a = bpp to the left, b = above, c = above-left; 0 left of the row
+ * and above row 0), bpp = channels.  img is h rows of pitch_bytes bytes (pitch_bytes >= w * channels; the padding is not read);
+ * channels == 3: a B, G, R image whose bytes are written as R, G, B (colour type 2, depth 8); channels == 1: the bytes as they are
+ * (colour type 0).  mode 0..4: that type for every row.  mode 5, adaptive: per row the type whose residual bytes v have the smallest
+ * sum of min(v, 256 - v); on a tie the lowest type.  The sums are integers; w * channels above 2^24 is RADNET_ERR_UNSUPPORTED so that
+ * they fit 32 bits.  `stream` needs no alignment (its rows start at every byte offset anyway) and must not overlap img.  A null
+ * pointer, h or w below 1, channels other than 1 and 3, a mode outside 0..5 or a short pitch is RADNET_ERR_ARG and nothing is
+ * launched.  One workgroup per row, one launch; every row reads raw bytes only, so rows do not wait for each other. */
+int radnet_png_filter_rows_u8(radnet_ctx* ctx, const uint8_t* img, int32_t h, int32_t w, int32_t channels, int64_t pitch_bytes, int32_t mode,
+                              uint8_t* stream);
+/* Rectangles painted into a uint8 [h][w][3] device image (rows pitch_bytes apart) IN PLACE.  The contract is this package's own:
+ *   the corners (x1, y1), (x2, y2) come in either order, as cv2.rectangle takes them, and are normalised to x1 <= x2, y1 <= y2;
+ *   thickness < 0 (cv2.FILLED): pixel (x, y) is painted iff x1 <= x <= x2 and y1 <= y <= y2;
+ *   thickness t > 0, hw = t / 2 (integer division): painted iff (x, y) lies in [x1 - hw, x2 + hw] x [y1 - hw, y2 + hw] and NOT
+ *     strictly inside (x1 + hw, x2 - hw) x (y1 + hw, y2 - hw); t = 1 is the one-pixel outline;
+ *   everything is clipped to the image, a rectangle wholly outside paints nothing; a painted pixel becomes (b, g, r).
+ * Against OpenCV: FILLED and t = 1 are cv2.rectangle's pixel sets; for t > 1 OpenCV joins four thick edges with round caps, so its
+ * outer corners are rounded where these are square.  Parity with cv2 itself is unpinned (absent here, as for the decoder).
+ * The result equals painting the rectangles one after the other in list order -- where they overlap the later one wins -- and is
+ * deterministic; a pixel no rectangle covers is not written (nor is the pitch padding).  rects_host and rects_dev hold the SAME
+ * table on the host and on the device (the caller uploads it; this entry copies nothing), as for radnet_png_unfilter_segments_u8.
+ * The host copy is validated before the launch: thickness != 0, b, g, r in 0..255, and pitch_bytes >= 3 * w; a violation is
+ * RADNET_ERR_ARG naming the entry's index and nothing is modified.  count == 0 is RADNET_OK without a launch, whatever the pointers.
+ * One launch: a workgroup per tile of 32 x 8 pixels, the table streamed through LDS in batches of RADNET_DRAW_RECT_BATCH entries,
+ * each batch culled against the tile; no atomics, no floating point. */
+typedef struct radnet_rect {
+  int32_t x1, y1, x2, y2, thickness, b, g, r;
+} radnet_rect; /* 32 bytes */
+#define RADNET_DRAW_RECT_BATCH 256
+int radnet_draw_rects_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int64_t pitch_bytes, const radnet_rect* rects_host,
+                         const radnet_rect* rects_dev, int32_t count);
 int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes);
 /* y = x * alpha (n floats); used to average gradients after all-reduce */
 int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha);

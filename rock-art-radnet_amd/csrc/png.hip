@@ -13,6 +13,8 @@
 // (rows, rowbytes, bpp); workgroups never wait for each other: radnet_png_unfilter_u8 launches one, and
 // radnet_png_unfilter_segments_u8 one per segment, where a segment (csrc/png_plan.cpp) is a run of rows whose first row does not
 // read the row above it (row 0 of a pass, or filter type 0 / 1), so no segment reads a byte another one writes.
+// The writer's half is the forward filter (radnet_png_filter_rows_u8, further down): a device image to the scanline stream, one
+// workgroup per row, the adaptive choice of a row's filter type by integer sums.
 #include "radnet_internal.h"
 
 namespace {
@@ -174,6 +176,72 @@ __global__ void __launch_bounds__(256) png_expand_kernel(const uint8_t* __restri
   d[2] = red;
 }
 
+// ---- forward filter (the writer's half) ------------------------------------------------------------------------------------------
+// A filtered byte depends on raw bytes only -- x, the byte bpp to the left (a), the one above (b), the one above-left (c) -- so
+// every row, and every byte of it, is independent: one workgroup per row, kFilterThreads consecutive stream bytes per sweep, one
+// byte per thread.  CH == 3 reads the B, G, R image as R, G, B.  The loads are byte loads of two image rows the caches hold; the
+// stores are byte stores to consecutive addresses (a stream row starts at any byte offset, so nothing wider is assumed).
+constexpr int kFilterThreads = 256;
+
+template <int CH>
+__device__ __forceinline__ void raw_neighbours(const uint8_t* __restrict__ row, const uint8_t* __restrict__ above, int i, int& x, int& a, int& b, int& c) {
+  int src = i;                                     // byte i of the stream row is byte src of the image row
+  if (CH == 3) {
+    const int px = i / 3;
+    src = 3 * px + 2 - (i - 3 * px);
+  }
+  x = row[src];
+  a = i >= CH ? row[src - CH] : 0;
+  b = above ? above[src] : 0;
+  c = (above && i >= CH) ? above[src - CH] : 0;
+}
+
+__device__ __forceinline__ int signed_size(int v) { return v > 128 ? 256 - v : v; }      // min(v, 256 - v) of a residual byte
+
+template <int CH>
+__global__ void __launch_bounds__(kFilterThreads) png_filter_rows_kernel(const uint8_t* __restrict__ img, int w, long long pitch, int mode,
+                                                                          uint8_t* __restrict__ stream) {
+  __shared__ unsigned wave_sums[kFilterThreads / 64][5];
+  const int r = (int)blockIdx.x, tid = (int)threadIdx.x, n = w * CH;
+  const uint8_t* row = img + (long long)r * pitch;
+  const uint8_t* above = r > 0 ? row - pitch : nullptr;
+  uint8_t* out = stream + (long long)r * (1 + (long long)n);
+  int ft = mode;
+  if (mode == 5) {
+    unsigned sums[5] = {0, 0, 0, 0, 0};            // at most 128 * 2^24 = 2^31 each
+    for (int i = tid; i < n; i += kFilterThreads) {
+      int x, a, b, c;
+      raw_neighbours<CH>(row, above, i, x, a, b, c);
+#pragma unroll
+      for (int f = 0; f < 5; ++f) sums[f] += (unsigned)signed_size((x - predictor(f, a, b, c)) & 255);
+    }
+#pragma unroll
+    for (int f = 0; f < 5; ++f) {
+      unsigned v = sums[f];
+      for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+      if ((tid & 63) == 0) wave_sums[tid >> 6][f] = v;
+    }
+    __syncthreads();
+    unsigned best = 0;
+    ft = 0;
+#pragma unroll
+    for (int f = 0; f < 5; ++f) {                  // every thread folds the same numbers: the choice is uniform
+      unsigned v = 0;
+      for (int k = 0; k < kFilterThreads / 64; ++k) v += wave_sums[k][f];
+      if (f == 0 || v < best) {                    // strictly smaller: on a tie the lowest type stays
+        best = v;
+        ft = f;
+      }
+    }
+  }
+  if (tid == 0) out[0] = (uint8_t)ft;
+  for (int i = tid; i < n; i += kFilterThreads) {
+    int x, a, b, c;
+    raw_neighbours<CH>(row, above, i, x, a, b, c);
+    out[1 + i] = (uint8_t)((x - predictor(ft, a, b, c)) & 255);
+  }
+}
+
 int channels_of(int color_type) {
   switch (color_type) {
     case 0: return 1;
@@ -280,5 +348,21 @@ extern "C" int radnet_png_expand_bgr_u8(radnet_ctx* ctx, const uint8_t* stream, 
   hipLaunchKernelGGL(png_expand_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, stream, pass_h, pass_w, rowbytes, color_type,
                      bit_depth, palette_bgr, dst, dst_w, y0, x0, dy, dx);
   RADNET_CHECK_LAUNCH(ctx, "png_expand_bgr_u8");
+  return RADNET_OK;
+}
+
+extern "C" int radnet_png_filter_rows_u8(radnet_ctx* ctx, const uint8_t* img, int32_t h, int32_t w, int32_t channels, int64_t pitch_bytes, int32_t mode,
+                                         uint8_t* stream) {
+  if (!ctx) return RADNET_ERR_ARG;
+  if (!img || !stream || h <= 0 || w <= 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_filter_rows: null image or stream, or an empty image (%d x %d)", h, w);
+  if (channels != 1 && channels != 3) RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_filter_rows: %d channels (1 or 3)", channels);
+  if (mode < 0 || mode > 5) RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_filter_rows: mode %d (0..4 fixed, 5 adaptive)", mode);
+  const int64_t rowbytes = (int64_t)w * channels;
+  if (rowbytes > (1 << 24)) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "png_filter_rows: %lld bytes per row (at most 2^24)", (long long)rowbytes);
+  if (pitch_bytes < rowbytes) RADNET_FAIL(ctx, RADNET_ERR_ARG, "png_filter_rows: a pitch of %lld bytes for rows of %lld bytes", (long long)pitch_bytes, (long long)rowbytes);
+  const dim3 grid((unsigned)h), block(kFilterThreads);
+  if (channels == 3) hipLaunchKernelGGL(png_filter_rows_kernel<3>, grid, block, 0, ctx->stream, img, w, (long long)pitch_bytes, mode, stream);
+  else hipLaunchKernelGGL(png_filter_rows_kernel<1>, grid, block, 0, ctx->stream, img, w, (long long)pitch_bytes, mode, stream);
+  RADNET_CHECK_LAUNCH(ctx, "png_filter_rows_u8");
   return RADNET_OK;
 }

@@ -3,6 +3,7 @@
     RADNet(C, model_rpn, model_detector, preprocess_func)              RADNet.py:33-41
     .predict(images) -> [{'class','prob','x1','y1','x2','y2'}, ...]     RADNet.py:502-718
     .predict_from_path(path)                                           RADNet.py:482-500
+    .draw_detections(img, dets) / .write_predictions(dets, img, dir)   predict.py:90-181 (boxes and files; no text labels)
     .format_img / .apply_spatial_pyramid_pooling / .final_nms / .get_real_coordinates
     load_radnet(config_path)                                           RADNet.py:721-775
 
@@ -461,6 +462,84 @@ class RADNet():
         else:
             images = [utils_io.get_image(img_path, C.img_types, random_type=False, to_host=to_host)]
         return self.predict(images)
+
+    # ---- the outputs of the predict driver (predict.py:90-181) -----------------------------------------------
+    PREDICTION_MAPS = (("all_predictions.png", (255, 255, 255), None),
+                       ("boat_predictions.png", (28, 26, 228), ("boat",)),
+                       ("human_predictions.png", (184, 126, 55), ("human",)),
+                       ("other_predictions.png", (0, 127, 255), lambda name: name not in ("boat", "human")))
+
+    def draw_detections(self, img, dets, color=(255, 255, 255), thickness=8, classes=None, inplace=False):
+        """cv2.rectangle(img, (x1, y1), (x2, y2), color, thickness) for every detection of `dets` (predict's dicts) that `classes`
+        selects -- None: all; a collection of class names; or a predicate on the name --, in list order, on the device: one
+        radnet_draw_rects_u8 launch (include/radnet_hip.h states the pixel set: OpenCV's for thickness 1 and FILLED, square
+        outer corners where OpenCV rounds them for thicker outlines).  img: a uint8 [H][W][3] (B, G, R) contiguous cuda tensor,
+        or a NumPy array, which is uploaded.  Returns the device image: a clone unless inplace.  The reference's text labels
+        (cv2.getTextSize / putText and the two label boxes, predict.py:109-115) are NOT drawn: the Hershey glyph tables exist only
+        inside OpenCV, which is not part of this build."""
+        if classes is None:
+            chosen = list(dets)
+        elif callable(classes):
+            chosen = [d for d in dets if classes(d['class'])]
+        else:
+            names = set(classes)
+            chosen = [d for d in dets if d['class'] in names]
+        b, g, r = (int(v) for v in color)
+        rects = [(int(d['x1']), int(d['y1']), int(d['x2']), int(d['y2']), int(thickness), b, g, r) for d in chosen]
+        return draw_rects_device(img, rects, inplace=inplace)
+
+    def write_predictions(self, dets, img, out_dir):
+        """What predict.py:96-181 writes for the detections of one scan, into out_dir: all_predictions.png (every detection in
+        (255, 255, 255)), boat_predictions.png (boats, (28, 26, 228)), human_predictions.png (humans, (184, 126, 55)),
+        other_predictions.png (every other class, (0, 127, 255)) -- each `img` (the map to annotate: a device image or a NumPy
+        array, uploaded once) with 8-pixel outlines from draw_detections, encoded by png.encode_device -- and predictions.json,
+        the label / confidence / x1 / y1 / x2 / y2 dicts with indent=4.  The reference's text labels are left out (see
+        draw_detections).  Returns the five paths."""
+        import json
+        import os
+        from . import png
+        if isinstance(img, np.ndarray):
+            import torch
+            png.check_writable(img)
+            img = torch.from_numpy(np.ascontiguousarray(img)).cuda()
+        os.makedirs(out_dir, exist_ok=True)
+        paths = []
+        for name, color, classes in self.PREDICTION_MAPS:
+            drawn = self.draw_detections(img, dets, color=color, thickness=8, classes=classes, inplace=False)
+            paths.append(os.path.join(out_dir, name))
+            with open(paths[-1], "wb") as f:
+                f.write(png.encode_device(drawn))
+        predictions = [{'label': d['class'], 'confidence': float(d['prob']), 'x1': int(d['x1']), 'y1': int(d['y1']), 'x2': int(d['x2']),
+                        'y2': int(d['y2'])} for d in dets]
+        paths.append(os.path.join(out_dir, "predictions.json"))
+        with open(paths[-1], "w") as outfile:
+            json.dump(predictions, outfile, indent=4)
+        return paths
+
+
+RECT = np.dtype([(k, np.int32) for k in ("x1", "y1", "x2", "y2", "thickness", "b", "g", "r")])      # radnet_rect, 32 bytes
+
+
+def draw_rects_device(img, rects, inplace=False, ctx=None):
+    """radnet_draw_rects_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): `rects` is a sequence of
+    (x1, y1, x2, y2, thickness, b, g, r), painted in order (thickness < 0 fills).  Returns the device image, a clone unless inplace.
+    The table goes up on its own, 32 bytes per rectangle; an empty list launches nothing.  ctx and the stream rules are
+    png.decode_device's."""
+    import torch
+    from . import augmentation_device as AD
+    if isinstance(img, np.ndarray):
+        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
+    check_device_image(img)
+    table = np.array([tuple(int(v) for v in r) for r in rects], RECT).reshape(-1)
+    producer = torch.cuda.current_stream()
+    with AD.feed_stream(ctx) as (ctx, side):
+        if side is not None:
+            side.wait_stream(producer)
+        out = img if inplace else img.clone()
+        if len(table):
+            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
+            ctx.call("radnet_draw_rects_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, table_dev, len(table))
+    return AD.hand_over(out, side)
 
 
 def resize_cubic(img, new_w, new_h, to_host=True, ctx=None):

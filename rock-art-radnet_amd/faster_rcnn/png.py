@@ -18,6 +18,13 @@ Adam7.  Output rules: grey is replicated to three channels, depths 1 / 2 / 4 sca
 (an index beyond the PLTE length gives 0); alpha channels and tRNS are dropped, not blended; 16-bit samples keep their high byte
 (libpng's strip_16); no gamma, no sBIT, no background.
 
+Writing (assemble, encode_device): the reference writes its annotated maps with cv2.imwrite (predict.py:118-181).  Device: ONE
+radnet_png_filter_rows_u8 launch turns the device image into the scanline stream (a fixed filter type or the adaptive choice per
+row); the stream comes down into one pinned buffer.  Host: the stream is cut into byte ranges, each range is deflated raw on a host
+thread (zlib releases the GIL) and ends in a sync flush, the last one in the final block, and the pieces are concatenated behind one
+zlib header and in front of one Adler-32 -- a valid zlib stream, the mirror image of decode_device_many.  8-bit colour type 2 or 0,
+not interlaced; no ancillary chunks.  The file's bytes are a function of the image and the arguments, not of the thread count.
+
 This restates libpng's documented transforms as OpenCV requests them for IMREAD_COLOR.  Parity with cv2 itself is UNPINNED: cv2 is
 not importable in this build, so no test compares against it (tests/png_cases.py holds an independent encoder and a NumPy statement
 of the rules above).  A file this module refuses raises ValueError naming the cause, where cv2.imdecode returns None.
@@ -272,3 +279,126 @@ def decode_device_many(datas, ctx=None, workers=None):
 def imdecode_color(data):
     """cv2.imdecode(data, cv2.IMREAD_COLOR) for a PNG file's bytes: decode_device, downloaded to a NumPy array."""
     return decode_device(data).cpu().numpy()
+
+
+# ---- writing ------------------------------------------------------------------------------------------------------------------------
+FILTER_MODES = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}      # `mode` of radnet_png_filter_rows_u8
+STRATEGIES = {"default": zlib.Z_DEFAULT_STRATEGY, "filtered": zlib.Z_FILTERED, "huffman": zlib.Z_HUFFMAN_ONLY, "rle": zlib.Z_RLE,
+              "fixed": zlib.Z_FIXED}
+IDAT_MAX = 0x7fffffff      # a chunk's length field
+
+
+def _chunk_bytes(kind, payload=b""):
+    return struct.pack(">I", len(payload)) + kind + payload + struct.pack(">I", zlib.crc32(payload, zlib.crc32(kind)))
+
+
+def _zlib_header(level):
+    """CMF / FLG for deflate with a 32 KiB window; FLEVEL as zlib derives it from the level, FCHECK so that the pair divides by 31."""
+    level = 6 if level == -1 else level
+    flevel = 0 if level in (0, 1) else 1 if level < 6 else 2 if level == 6 else 3
+    head = (0x78 << 8) | (flevel << 6)
+    return struct.pack(">H", head + (31 - head % 31) % 31)
+
+
+def _deflate_piece(piece, level, strategy, last):
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    return c.compress(piece) + c.flush(zlib.Z_FINISH if last else zlib.Z_SYNC_FLUSH)
+
+
+def _workers(pieces, workers):
+    workers = min(pieces, MANY_DEFAULT_WORKERS) if workers is None else int(workers)
+    return max(1, min(workers, MANY_MAX_WORKERS))
+
+
+def assemble(stream_bytes, width, height, color_type, level=1, strategy="rle", workers=None, chunk_bytes=1 << 20):
+    """The PNG file of a filtered scanline stream (8 bits per sample, colour type 0 or 2, not interlaced): signature, IHDR, one
+    IDAT, IEND.  The stream is cut into ranges of chunk_bytes bytes; each is deflated raw (zlib.compressobj(level, DEFLATED, -15, 9,
+    strategy)) on one of `workers` host threads (default min(pieces, 8), at most 16) and ends in Z_SYNC_FLUSH, the last in
+    Z_FINISH; the IDAT holds the zlib header, the pieces in order and zlib.adler32 of the whole stream.  No device is involved.
+    The bytes depend on the arguments other than `workers`; the inflated stream depends on stream_bytes alone."""
+    import concurrent.futures
+    view = memoryview(stream_bytes).cast("B")
+    width, height, level, chunk_bytes = int(width), int(height), int(level), int(chunk_bytes)
+    if color_type not in (0, 2):
+        raise ValueError("PNG: the writer takes colour type 0 or 2, not %r" % (color_type,))
+    if width < 1 or height < 1 or width > 0x7fffffff or height > 0x7fffffff:
+        raise ValueError("PNG: illegal size %d x %d" % (width, height))
+    if len(view) != height * (1 + width * CHANNELS[color_type]):
+        raise ValueError("PNG: a stream of %d bytes for %d x %d pixels of colour type %d" % (len(view), width, height, color_type))
+    if not -1 <= level <= 9:
+        raise ValueError("PNG: deflate level %d" % level)
+    if chunk_bytes < 1:
+        raise ValueError("PNG: chunk_bytes %d" % chunk_bytes)
+    if isinstance(strategy, str):
+        if strategy not in STRATEGIES:
+            raise ValueError("PNG: unknown deflate strategy %r (one of %s)" % (strategy, ", ".join(sorted(STRATEGIES))))
+        strategy = STRATEGIES[strategy]
+    starts = range(0, len(view), chunk_bytes)
+    jobs = [(view[s:s + chunk_bytes], level, strategy, s + chunk_bytes >= len(view)) for s in starts]
+    workers = _workers(len(jobs), workers)
+    if workers == 1:
+        pieces = [_deflate_piece(*job) for job in jobs]
+        adler = zlib.adler32(view)
+    else:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
+            check = pool.submit(zlib.adler32, view)
+            pieces = list(pool.map(lambda job: _deflate_piece(*job), jobs))
+            adler = check.result()
+    idat = b"".join([_zlib_header(level)] + pieces + [struct.pack(">I", adler & 0xffffffff)])
+    if len(idat) > IDAT_MAX:
+        raise ValueError("PNG: an IDAT chunk of %d bytes (at most 2^31 - 1)" % len(idat))
+    ihdr = struct.pack(">IIBBBBB", width, height, 8, color_type, 0, 0, 0)
+    return b"".join([SIGNATURE, _chunk_bytes(b"IHDR", ihdr), _chunk_bytes(b"IDAT", idat), _chunk_bytes(b"IEND")])
+
+
+def _filter_mode(filter):
+    if isinstance(filter, str):
+        if filter not in FILTER_MODES:
+            raise ValueError("PNG: unknown filter %r (one of %s, or 0..4)" % (filter, ", ".join(FILTER_MODES)))
+        return FILTER_MODES[filter]
+    if int(filter) not in range(5):
+        raise ValueError("PNG: filter type %r (0..4, or a name)" % (filter,))
+    return int(filter)
+
+
+def check_writable(img):
+    """(height, width, channels) of an image encode_device takes: uint8, [H][W][3] or [H][W], not empty, contiguous if on the device."""
+    if str(img.dtype).split(".")[-1] != "uint8":
+        raise TypeError("PNG: the writer takes a uint8 image, not %s" % (img.dtype,))
+    shape = tuple(int(v) for v in img.shape)
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+        raise ValueError("PNG: the writer takes an image [H][W][3] (B, G, R) or [H][W], not shape %s" % (shape,))
+    if shape[0] < 1 or shape[1] < 1:
+        raise ValueError("PNG: the writer takes no empty image, shape %s" % (shape,))
+    if not isinstance(img, np.ndarray) and not img.is_contiguous():
+        raise ValueError("PNG: a device image must be contiguous (strides %s for shape %s)" % (img.stride(), shape))
+    return shape[0], shape[1], 1 if len(shape) == 2 else 3
+
+
+def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None, chunk_bytes=1 << 20, ctx=None):
+    """The PNG file (bytes) of a contiguous uint8 cuda tensor [H][W][3] (B, G, R; written as 8-bit RGB) or [H][W] (8-bit grey); a
+    NumPy array is uploaded first -- there is no CPU filter path, as there is no CPU reconstruction.  filter: "adaptive" (per row
+    the type with the smallest sum of |signed residual|, the lowest on a tie), a fixed type 0..4 or its name.  One
+    radnet_png_filter_rows_u8 launch, one download of the stream into a pinned buffer, then assemble() with level / strategy
+    (OpenCV's imwrite defaults: 1, Z_RLE) / workers / chunk_bytes.  ctx and the stream rules are decode_device's; a worker thread's
+    own stream waits for the stream that is current at the call, where the image is taken to be ready."""
+    import torch
+    from . import augmentation_device as AD
+    mode = _filter_mode(filter)
+    h, w, channels = check_writable(img)
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(np.ascontiguousarray(img)).cuda()
+    elif not img.is_cuda:
+        raise TypeError("PNG: the writer takes a cuda tensor or a NumPy array, not a tensor on %s" % (img.device,))
+    n = h * (1 + w * channels)
+    producer = torch.cuda.current_stream()
+    with AD.feed_stream(ctx) as (ctx, side):
+        if side is not None:
+            side.wait_stream(producer)
+            img.record_stream(side)
+        dev = torch.empty(n, dtype=torch.uint8, device="cuda")
+        ctx.call("radnet_png_filter_rows_u8", img, h, w, channels, w * channels, mode, dev)
+        staged = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        staged.copy_(dev, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    return assemble(staged.numpy(), w, h, 2 if channels == 3 else 0, level, strategy, workers, chunk_bytes)

@@ -136,3 +136,15 @@ class DeviceImageLoader:
         img = png.decode_device(buf) if self.decode is None else self.decode(buf)
         self._insert(key, img)
         return img
+
+
+def imwrite(path, img, **kw):
+    """cv2.imwrite(path, img) for a PNG map: png.encode_device(img, **kw) written to `path` (a cuda tensor stays where it is; only
+    the filtered stream comes down).  Only the .png suffix is accepted; returns True like cv2.imwrite."""
+    path = os.fspath(path)
+    if os.path.splitext(path)[1].lower() != ".png":
+        raise ValueError("imwrite: only PNG files are written, not %r" % (os.path.splitext(path)[1] or path,))
+    data = png.encode_device(img, **kw)
+    with open(path, "wb") as f:
+        f.write(data)
+    return True

@@ -264,6 +264,8 @@ def load_library():
         "radnet_png_plan_segments": (C.c_int, [vp, i64, i32, i32, i32, vp, i32]),
         "radnet_png_unfilter_segments_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32]),
         "radnet_png_expand_bgr_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32]),
+        "radnet_png_filter_rows_u8": (C.c_int, [vp, vp, i32, i32, i32, i64, i32, vp]),
+        "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
         "radnet_fill_zero": (C.c_int, [vp, vp, u64]),
         "radnet_copy_bytes": (C.c_int, [vp, vp, vp, C.c_uint64]),
         "radnet_program_run": (C.c_int, [vp, C.POINTER(Op), i32]),
