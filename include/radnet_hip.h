@@ -591,6 +591,38 @@ typedef struct radnet_rect {
 #define RADNET_DRAW_RECT_BATCH 256
 int radnet_draw_rects_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int64_t pitch_bytes, const radnet_rect* rects_host,
                          const radnet_rect* rects_dev, int32_t count);
+/* An ORDERED list of rectangles and text runs painted into the same kind of image in place, in one launch: what one labelled
+ * detection needs (outline, label box, label) without a launch per step and with the later entry on top.
+ *   kind RADNET_PRIM_RECT: (x1, y1), (x2, y2) the corners, a the thickness, b unused, bgr = b | g << 8 | r << 16.  The pixel set is
+ *     exactly radnet_draw_rects_u8's, FILLED (a < 0) included.
+ *   kind RADNET_PRIM_TEXT: (x1, y1) the left end of the baseline (cv2.putText's org), x2 = s the integer scale in
+ *     1..RADNET_DRAW_TEXT_MAX_SCALE, y2 = 0, a the offset and b the length n of the run in the character pool `chars`, bgr the
+ *     colour.  The font is this package's own (csrc/draw_font.h; radnet_draw_glyph_rows): glyphs of 5 columns x 8 rows of dots,
+ *     advance 6.  Dot (c, r) of character k covers the pixels x1 + (6k + c) * s .. + s - 1 by y1 - 7s + r * s .. + s - 1: the cap
+ *     rows 0..6 lie in [y1 - 7s, y1 - 1], the descender row 7 in [y1, y1 + s - 1].  Only set dots are painted (a glyph's
+ *     background and the gap column are transparent); n = 0 paints nothing.  Neither glyphs nor metrics are OpenCV's Hershey
+ *     fonts; parity with cv2.putText is unpinned, as for the outlines.
+ * Everything is clipped to the image; arithmetic that can leave int32 is done in 64 bits.  The result equals painting the list
+ * entry by entry in order -- the later entry wins -- and is deterministic; a pixel no entry covers is not written (nor is the
+ * pitch padding).  prims_host / prims_dev and chars_host / chars_dev hold the SAME table and the SAME pool on the host and on the
+ * device (the caller uploads them; this entry copies nothing).  The host copies are validated before the launch; a violation is
+ * RADNET_ERR_ARG naming the entry's index and nothing is modified: an unknown kind, a rectangle of thickness 0, a scale outside
+ * 1..RADNET_DRAW_TEXT_MAX_SCALE, y2 != 0 on a text entry, a negative offset or length, a + b > n_chars, a byte of a referenced
+ * run outside 0x20..0x7E, bgr with bits above 24; likewise pitch_bytes < 3 * w.  The pool pointers may be null when n_chars is 0.
+ * count == 0 is RADNET_OK without a launch, whatever the pointers.
+ * One launch with the scheme of radnet_draw_rects_u8 (tiles of 32 x 8 pixels, batches of RADNET_DRAW_RECT_BATCH entries culled
+ * against the tile); a run is one entry whatever its length; no atomics, no floating point. */
+typedef struct radnet_prim {
+  int32_t kind, x1, y1, x2, y2, a, b, bgr;
+} radnet_prim; /* 32 bytes */
+#define RADNET_PRIM_RECT 0
+#define RADNET_PRIM_TEXT 1
+#define RADNET_DRAW_TEXT_MAX_SCALE 64
+int radnet_draw_list_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int64_t pitch_bytes, const radnet_prim* prims_host,
+                        const radnet_prim* prims_dev, int32_t count, const uint8_t* chars_host, const uint8_t* chars_dev, int32_t n_chars);
+/* Host only (no context, no device, like radnet_png_plan_segments): the 8 row bytes of the glyph of `code`, top row first; the dot
+ * of column c is (row >> (4 - c)) & 1.  RADNET_ERR_ARG for a code outside 0x20..0x7E or a null pointer (nothing is written). */
+int radnet_draw_glyph_rows(int32_t code, uint8_t rows[8]);
 int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes);
 /* y = x * alpha (n floats); used to average gradients after all-reduce */
 int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha);

@@ -469,14 +469,19 @@ class RADNet():
                        ("human_predictions.png", (184, 126, 55), ("human",)),
                        ("other_predictions.png", (0, 127, 255), lambda name: name not in ("boat", "human")))
 
-    def draw_detections(self, img, dets, color=(255, 255, 255), thickness=8, classes=None, inplace=False):
+    def draw_detections(self, img, dets, color=(255, 255, 255), thickness=8, classes=None, inplace=False, labels=False, label_scale=3):
         """cv2.rectangle(img, (x1, y1), (x2, y2), color, thickness) for every detection of `dets` (predict's dicts) that `classes`
         selects -- None: all; a collection of class names; or a predicate on the name --, in list order, on the device: one
         radnet_draw_rects_u8 launch (include/radnet_hip.h states the pixel set: OpenCV's for thickness 1 and FILLED, square
         outer corners where OpenCV rounds them for thicker outlines).  img: a uint8 [H][W][3] (B, G, R) contiguous cuda tensor,
-        or a NumPy array, which is uploaded.  Returns the device image: a clone unless inplace.  The reference's text labels
-        (cv2.getTextSize / putText and the two label boxes, predict.py:109-115) are NOT drawn: the Hershey glyph tables exist only
-        inside OpenCV, which is not part of this build."""
+        or a NumPy array, which is uploaded.  Returns the device image: a clone unless inplace.
+        labels=True adds the reference's `class: percent` label to every chosen detection (predict.py:107-115), all of it as ONE
+        ordered radnet_draw_list_u8 launch: per detection the outline, then label = '{}: {}'.format(class, int(100 * prob)) with
+        ((tw, th), baseline) = text_size(label, label_scale) and org = (x1, y1): the label box from (x1 - 5, y1 + baseline - 5) to
+        (x1 + tw + 5, y1 - th - 5) as a black outline of thickness 1 and then FILLED white, and the text at org in black.  The
+        glyphs and the metrics are the package's own dot-matrix font (csrc/draw_font.h), not OpenCV's Hershey fonts, which this
+        build does not have: label_scale=3 gives capitals of 21 pixels against Hershey's roughly 22 at fontScale 1.  Parity with
+        cv2 is unpinned for the text as it is for the outlines."""
         if classes is None:
             chosen = list(dets)
         elif callable(classes):
@@ -485,16 +490,32 @@ class RADNet():
             names = set(classes)
             chosen = [d for d in dets if d['class'] in names]
         b, g, r = (int(v) for v in color)
-        rects = [(int(d['x1']), int(d['y1']), int(d['x2']), int(d['y2']), int(thickness), b, g, r) for d in chosen]
-        return draw_rects_device(img, rects, inplace=inplace)
+        if not labels:
+            rects = [(int(d['x1']), int(d['y1']), int(d['x2']), int(d['y2']), int(thickness), b, g, r) for d in chosen]
+            return draw_rects_device(img, rects, inplace=inplace)
+        prims = []
+        for d in chosen:
+            x1, y1 = int(d['x1']), int(d['y1'])
+            label = '{}: {}'.format(d['class'], int(100 * d['prob']))
+            (tw, th), baseline = text_size(label, label_scale)
+            box = (x1 - 5, y1 + baseline - 5, x1 + tw + 5, y1 - th - 5)
+            prims += [("rect", x1, y1, int(d['x2']), int(d['y2']), int(thickness), b, g, r),
+                      ("rect",) + box + (1, 0, 0, 0),
+                      ("rect",) + box + (-1, 255, 255, 255),
+                      ("text", x1, y1, label, int(label_scale), 0, 0, 0)]
+        return draw_list_device(img, prims, inplace=inplace)
 
-    def write_predictions(self, dets, img, out_dir):
+    LABELLED_MAPS = ("all_predictions.png", "other_predictions.png")      # predict.py:109-115 and 172-178
+
+    def write_predictions(self, dets, img, out_dir, labels=False, label_scale=3):
         """What predict.py:96-181 writes for the detections of one scan, into out_dir: all_predictions.png (every detection in
         (255, 255, 255)), boat_predictions.png (boats, (28, 26, 228)), human_predictions.png (humans, (184, 126, 55)),
         other_predictions.png (every other class, (0, 127, 255)) -- each `img` (the map to annotate: a device image or a NumPy
         array, uploaded once) with 8-pixel outlines from draw_detections, encoded by png.encode_device -- and predictions.json,
-        the label / confidence / x1 / y1 / x2 / y2 dicts with indent=4.  The reference's text labels are left out (see
-        draw_detections).  Returns the five paths."""
+        the label / confidence / x1 / y1 / x2 / y2 dicts with indent=4.  labels=True draws the reference's text labels on the two
+        maps that carry them there, all_predictions.png and other_predictions.png (draw_detections(labels=True): the package's
+        own font at label_scale, not OpenCV's glyphs or metrics; unpinned against cv2); the boat and human maps stay outlines
+        only.  The default leaves the labels out and writes the same bytes as before they existed.  Returns the five paths."""
         import json
         import os
         from . import png
@@ -505,7 +526,10 @@ class RADNet():
         os.makedirs(out_dir, exist_ok=True)
         paths = []
         for name, color, classes in self.PREDICTION_MAPS:
-            drawn = self.draw_detections(img, dets, color=color, thickness=8, classes=classes, inplace=False)
+            if labels and name in self.LABELLED_MAPS:
+                drawn = self.draw_detections(img, dets, color=color, thickness=8, classes=classes, inplace=False, labels=True, label_scale=label_scale)
+            else:
+                drawn = self.draw_detections(img, dets, color=color, thickness=8, classes=classes, inplace=False)
             paths.append(os.path.join(out_dir, name))
             with open(paths[-1], "wb") as f:
                 f.write(png.encode_device(drawn))
@@ -540,6 +564,70 @@ def draw_rects_device(img, rects, inplace=False, ctx=None):
             table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
             ctx.call("radnet_draw_rects_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, table_dev, len(table))
     return AD.hand_over(out, side)
+
+
+PRIM = np.dtype([(k, np.int32) for k in ("kind", "x1", "y1", "x2", "y2", "a", "b", "bgr")])      # radnet_prim, 32 bytes
+PRIM_RECT, PRIM_TEXT = 0, 1                                                                      # RADNET_PRIM_RECT, RADNET_PRIM_TEXT
+FONT_CAP_ROWS, FONT_ADVANCE = 7, 6      # the metrics of csrc/draw_font.h in dots (the glyph table itself stands only there)
+
+
+def text_size(text, scale=3):
+    """((w, h), baseline) of a text run of radnet_draw_list_u8, the shape cv2.getTextSize returns: w = max(0, 6 * len - 1) * scale
+    (the last character's gap column is not counted), h = 7 * scale (the cap rows above the baseline), baseline = scale (the
+    descender row).  The metrics of the package's own font, not Hershey's."""
+    n, scale = len(label_bytes(text)), int(scale)
+    return (max(0, FONT_ADVANCE * n - 1) * scale, FONT_CAP_ROWS * scale), scale
+
+
+def label_bytes(text):
+    """The bytes a text entry draws for `text`: ASCII, every byte outside 0x20..0x7E (what the font has) replaced by b'?'."""
+    return bytes(c if 0x20 <= c <= 0x7E else 0x3F for c in str(text).encode("ascii", "replace"))
+
+
+def draw_list_device(img, prims, inplace=False, ctx=None):
+    """radnet_draw_list_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): `prims` is a sequence of
+    ("rect", x1, y1, x2, y2, thickness, b, g, r) and ("text", x, y, string, scale, b, g, r) -- (x, y) the left end of the baseline,
+    the string through label_bytes --, painted in order in one launch, the later entry on top (include/radnet_hip.h states the
+    pixel sets).  Returns the device image, a clone unless inplace.  The table (32 bytes per entry) and the character pool go up
+    on their own; an empty list launches nothing.  ctx and the stream rules are draw_rects_device's."""
+    import torch
+    from . import augmentation_device as AD
+    if isinstance(img, np.ndarray):
+        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
+    check_device_image(img)
+    rows, pool = [], bytearray()
+    for p in prims:
+        if p[0] == "rect":
+            _, x1, y1, x2, y2, thickness, b, g, r = p
+            rows.append((PRIM_RECT, int(x1), int(y1), int(x2), int(y2), int(thickness), 0, _bgr(b, g, r)))
+        elif p[0] == "text":
+            _, x, y, string, scale, b, g, r = p
+            run = label_bytes(string)
+            rows.append((PRIM_TEXT, int(x), int(y), int(scale), 0, len(pool), len(run), _bgr(b, g, r)))
+            pool += run
+        else:
+            raise ValueError("draw_list_device: entry %d is %r, neither 'rect' nor 'text'" % (len(rows), p[0]))
+    table = np.array(rows, PRIM).reshape(-1)
+    chars = np.frombuffer(bytes(pool), np.uint8)
+    producer = torch.cuda.current_stream()
+    with AD.feed_stream(ctx) as (ctx, side):
+        if side is not None:
+            side.wait_stream(producer)
+        out = img if inplace else img.clone()
+        if len(table):
+            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
+            chars_dev = torch.from_numpy(chars.copy()).cuda() if len(chars) else None
+            ctx.call("radnet_draw_list_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, table_dev, len(table),
+                     chars.ctypes.data if len(chars) else None, chars_dev, len(chars))
+    return AD.hand_over(out, side)
+
+
+def _bgr(b, g, r):
+    """b | g << 8 | r << 16 of three colour values in 0..255 (radnet_prim.bgr)."""
+    b, g, r = int(b), int(g), int(r)
+    if not (0 <= b <= 255 and 0 <= g <= 255 and 0 <= r <= 255):
+        raise ValueError("draw_list_device: the colour (%d, %d, %d)" % (b, g, r))
+    return b | g << 8 | r << 16
 
 
 def resize_cubic(img, new_w, new_h, to_host=True, ctx=None):

@@ -266,6 +266,8 @@ def load_library():
         "radnet_png_expand_bgr_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32]),
         "radnet_png_filter_rows_u8": (C.c_int, [vp, vp, i32, i32, i32, i64, i32, vp]),
         "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
+        "radnet_draw_list_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
+        "radnet_draw_glyph_rows": (C.c_int, [i32, vp]),
         "radnet_fill_zero": (C.c_int, [vp, vp, u64]),
         "radnet_copy_bytes": (C.c_int, [vp, vp, vp, C.c_uint64]),
         "radnet_program_run": (C.c_int, [vp, C.POINTER(Op), i32]),
@@ -296,6 +298,16 @@ def load_library():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def glyph_rows(code):
+    """The 8 row bytes of the draw list's glyph of `code` (radnet_draw_glyph_rows: host only, no context, no device), top row
+    first; the dot of column c is (row >> (4 - c)) & 1.  The table stands in csrc/draw_font.h and nowhere else."""
+    rows = (C.c_uint8 * 8)()
+    rc = load_library().radnet_draw_glyph_rows(int(code), rows)
+    if rc != 0:
+        raise RadnetError("radnet_draw_glyph_rows: no glyph for the code 0x%02X (the font has 0x20..0x7E)" % int(code))
+    return bytes(rows)
 
 
 def _ptr(t):
