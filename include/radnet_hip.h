@@ -392,8 +392,9 @@ int radnet_roi_targets(radnet_ctx* ctx, const int64_t* rois, int32_t n, const do
                        double max_overlap, const double* regr_std_host4, int32_t bg_class, uint8_t* keep, int32_t* cls,
                        int32_t* box, double* t, double* iou, const int32_t* n_dev);
 /* ^ cls is -1 for dropped RoIs.  n_dev (optional device int32): only the first min(*n_dev, n) rows are labelled,
- *   so the NMS count never has to travel to the host between the two kernels. */
-/* Build the detector batch for `r` selected RoIs: rois_out fp32 [r][4], y1 [r][nc], y2 [r][8(nc-1)]. */
+ *   so the NMS count never has to travel to the host between the two kernels.
+ *   max_overlap must be > 0: the call is refused otherwise (an RoI that overlaps nothing would be foreground without a box). */
+/* Build the detector batch for `r` selected RoIs: rois_out fp32 [r][4], y1 [r][nc], y2 [r][8(nc-1)].  r = 0 writes nothing. */
 int radnet_roi_batch_pack(radnet_ctx* ctx, const int32_t* sel, int32_t r, const int32_t* cls, const int32_t* box,
                           const double* t, int32_t nc, int32_t bg_class, float* rois_out, float* y1, float* y2);
 

@@ -22,6 +22,7 @@ namespace {
 
 __device__ __forceinline__ unsigned int sortable_bits(float f) {
   unsigned int u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;      // -0.0 == +0.0 for NumPy's sort: one key, so the tie rule (higher index first) decides
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -66,8 +67,11 @@ __global__ void __launch_bounds__(256) decode_kernel(DecodeArgs g, double4* __re
   const double x1 = fmax(0.0, x), y1 = fmax(0.0, y);
   x2 = fmin((double)(g.cols - 1), x2);
   y2 = fmin((double)(g.rows - 1), y2);
-  // rpn.py:163: drop where (x1 - x2 >= 0) | (y1 - y2 >= 0); NaN boxes (the reference would assert) are dropped too
-  const bool ok = (x1 < x2) && (y1 < y2);
+  // rpn.py:163: drop where (x1 - x2 >= 0) | (y1 - y2 >= 0).  A NaN or infinite decoded x, y, w or h (a NaN or infinite delta, an
+  // overflowing exp: the reference asserts on the NaN box) is dropped too: fmax / fmin return the operand that is not NaN, so
+  // the clip above would otherwise turn such a box into a valid full-width one.  Finite boxes are not touched.
+  const bool finite = isfinite(x) && isfinite(y) && isfinite(w) && isfinite(h);
+  const bool ok = finite && (x1 < x2) && (y1 < y2);
   unsigned long long key = 0ull;
   if (ok) key = ((unsigned long long)sortable_bits(p[a]) << 32) | (unsigned int)idx;
   keys[idx] = key;

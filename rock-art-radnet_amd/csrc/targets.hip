@@ -300,6 +300,8 @@ extern "C" int radnet_roi_targets(radnet_ctx* ctx, const int64_t* rois, int32_t 
                                   double max_overlap, const double* regr_std_host4, int32_t bg_class, uint8_t* keep, int32_t* cls,
                                   int32_t* box, double* t, double* iou, const int32_t* n_dev) {
   if (!ctx || !rois || !keep || !cls || !box || !t || !iou || !regr_std_host4) return RADNET_ERR_ARG;
+  // best starts at 0.0: with max_overlap <= 0 an RoI that overlaps nothing would pass the foreground test with no best box
+  if (!(max_overlap > 0.0)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "roi_targets: max_overlap %g must be > 0", max_overlap);
   if (n <= 0) return RADNET_OK;
   if (g > 0 && (!gt || !gt_cls)) return RADNET_ERR_ARG;
   RoiArgs a{};
@@ -315,6 +317,7 @@ extern "C" int radnet_roi_targets(radnet_ctx* ctx, const int64_t* rois, int32_t 
 extern "C" int radnet_roi_batch_pack(radnet_ctx* ctx, const int32_t* sel, int32_t r, const int32_t* cls, const int32_t* box, const double* t,
                                      int32_t nc, int32_t bg_class, float* rois_out, float* y1, float* y2) {
   if (!ctx || !sel || !cls || !box || !t || !rois_out || !y1 || !y2) return RADNET_ERR_ARG;
+  if (r == 0) return RADNET_OK;      // an empty batch: nothing to write, and a grid of zero blocks is no valid launch
   hipLaunchKernelGGL(roi_batch_pack_kernel, dim3(r), dim3(64), 0, ctx->stream, sel, r, cls, box, t, nc, bg_class, rois_out, y1, y2);
   RADNET_CHECK_LAUNCH(ctx, "roi_batch_pack");
   return RADNET_OK;
