@@ -571,6 +571,73 @@ int radnet_png_expand_bgr_u8(radnet_ctx* ctx, const uint8_t* stream, int32_t pas
  * launched.  One workgroup per row, one launch; every row reads raw bytes only, so rows do not wait for each other. */
 int radnet_png_filter_rows_u8(radnet_ctx* ctx, const uint8_t* img, int32_t h, int32_t w, int32_t channels, int64_t pitch_bytes, int32_t mode,
                               uint8_t* stream);
+/* ---- deflate of the scanline stream on the device (csrc/deflate.hip, csrc/deflate_plan.cpp): run-length tokens, one Huffman code ---
+ * What zlib's Z_RLE strategy does (matches at distance 1 only), restated so that a position's token depends on nothing but the run
+ * it sits in.  THE TOKEN RULE: the stream of n bytes is cut into chunks of RADNET_DEFLATE_CHUNK bytes; each chunk becomes one
+ * deflate block, one "piece".  Inside a chunk, runs are additionally cut at multiples of RADNET_DEFLATE_TILE bytes (counted from the
+ * chunk's start), so a token never needs bytes beyond its tile.  A maximal run of L equal bytes b inside a tile is coded as
+ *   the literal b; then floor((L - 1) / 258) matches of length 258 at distance 1; then the rest r = (L - 1) mod 258: one match of
+ *   length r at distance 1 if r >= 3, else r literals b.
+ * The rule is deterministic: tests/deflate_cases.py states it in Python and the kernels are compared with it byte for byte.
+ * A code is a table of 286 literal/length symbols (RFC 1951, 3.2.5): `bits` the canonical code as RFC 1951 3.2.2 numbers it (its most
+ * significant bit goes into the stream first), `length` its length in bits, 0 for a symbol that does not occur. */
+#define RADNET_DEFLATE_CHUNK 65536
+#define RADNET_DEFLATE_TILE 4096
+#define RADNET_DEFLATE_SYMBOLS 286
+#define RADNET_DEFLATE_HEADER_MAX_BITS 2048
+typedef struct radnet_deflate_code {
+  uint16_t bits, length;
+} radnet_deflate_code; /* 4 bytes */
+/* First pass over the stream (device, n bytes): one workgroup per chunk tokenises by the rule above and ADDS the counts of the
+ * literal/length symbols, one end-of-block (256) per chunk included, to hist[286] (device, uint32; the caller zeroes it; integer
+ * atomics, so the result does not depend on the order).  adler_parts (device, uint64 [chunks][2], 8-byte aligned) receives per chunk
+ * of len bytes the two exact sums  sum(byte[i])  and  sum((len - i) * byte[i]),  i counted from the chunk's start: the host combines
+ * them into the Adler-32 of the stream without seeing it.  chunks = ceil(n / RADNET_DEFLATE_CHUNK).  A null pointer or n < 1 is
+ * RADNET_ERR_ARG, n >= 2^32 (a count could leave 32 bits) RADNET_ERR_UNSUPPORTED; nothing is launched then. */
+int radnet_deflate_rle_scan_u8(radnet_ctx* ctx, const uint8_t* stream, int64_t n, uint32_t* hist, uint64_t* adler_parts);
+/* Second pass: one workgroup per chunk writes piece c to pieces + c * piece_cap (device) and its size in bytes to sizes[c] (device,
+ * uint32).  A piece holds, from its bit 0 on (bits fill a byte from its least significant end, RFC 1951 3.1.1):
+ *   header_bits[0 .. header_nbits): the caller's block header -- BFINAL = 0, BTYPE and, for a dynamic block, the code description;
+ *   the tokens of the chunk: Huffman codes most significant bit first, a length symbol's extra bits least significant bit first,
+ *     and after every match the distance code of distance 1: dist_nbits zero bits (1 for radnet_deflate_build_code's table, 5 for
+ *     the fixed code);
+ *   end-of-block;
+ *   then a sync flush, the empty stored block: 000, zero bits up to the byte, 00 00 FF FF.  The LAST piece instead has BFINAL = 1
+ *     (bit 0 of the piece is set) and zero bits up to the byte, no stored block.
+ * Bit offsets come from a workgroup prefix sum of per-position bit counts.  Bits no code covers are zero; no byte at or beyond
+ * sizes[c] is written.  `code` (286 entries) and header_bits (ceil(header_nbits / 8) bytes) are HOST memory and travel with the
+ * launch; the code is data, so the fixed code of RFC 1951 3.2.6 is one more table (header 3 bits, BTYPE 01) and any legal table
+ * works.  The caller answers for a table that gives a length to every symbol radnet_deflate_rle_scan_u8 counted.
+ * piece_cap must be at least radnet_deflate_piece_cap(code, header_nbits, dist_nbits).  RADNET_ERR_ARG and nothing is launched: a
+ * null pointer, n < 1, a code length outside 0..15, bits that do not fit the length, a zero length for end-of-block (256),
+ * header_nbits outside 3..RADNET_DEFLATE_HEADER_MAX_BITS, dist_nbits outside 0..15, a short piece_cap; n >= 2^32 is
+ * RADNET_ERR_UNSUPPORTED. */
+int radnet_deflate_rle_emit_u8(radnet_ctx* ctx, const uint8_t* stream, int64_t n, const radnet_deflate_code* code, const uint8_t* header_bits,
+                               int32_t header_nbits, int32_t dist_nbits, uint8_t* pieces, int64_t piece_cap, uint32_t* sizes);
+/* Host only (csrc/deflate_plan.cpp; no context, no device): the bound a piece cannot pass,
+ *   ceil(header_nbits / 8) + ceil(w * RADNET_DEFLATE_CHUNK / 8) + 16,
+ * w = the larger of the longest code length and ceil((longest length-symbol code + 5 extra bits + dist_nbits) / 3): a literal costs
+ * at most the first per byte, a match covers three bytes at least; from a longest code of 9 bits on (the fixed code, every code of
+ * an image) w is the longest code length.  The 16 hold end-of-block and the sync flush.  Negative (RADNET_ERR_ARG) for the table,
+ * header_nbits and dist_nbits that radnet_deflate_rle_emit_u8 refuses. */
+int64_t radnet_deflate_piece_cap(const radnet_deflate_code* code, int32_t header_nbits, int32_t dist_nbits);
+/* The pieces one behind the other: out[0 .. total) (device) = piece 0, piece 1, ... by an exclusive prefix sum of sizes[0 .. count),
+ * and *total (device, uint64) = their sum.  The host reads the 8 bytes of total and then downloads exactly that many.  Nothing is
+ * written at or beyond out + out_cap: if *total > out_cap the copy is cut there and the caller sees it from total.  One launch, a
+ * workgroup per piece; each sums the sizes in front of its own (count^2 / 2 reads of 4 bytes in all, from the caches).  A null
+ * pointer, count < 1, piece_cap < 1 or out_cap < 0 is RADNET_ERR_ARG, count > 65536 (more than n < 2^32 gives) RADNET_ERR_UNSUPPORTED. */
+int radnet_deflate_pack(radnet_ctx* ctx, const uint8_t* pieces, int64_t piece_cap, const uint32_t* sizes, int32_t count, uint8_t* out,
+                        int64_t out_cap, uint64_t* total);
+/* Host only (csrc/deflate_plan.cpp; no context, no device, like radnet_png_plan_segments): from the 286 counts of
+ * radnet_deflate_rle_scan_u8 a literal/length code of at most 15 bits per symbol and the dynamic block header that describes it.
+ * A symbol with a count gets a length; end-of-block always does; with fewer than two such symbols literal 0 (or 1) joins them, so
+ * the code is COMPLETE -- the Kraft sum of 2^-length is exactly 1 -- as zlib's inflate demands.  Lengths are Huffman's, and where
+ * the tree is deeper than 15, shortened to 15 and repaired to a Kraft sum of 1; codes are canonical (RFC 1951 3.2.2).
+ * header receives ceil(*header_nbits / 8) bytes, unused bits zero: BFINAL 0, BTYPE 10, HLIT 29, HDIST 0, HCLEN 15; the code-length
+ * code gives 4 bits to each of its symbols 0..15 and none to 16..18 (complete); then the 286 lengths and the one distance length,
+ * 1 for distance symbol 0, four bits each: 1222 bits.  A match's distance code is therefore one zero bit (dist_nbits = 1).
+ * A null pointer or header_cap < 153 is RADNET_ERR_ARG and nothing is written. */
+int radnet_deflate_build_code(const uint32_t* hist, radnet_deflate_code* code, uint8_t* header, int32_t header_cap, int32_t* header_nbits);
 /* Rectangles painted into a uint8 [h][w][3] device image (rows pitch_bytes apart) IN PLACE.  The contract is this package's own:
  *   the corners (x1, y1), (x2, y2) come in either order, as cv2.rectangle takes them, and are normalised to x1 <= x2, y1 <= y2;
  *   thickness < 0 (cv2.FILLED): pixel (x, y) is painted iff x1 <= x <= x2 and y1 <= y <= y2;

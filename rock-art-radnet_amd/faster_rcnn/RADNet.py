@@ -507,7 +507,7 @@ class RADNet():
 
     LABELLED_MAPS = ("all_predictions.png", "other_predictions.png")      # predict.py:109-115 and 172-178
 
-    def write_predictions(self, dets, img, out_dir, labels=False, label_scale=3):
+    def write_predictions(self, dets, img, out_dir, labels=False, label_scale=3, deflate="host", huffman="dynamic"):
         """What predict.py:96-181 writes for the detections of one scan, into out_dir: all_predictions.png (every detection in
         (255, 255, 255)), boat_predictions.png (boats, (28, 26, 228)), human_predictions.png (humans, (184, 126, 55)),
         other_predictions.png (every other class, (0, 127, 255)) -- each `img` (the map to annotate: a device image or a NumPy
@@ -515,7 +515,9 @@ class RADNet():
         the label / confidence / x1 / y1 / x2 / y2 dicts with indent=4.  labels=True draws the reference's text labels on the two
         maps that carry them there, all_predictions.png and other_predictions.png (draw_detections(labels=True): the package's
         own font at label_scale, not OpenCV's glyphs or metrics; unpinned against cv2); the boat and human maps stay outlines
-        only.  The default leaves the labels out and writes the same bytes as before they existed.  Returns the five paths."""
+        only.  The default leaves the labels out and writes the same bytes as before they existed.  deflate / huffman go to
+        png.encode_device as they are (deflate="device": the four streams are compressed on the device and only the files' bytes
+        come down); the defaults are the host deflate and the bytes it always wrote.  Returns the five paths."""
         import json
         import os
         from . import png
@@ -525,6 +527,7 @@ class RADNet():
             img = torch.from_numpy(np.ascontiguousarray(img)).cuda()
         os.makedirs(out_dir, exist_ok=True)
         paths = []
+        encoder = {} if (deflate, huffman) == ("host", "dynamic") else dict(deflate=deflate, huffman=huffman)
         for name, color, classes in self.PREDICTION_MAPS:
             if labels and name in self.LABELLED_MAPS:
                 drawn = self.draw_detections(img, dets, color=color, thickness=8, classes=classes, inplace=False, labels=True, label_scale=label_scale)
@@ -532,7 +535,7 @@ class RADNet():
                 drawn = self.draw_detections(img, dets, color=color, thickness=8, classes=classes, inplace=False)
             paths.append(os.path.join(out_dir, name))
             with open(paths[-1], "wb") as f:
-                f.write(png.encode_device(drawn))
+                f.write(png.encode_device(drawn, **encoder))
         predictions = [{'label': d['class'], 'confidence': float(d['prob']), 'x1': int(d['x1']), 'y1': int(d['y1']), 'x2': int(d['x2']),
                         'y2': int(d['y2'])} for d in dets]
         paths.append(os.path.join(out_dir, "predictions.json"))

@@ -24,6 +24,11 @@ row); the stream comes down into one pinned buffer.  Host: the stream is cut int
 thread (zlib releases the GIL) and ends in a sync flush, the last one in the final block, and the pieces are concatenated behind one
 zlib header and in front of one Adler-32 -- a valid zlib stream, the mirror image of decode_device_many.  8-bit colour type 2 or 0,
 not interlaced; no ancillary chunks.  The file's bytes are a function of the image and the arguments, not of the thread count.
+encode_device(deflate="device") keeps the stream on the device instead (csrc/deflate.hip): radnet_deflate_rle_scan_u8 counts the
+symbols of a run-length tokenisation (what Z_RLE does: matches at distance 1 only) and sums the Adler-32 parts, the host builds one
+Huffman code from the 286 counts (huffman_code) or takes the fixed one, radnet_deflate_rle_emit_u8 writes one deflate block per
+RADNET_DEFLATE_CHUNK bytes, radnet_deflate_pack moves the blocks together, and only the compressed bytes come down
+(assemble_pieces puts the container round them).  The default, deflate="host", is the path above, byte for byte.
 
 This restates libpng's documented transforms as OpenCV requests them for IMREAD_COLOR.  Parity with cv2 itself is UNPINNED: cv2 is
 not importable in this build, so no test compares against it (tests/png_cases.py holds an independent encoder and a NumPy statement
@@ -375,16 +380,200 @@ def check_writable(img):
     return shape[0], shape[1], 1 if len(shape) == 2 else 3
 
 
-def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None, chunk_bytes=1 << 20, ctx=None):
+# ---- deflate on the device ---------------------------------------------------------------------------------------------------------
+DEFLATE_CODE = np.dtype([("bits", np.uint16), ("length", np.uint16)])      # radnet_deflate_code, 4 bytes
+DEFLATE_SYMBOLS = 286
+HuffmanCode = collections.namedtuple("HuffmanCode", "code header header_nbits dist_nbits")      # the arguments of radnet_deflate_rle_emit_u8
+
+
+def _deflate_constant(name):
+    from radnet_hip.lib import header_constant
+    return header_constant(name)
+
+
+def huffman_code(hist):
+    """The literal/length code of an image from the 286 counts of radnet_deflate_rle_scan_u8 and the dynamic block header that
+    describes it (radnet_deflate_build_code: host only, no device): HuffmanCode(code, header, header_nbits, dist_nbits) with code a
+    structured array of 286 (bits, length), lengths of at most 15 bits and Kraft sum 1, header the block header's bytes (BFINAL 0,
+    BTYPE 10, ...; header_nbits bits of them count) and dist_nbits = 1, the distance code of the one-symbol distance table."""
+    import ctypes
+    from radnet_hip import lib as L
+    hist = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if hist.size != DEFLATE_SYMBOLS:
+        raise ValueError("PNG: a histogram of %d counts (the literal/length alphabet has %d)" % (hist.size, DEFLATE_SYMBOLS))
+    code = np.zeros(DEFLATE_SYMBOLS, DEFLATE_CODE)
+    header = np.zeros(_deflate_constant("RADNET_DEFLATE_HEADER_MAX_BITS") // 8, np.uint8)
+    nbits = ctypes.c_int32(0)
+    rc = L.load_library().radnet_deflate_build_code(hist.ctypes.data, code.ctypes.data, header.ctypes.data, header.size, ctypes.byref(nbits))
+    if rc != 0:
+        raise ValueError("PNG: radnet_deflate_build_code failed (%d)" % rc)
+    return HuffmanCode(code, header[:(nbits.value + 7) // 8].tobytes(), nbits.value, 1)
+
+
+def fixed_code():
+    """The fixed code of RFC 1951, 3.2.6 as a HuffmanCode: lengths 8 / 9 / 7 / 8, canonical; the header is BFINAL 0, BTYPE 01; a
+    distance code has 5 bits."""
+    code = np.zeros(DEFLATE_SYMBOLS, DEFLATE_CODE)
+    s = np.arange(DEFLATE_SYMBOLS)
+    code["length"] = np.where(s < 144, 8, np.where(s < 256, 9, np.where(s < 280, 7, 8)))
+    code["bits"] = np.where(s < 144, 0x30 + s, np.where(s < 256, 0x190 + s - 144, np.where(s < 280, s - 256, 0xC0 + s - 280)))
+    return HuffmanCode(code, b"\x02", 3, 5)
+
+
+def adler32_of_parts(parts, n):
+    """The Adler-32 of a stream of n bytes from radnet_deflate_rle_scan_u8's parts, per chunk of len bytes at offset s the sums
+    S1 = sum(byte[i]) and S2 = sum((len - i) * byte[i]):  a = 1 + sum(S1),  b = n + sum(S2 + (n - s - len) * S1),  both mod 65521."""
+    chunk = _deflate_constant("RADNET_DEFLATE_CHUNK")
+    a, b = 1, int(n)
+    for c, (s1, s2) in enumerate(np.asarray(parts, np.uint64).reshape(-1, 2).tolist()):
+        start = c * chunk
+        a += s1
+        b += s2 + (n - start - min(chunk, n - start)) * s1
+    return ((b % 65521) << 16) | (a % 65521)
+
+
+def _gf2_times(mat, vec):
+    out, i = 0, 0
+    while vec:
+        if vec & 1:
+            out ^= mat[i]
+        vec >>= 1
+        i += 1
+    return out
+
+
+def crc32_combine(crc1, crc2, len2):
+    """zlib.crc32(a + b) from crc1 = zlib.crc32(a), crc2 = zlib.crc32(b) and len2 = len(b): zlib's crc32_combine (the operator that
+    appends len2 zero bytes, by repeated squaring over GF(2)), which the standard library does not export."""
+    if len2 <= 0:
+        return crc1
+    square = lambda mat: [_gf2_times(mat, mat[n]) for n in range(32)]      # noqa: E731
+    odd = [0xedb88320] + [1 << n for n in range(31)]      # the operator for one zero bit
+    even = square(odd)                                     # two
+    odd = square(even)                                     # four
+    while True:
+        even = square(odd)
+        if len2 & 1:
+            crc1 = _gf2_times(even, crc1)
+        len2 >>= 1
+        if not len2:
+            break
+        odd = square(even)
+        if len2 & 1:
+            crc1 = _gf2_times(odd, crc1)
+        len2 >>= 1
+        if not len2:
+            break
+    return crc1 ^ crc2
+
+
+def _crc32_threads(view, crc, workers=MANY_DEFAULT_WORKERS, least=1 << 20):
+    """zlib.crc32(view, crc) with the buffer cut into at most `workers` ranges of at least `least` bytes, each summed on a host thread
+    (zlib releases the GIL) and the sums joined by crc32_combine."""
+    import concurrent.futures
+    n = len(view)
+    ranges = max(1, min(workers, n // least))
+    if ranges == 1:
+        return zlib.crc32(view, crc)
+    step = -(-n // ranges)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=ranges) as pool:
+        sums = list(pool.map(lambda s: zlib.crc32(view[s:s + step]), range(0, n, step)))
+    for k, part in enumerate(sums):
+        crc = crc32_combine(crc, part, min(step, n - k * step))
+    return crc
+
+
+def assemble_pieces(packed, adler, width, height, color_type):
+    """The PNG file round a deflate stream made elsewhere (8 bits per sample, colour type 0 or 2, not interlaced): signature, IHDR,
+    one IDAT holding the zlib header 78 01, `packed` (raw deflate blocks, the last one final) and the Adler-32 `adler` of what they
+    inflate to, IEND.  Nothing is inflated or checked here but the sizes.  `packed` is read twice and copied once: the chunk's
+    CRC-32 is summed over ranges of it on up to 8 host threads, then the file is joined."""
+    width, height, adler = int(width), int(height), int(adler)
+    if color_type not in (0, 2):
+        raise ValueError("PNG: the writer takes colour type 0 or 2, not %r" % (color_type,))
+    if width < 1 or height < 1 or width > 0x7fffffff or height > 0x7fffffff:
+        raise ValueError("PNG: illegal size %d x %d" % (width, height))
+    if not 0 <= adler <= 0xffffffff:
+        raise ValueError("PNG: an Adler-32 of %d" % adler)
+    view = memoryview(packed).cast("B")
+    if len(view) + 6 > IDAT_MAX:
+        raise ValueError("PNG: an IDAT chunk of %d bytes (at most 2^31 - 1)" % (len(view) + 6))
+    head, tail = b"IDAT" + _zlib_header(1), struct.pack(">I", adler)
+    crc = zlib.crc32(tail, _crc32_threads(view, zlib.crc32(head)))
+    ihdr = struct.pack(">IIBBBBB", width, height, 8, color_type, 0, 0, 0)
+    return b"".join([SIGNATURE, _chunk_bytes(b"IHDR", ihdr), struct.pack(">I", len(view) + 6), head, view, tail, struct.pack(">I", crc), _chunk_bytes(b"IEND")])
+
+
+def deflate_device(dev, ctx, huffman="dynamic"):
+    """(packed, adler): the raw deflate blocks (bytes-like, in a pinned buffer) and the Adler-32 of the uint8 cuda tensor `dev` of n
+    bytes, on the radnet context ctx whose stream is current: scan, ONE small download (286 counts, the Adler parts), the code
+    (huffman_code, or fixed_code for huffman="fixed"), emit, pack, the 8 bytes of the total, ONE download of exactly that many."""
+    import torch
+    from radnet_hip import lib as L
+    n = int(dev.numel())
+    chunk = _deflate_constant("RADNET_DEFLATE_CHUNK")
+    chunks = -(-n // chunk)
+    scan = torch.zeros(DEFLATE_SYMBOLS * 4 + chunks * 16, dtype=torch.uint8, device="cuda")      # 1144 bytes: the parts stand 8-aligned
+    ctx.call("radnet_deflate_rle_scan_u8", dev, n, scan, scan.data_ptr() + DEFLATE_SYMBOLS * 4)
+    scan_host = torch.empty(scan.numel(), dtype=torch.uint8, pin_memory=True)
+    scan_host.copy_(scan, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    hist = scan_host.numpy()[:DEFLATE_SYMBOLS * 4].view(np.uint32)
+    adler = adler32_of_parts(scan_host.numpy()[DEFLATE_SYMBOLS * 4:].view(np.uint64), n)
+    hc = fixed_code() if huffman == "fixed" else huffman_code(hist)
+    piece_cap = int(L.load_library().radnet_deflate_piece_cap(hc.code.ctypes.data, hc.header_nbits, hc.dist_nbits))
+    if piece_cap < 0:
+        raise ValueError("PNG: radnet_deflate_piece_cap failed (%d)" % piece_cap)
+    pieces = torch.empty(chunks * piece_cap, dtype=torch.uint8, device="cuda")
+    sizes = torch.empty(chunks, dtype=torch.int32, device="cuda")
+    header = np.frombuffer(hc.header, np.uint8)
+    ctx.call("radnet_deflate_rle_emit_u8", dev, n, hc.code.ctypes.data, header.ctypes.data, hc.header_nbits, hc.dist_nbits, pieces, piece_cap, sizes)
+    # the bits of all tokens follow from the counts (a match: at most 5 extra bits and the distance code); per piece the header,
+    # the flush and the padding come on top
+    counts = hist.astype(np.int64)
+    token_bits = int((counts * hc.code["length"].astype(np.int64)).sum()) + int(counts[257:].sum()) * (5 + hc.dist_nbits)
+    out_cap = (token_bits + 7) // 8 + chunks * ((hc.header_nbits + 7) // 8 + 16)
+    out = torch.empty(out_cap, dtype=torch.uint8, device="cuda")
+    total = torch.empty(1, dtype=torch.int64, device="cuda")
+    ctx.call("radnet_deflate_pack", pieces, piece_cap, sizes, chunks, out, out_cap, total)
+    total_host = torch.empty(1, dtype=torch.int64, pin_memory=True)
+    total_host.copy_(total, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    size = int(total_host[0])
+    if size > out_cap:
+        raise RuntimeError("PNG: the deflate pieces hold %d bytes, more than the %d their counts allow" % (size, out_cap))
+    packed = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+    packed.copy_(out[:size], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return packed.numpy(), adler
+
+
+HOST_DEFLATE_DEFAULTS = dict(level=1, strategy="rle", workers=None, chunk_bytes=1 << 20)
+
+
+def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None, chunk_bytes=1 << 20, ctx=None, deflate="host", huffman="dynamic"):
     """The PNG file (bytes) of a contiguous uint8 cuda tensor [H][W][3] (B, G, R; written as 8-bit RGB) or [H][W] (8-bit grey); a
     NumPy array is uploaded first -- there is no CPU filter path, as there is no CPU reconstruction.  filter: "adaptive" (per row
     the type with the smallest sum of |signed residual|, the lowest on a tie), a fixed type 0..4 or its name.  One
     radnet_png_filter_rows_u8 launch, one download of the stream into a pinned buffer, then assemble() with level / strategy
     (OpenCV's imwrite defaults: 1, Z_RLE) / workers / chunk_bytes.  ctx and the stream rules are decode_device's; a worker thread's
-    own stream waits for the stream that is current at the call, where the image is taken to be ready."""
+    own stream waits for the stream that is current at the call, where the image is taken to be ready.
+    deflate="device": the stream stays on the device and is deflated there (deflate_device: run-length tokens, one Huffman code per
+    image for huffman="dynamic", RFC 1951's fixed code for huffman="fixed"); only the compressed bytes come down and
+    assemble_pieces wraps them.  The file inflates to the same stream as the host path's but its bytes differ.  level, strategy,
+    workers and chunk_bytes belong to the host deflate: any of them off its default together with deflate="device" is a ValueError."""
     import torch
     from . import augmentation_device as AD
     mode = _filter_mode(filter)
+    if deflate not in ("host", "device"):
+        raise ValueError("PNG: deflate=%r (\"host\" or \"device\")" % (deflate,))
+    if huffman not in ("dynamic", "fixed"):
+        raise ValueError("PNG: huffman=%r (\"dynamic\" or \"fixed\")" % (huffman,))
+    if deflate == "device":
+        given = dict(level=level, strategy=strategy, workers=workers, chunk_bytes=chunk_bytes)
+        off = sorted(k for k, v in given.items() if v != HOST_DEFLATE_DEFAULTS[k])
+        if off:
+            raise ValueError("PNG: %s belong%s to the host deflate and cannot be set with deflate=\"device\"" % (", ".join(off), "s" if len(off) == 1 else ""))
     h, w, channels = check_writable(img)
     if isinstance(img, np.ndarray):
         img = torch.from_numpy(np.ascontiguousarray(img)).cuda()
@@ -398,6 +587,9 @@ def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None,
             img.record_stream(side)
         dev = torch.empty(n, dtype=torch.uint8, device="cuda")
         ctx.call("radnet_png_filter_rows_u8", img, h, w, channels, w * channels, mode, dev)
+        if deflate == "device":
+            packed, adler = deflate_device(dev, ctx, huffman)
+            return assemble_pieces(packed, adler, w, h, 2 if channels == 3 else 0)
         staged = torch.empty(n, dtype=torch.uint8, pin_memory=True)
         staged.copy_(dev, non_blocking=True)
         torch.cuda.current_stream().synchronize()

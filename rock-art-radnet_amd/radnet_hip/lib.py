@@ -265,6 +265,11 @@ def load_library():
         "radnet_png_unfilter_segments_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32]),
         "radnet_png_expand_bgr_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32]),
         "radnet_png_filter_rows_u8": (C.c_int, [vp, vp, i32, i32, i32, i64, i32, vp]),
+        "radnet_deflate_rle_scan_u8": (C.c_int, [vp, vp, i64, vp, vp]),
+        "radnet_deflate_rle_emit_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, vp, i64, vp]),
+        "radnet_deflate_piece_cap": (i64, [vp, i32, i32]),
+        "radnet_deflate_pack": (C.c_int, [vp, vp, i64, vp, i32, vp, i64, vp]),
+        "radnet_deflate_build_code": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32)]),
         "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
         "radnet_draw_list_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
         "radnet_draw_glyph_rows": (C.c_int, [i32, vp]),
