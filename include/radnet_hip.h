@@ -257,7 +257,8 @@ int radnet_conv_wgrad_bf16(radnet_ctx* ctx, const radnet_conv_desc* d, int32_t m
 int32_t radnet_dgrad_bf16_pick_split(int64_t p, int32_t c, int32_t kd);
 int32_t radnet_wgrad_bf16_pick_split(int64_t m, int32_t n, int32_t k);
 
-/* out[n] (+)= sum_m g[m][n] * gscale[n]   (bias gradients) */
+/* out[n] (+)= sum_m g[m][n] * gscale[n]   (bias gradients).  g is [m][ld] with ld >= n (columns n..ld are never read); gscale may be
+ * null.  accumulate = 0 zeroes out[0..n) first.  RADNET_ERR_ARG, nothing zeroed or launched, for m < 1, n < 1 or ld < n. */
 int radnet_colsum(radnet_ctx* ctx, const float* g, int32_t m, int32_t n, int32_t ld, const float* gscale,
                   float* out, int32_t accumulate);
 
@@ -410,7 +411,7 @@ int64_t radnet_host_choice_round(double* live_p, int64_t* live_idx, int64_t* n_l
 
 /* ---- small utilities ---------------------------------------------------------------------------- */
 /* uint8 BGR HWC image -> fp32 NHWC with `cpad` channels (zeros beyond 3), minus the caffe BGR means
- * (RADNet.py:83-87 / utils.py:468-472 with keras 'caffe' preprocess_input). */
+ * (RADNet.py:83-87 / utils.py:468-472 with keras 'caffe' preprocess_input).  cpad >= 3; RADNET_ERR_ARG for h < 1 or w < 1. */
 int radnet_preprocess_bgr(radnet_ctx* ctx, const uint8_t* img, int32_t h, int32_t w, int32_t cpad, float* out);
 /* dst[0..bytes) = src[0..bytes) by a kernel on the context's stream; either side may be pinned host memory (hipHostMalloc /
  * torch pin_memory: mapped into the device's address space).  The step's small transfers between host and device (image panel
@@ -692,18 +693,22 @@ int radnet_draw_list_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int
  * of column c is (row >> (4 - c)) & 1.  RADNET_ERR_ARG for a code outside 0x20..0x7E or a null pointer (nothing is written). */
 int radnet_draw_glyph_rows(int32_t code, uint8_t rows[8]);
 int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes);
-/* y = x * alpha (n floats); used to average gradients after all-reduce */
+/* y = x * alpha (n floats); used to average gradients after all-reduce.  n = 0 launches nothing; RADNET_ERR_ARG for n < 0. */
 int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha);
 /* out[i] = a[i]*b[i] + c[i]: refreshes the folded epilogue shift (BN scale * conv bias + BN shift,
- * FixedBatchNormalization.py:59-85) of the trainable head convs after an optimizer step. */
+ * FixedBatchNormalization.py:59-85) of the trainable head convs after an optimizer step.  out may be a, b or c.  n = 0 launches
+ * nothing; RADNET_ERR_ARG for n < 0. */
 int radnet_affine_vec(radnet_ctx* ctx, float* out, const float* a, const float* b, const float* c, int64_t n);
 /* Input gradient of a stride-s 1x1 convolution (resnet50.py:100,111: the first 1x1 and the shortcut of every
  * conv_block).  The GEMM runs on the compact grid -- radnet_conv_dgrad with a descriptor whose input geometry is
  * the OUTPUT grid (h = oh, w = ow, stride 1) -- and this pass places its rows at (oh*s, ow*s) of the full
- * [nb][h][w][c] gradient, zeros elsewhere, then applies the producer's ReLU mask (mask > 0) if given. */
+ * [nb][h][w][c] gradient, zeros elsewhere, then applies the producer's ReLU mask (mask > 0) if given.  Every element of dst is
+ * written.  RADNET_ERR_ARG for nb < 1, oh < 1, ow < 1, c < 4, c % 4, stride < 1 or a compact grid that does not fit:
+ * (oh - 1) * stride >= h or (ow - 1) * stride >= w; RADNET_ERR_UNSUPPORTED for 2^31 float4 elements or more. */
 int radnet_scatter_strided(radnet_ctx* ctx, const float* src, int32_t nb, int32_t oh, int32_t ow, int32_t c, int32_t stride,
                            int32_t h, int32_t w, const float* mask, float* dst);
-/* g[i] = act[i] > 0 ? g[i] : 0 -- ReLU backward where it cannot ride a GEMM epilogue (VGG16 head, vgg16.py:98-101) */
+/* g[i] = act[i] > 0 ? g[i] : 0 -- ReLU backward where it cannot ride a GEMM epilogue (VGG16 head, vgg16.py:98-101).  A NaN
+ * activation gives 0.  n = 0 launches nothing; RADNET_ERR_ARG for n < 0. */
 int radnet_relu_mask(radnet_ctx* ctx, float* g, const float* act, int64_t n);
 
 /* ==== layer programs and composed entry points (rpn_forward, train_step, predict_tile, allreduce_grads) ====

@@ -638,6 +638,7 @@ extern "C" int radnet_dense_heads_bwd(radnet_ctx* ctx, const float* feat, const 
 extern "C" int radnet_colsum(radnet_ctx* ctx, const float* g, int32_t m, int32_t n, int32_t ld, const float* gscale, float* out,
                              int32_t accumulate) {
   if (!ctx || !g || !out) return RADNET_ERR_ARG;
+  if (m < 1 || n < 1 || ld < n) RADNET_FAIL(ctx, RADNET_ERR_ARG, "colsum: bad m=%d n=%d ld=%d", m, n, ld);
   if (!accumulate) RADNET_CHECK_HIP(ctx, hipMemsetAsync(out, 0, (size_t)n * sizeof(float), ctx->stream));
   int rows_per_block = 128;
   float* partials = nullptr;
@@ -678,6 +679,7 @@ extern "C" int radnet_det_loss(radnet_ctx* ctx, const float* p_cls, const float*
 
 extern "C" int radnet_preprocess_bgr(radnet_ctx* ctx, const uint8_t* img, int32_t h, int32_t w, int32_t cpad, float* out) {
   if (!ctx || !img || !out || cpad < 3) return RADNET_ERR_ARG;
+  if (h < 1 || w < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "preprocess: empty image %dx%d", h, w);
   hipLaunchKernelGGL(preprocess_kernel, dim3(grid_for((long long)h * w)), dim3(256), 0, ctx->stream, img, (long long)h * w, cpad, out);
   RADNET_CHECK_LAUNCH(ctx, "preprocess");
   return RADNET_OK;
@@ -713,6 +715,8 @@ extern "C" int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes) {
 
 extern "C" int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha) {
   if (!ctx || !x) return RADNET_ERR_ARG;
+  if (n < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "scale: n=%lld", (long long)n);
+  if (n == 0) return RADNET_OK;
   hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, x, (long long)n, alpha);
   RADNET_CHECK_LAUNCH(ctx, "scale");
   return RADNET_OK;
@@ -753,6 +757,7 @@ __global__ void __launch_bounds__(256) scatter_strided_kernel(const float4* __re
 extern "C" int radnet_scatter_strided(radnet_ctx* ctx, const float* src, int32_t nb, int32_t oh, int32_t ow, int32_t c, int32_t stride,
                                       int32_t h, int32_t w, const float* mask, float* dst) {
   if (!ctx || !src || !dst) return RADNET_ERR_ARG;
+  if (nb < 1 || oh < 1 || ow < 1 || c < 4) RADNET_FAIL(ctx, RADNET_ERR_ARG, "scatter_strided: bad nb=%d oh=%d ow=%d c=%d", nb, oh, ow, c);
   if (c % 4 || stride < 1 || (oh - 1) * stride >= h || (ow - 1) * stride >= w)
     RADNET_FAIL(ctx, RADNET_ERR_ARG, "scatter_strided: c=%d stride=%d grid %dx%d into %dx%d", c, stride, oh, ow, h, w);
   const long long total = (long long)nb * h * w * (c / 4);
@@ -765,6 +770,8 @@ extern "C" int radnet_scatter_strided(radnet_ctx* ctx, const float* src, int32_t
 
 extern "C" int radnet_relu_mask(radnet_ctx* ctx, float* g, const float* act, int64_t n) {
   if (!ctx || !g || !act) return RADNET_ERR_ARG;
+  if (n < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "relu_mask: n=%lld", (long long)n);
+  if (n == 0) return RADNET_OK;
   long long b = (n + 255) / 256;
   if (b > 4096) b = 4096;
   if (b < 1) b = 1;
@@ -775,6 +782,8 @@ extern "C" int radnet_relu_mask(radnet_ctx* ctx, float* g, const float* act, int
 
 extern "C" int radnet_affine_vec(radnet_ctx* ctx, float* out, const float* a, const float* b, const float* c, int64_t n) {
   if (!ctx || !out || !a || !b || !c) return RADNET_ERR_ARG;
+  if (n < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "affine_vec: n=%lld", (long long)n);
+  if (n == 0) return RADNET_OK;
   hipLaunchKernelGGL(affine_vec_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, out, a, b, c, (long long)n);
   RADNET_CHECK_LAUNCH(ctx, "affine_vec");
   return RADNET_OK;
