@@ -169,6 +169,25 @@ int radnet_conv_wgrad(radnet_ctx* ctx, const radnet_conv_desc* d);
  * each other's -- and as radnet_conv_wgrad followed by radnet_conv_dgrad otherwise (other launch shapes, d->dx == 0,
  * RADNET_NO_BWD_PAIR=1).  Same results as the two calls.  Timing class 4. */
 int radnet_conv_bwd(radnet_ctx* ctx, const radnet_conv_desc* d);
+/* The weight gradients (and bias gradients, d->db) of n layers in as few launches as their launch shapes allow: the problems are
+ * grouped by the output tile radnet_conv_wgrad would give each of them, up to 16 problems of one tile shape share a launch, and every
+ * problem keeps the grid, the slice count and the slice order of its own radnet_conv_wgrad call -- dw and db hold the bits of the n
+ * single calls.  d->dx is ignored.  Row tables and problem tables are built on the host at the first call (not inside a stream
+ * capture).
+ * opt != 0 with opt->p != 0: Adam in the tile epilogue.  Every dw must lie inside the gradient arena opt->g [n]; the workgroup that
+ * holds the final value of a dw tile -- the tile's only workgroup, or the last arriver of its ordered slice reduction -- applies the
+ * update of radnet_adam_step (step t, grad_scale on the gradient) to the weights and moments at the same offset of opt->p / m / v and
+ * does NOT store the gradient: opt->g is neither written nor read, the same bits as radnet_conv_wgrad into a zeroed arena followed by
+ * radnet_adam_step over these ranges.  The caller guarantees that nothing in flight reads the weights (all data gradients of the step
+ * have run).  Bias gradients still go to d->db.  Refused: dw_accumulate == 1, and split problems on a context whose reductions are
+ * not ordered (radnet_set_deterministic 0).  opt == 0 or opt->p == 0: gradients only. */
+typedef struct radnet_wgrad_adam {
+  float* p; float* g; float* m; float* v;   /* the four arenas; dw - g locates a problem's weights and moments */
+  int64_t n;                                /* floats per arena */
+  int32_t t;                                /* Adam step, from 1 */
+  float lr, beta1, beta2, eps, grad_scale;
+} radnet_wgrad_adam;
+int radnet_conv_wgrad_multi(radnet_ctx* ctx, const radnet_conv_desc* descs, int32_t n, const radnet_wgrad_adam* opt);
 /* Two INDEPENDENT forward convolutions with the same output grid and reduction depth -- branch2a and the shortcut conv of a conv_block
  * (resnet50.py:100,111: both read the block's input) -- as ONE launch where that measured faster than the two launches with their own
  * launch shapes (decided once per pair of shapes, kept in the tuning table), as radnet_conv_fwd(d1), radnet_conv_fwd(d2) otherwise
@@ -339,6 +358,15 @@ typedef struct radnet_adam_wino {
 int radnet_adam_step_fused(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1, float beta2,
                            float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len, const float* scale,
                            const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers);
+/* What is left of that launch behind radnet_conv_wgrad_multi with its optimizer block, which has already stepped the kernels in front of
+ * float offset sweep_from (> 0, a multiple of 4): Adam over [sweep_from, n) only -- biases with their folded shifts (the bias range must
+ * not start in front of sweep_from), dense heads -- and, in the same launch, the filter transforms of the listed 3x3 kernels (all in
+ * front of sweep_from) from the weights as they ARE: their workgroups read the kernels instead of stepping them.  The gradients, moments
+ * and weights in front of sweep_from are not touched.  Same bits as radnet_adam_step_affine on the tail followed by
+ * radnet_winograd4_filter per layer. */
+int radnet_adam_step_tail(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1, float beta2,
+                          float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len, const float* scale,
+                          const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers, int64_t sweep_from);
 /* bf16-mixed training: radnet_adam_step_affine (shift may be 0: no bias re-fold) that ALSO rewrites the bf16 images of up to sixteen
  * conv kernels that live in the arena -- [k][ldw] fp32 at float offset `off` -- from the weights it has just updated:
  * wt[j][i] = bf16(p[off + i*ldw + j]) for i < k, j < n; 0 for k <= i < ldk (radnet_weights_to_bf16's layout and rounding).

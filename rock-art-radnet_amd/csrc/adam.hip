@@ -7,6 +7,7 @@
 // Every arena (p, g, m, v) must be 16-byte aligned -- all paths read float4 -- and ALL FOUR entry points refuse one that is not
 // (radnet_adam_step_bf16 alone did once); every caller in the tree passes whole allocations.
 #include "radnet_internal.h"
+#include "adam_update.h"
 #include "radnet_wino4.h"
 
 namespace {
@@ -34,15 +35,10 @@ struct AdamArgs {
 };
 
 __device__ __forceinline__ void adam_one(float4& pp, const float4& gg, float4& mm, float4& vv, float lr_t, float b1, float b2, float eps, float gs) {
-#define ADAM1(q)                                         \
-  {                                                      \
-    float gq = gg.q * gs;                                \
-    mm.q = b1 * mm.q + (1.f - b1) * gq;                  \
-    vv.q = b2 * vv.q + (1.f - b2) * gq * gq;             \
-    pp.q = pp.q - lr_t * mm.q / (sqrtf(vv.q) + eps);     \
-  }
-  ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
-#undef ADAM1
+  adam_update1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps, gs);
+  adam_update1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps, gs);
+  adam_update1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps, gs);
+  adam_update1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps, gs);
 }
 
 // Adam on float4 chunk i of the arena; returns the new weights.
@@ -88,6 +84,8 @@ struct AdamWino {
   int unit0[kAdamWinoMax + 1];    // first workgroup (relative to the first Winograd workgroup) of each layer; [n] = their total
   float* u[kAdamWinoMax];
   int n;
+  int load_only;                  // radnet_adam_step_tail: the layers' weights are already updated (Adam in the weight gradient's tile
+                                  // epilogue, conv_wgrad_body.h): phase 1 only reads them, phase 2 transforms them as ever
 };
 __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a, AdamWino wz) {
   if (blockIdx.x < a.sweep_blocks) {
@@ -103,7 +101,8 @@ __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a, AdamWino wz) {
   const long long j0 = (long long)(unit - wz.unit0[layer]) * 64;
   for (int it = threadIdx.x; it < 9 * 64; it += 256) {
     const int tap = it >> 6, jj = it & 63;
-    taps[tap][jj] = adam_at(a, wz.off4[layer] + (long long)tap * cn4 + j0 + jj);
+    const long long i = wz.off4[layer] + (long long)tap * cn4 + j0 + jj;
+    taps[tap][jj] = wz.load_only ? a.p[i] : adam_at(a, i);
   }
   __syncthreads();
   // phase 2: wino4_filter_kernel's own code on the same vector type (one thread per float4 chunk), so that both produce the same bits
@@ -190,9 +189,7 @@ struct AdamRange {
 };
 
 // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)   (keras.optimizers.Adam.get_updates)
-float adam_lr_t(float lr, float beta1, float beta2, int t) {
-  return (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
-}
+float adam_lr_t(float lr, float beta1, float beta2, int t) { return radnet_adam_lr_t(lr, beta1, beta2, t); }
 
 // What all four entry points ask of their common arguments; `who` names the entry point in the message.
 int adam_check(radnet_ctx* ctx, const char* who, const float* p, const float* g, const float* m, const float* v, int64_t n, int32_t t,
@@ -250,12 +247,13 @@ int adam_prepare(radnet_ctx* ctx, const char* who, float* p, float* g, float* m,
 
 int adam_fused(radnet_ctx* ctx, const char* who, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,
                float beta2, float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len, const float* scale,
-               const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers) {
+               const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers, int64_t sweep_from = 0) {
   if (!ctx) return RADNET_ERR_ARG;
   if (n_layers < 0 || n_layers > kAdamWinoMax || (n_layers > 0 && !layers)) RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: %d layers (at most %d, in a table)", who, n_layers, kAdamWinoMax);
   AdamWino wz{};
-  AdamRange r[kAdamWinoMax];
+  AdamRange r[kAdamGapMax];
   wz.n = n_layers;
+  wz.load_only = sweep_from > 0 ? 1 : 0;
   for (int l = 0; l < n_layers; ++l) {
     const radnet_adam_wino& d = layers[l];
     if (!d.u || d.c <= 0 || d.n <= 0 || (d.n & 3) || ((uintptr_t)d.u & 15) || (int64_t)d.c * d.n / 4 >= (1ll << 28) || ((int64_t)d.c * d.n / 4) % 64)
@@ -267,8 +265,26 @@ int adam_fused(radnet_ctx* ctx, const char* who, float* p, float* g, float* m, f
     wz.unit0[l + 1] = wz.unit0[l] + wz.cn4[l] / 64;
     r[l] = {d.off, 9ll * d.c * d.n};
   }
+  int nr = n_layers;
+  if (sweep_from > 0) {
+    // the sweep covers [sweep_from, n) only: what lies in front of it and is no listed layer leaves the sweep as ranges of its own
+    // (nobody's workgroups: those weights were updated elsewhere)
+    if ((sweep_from & 3) || sweep_from > n) RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: sweep_from %lld must be a multiple of 4 inside the arena", who, (long long)sweep_from);
+    std::sort(r, r + n_layers, [](const AdamRange& x, const AdamRange& y) { return x.off < y.off; });
+    int64_t at = 0;
+    for (int l = 0; l <= n_layers; ++l) {
+      const int64_t end = l < n_layers ? r[l].off : sweep_from;
+      if (l < n_layers && (r[l].off < at || r[l].off + r[l].len > sweep_from))
+        RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: layer [%lld, +%lld) overlaps another or reaches past sweep_from", who, (long long)r[l].off, (long long)r[l].len);
+      if (end > at) {
+        if (nr + 1 >= kAdamGapMax) RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s: too many layers for the gap table", who);
+        r[nr++] = {at, end - at};
+      }
+      if (l < n_layers) at = r[l].off + r[l].len;
+    }
+  }
   AdamArgs a{};
-  if (int rc = adam_prepare(ctx, who, p, g, m, v, n, t, lr, beta1, beta2, eps, grad_scale, zero_grad, bias_off, bias_len, scale, t0, shift, r, n_layers, a)) return rc;
+  if (int rc = adam_prepare(ctx, who, p, g, m, v, n, t, lr, beta1, beta2, eps, grad_scale, zero_grad, bias_off, bias_len, scale, t0, shift, r, nr, a)) return rc;
   hipLaunchKernelGGL(adam_kernel, dim3(a.sweep_blocks + (unsigned)wz.unit0[n_layers]), dim3(256), 0, ctx->stream, a, wz);
   RADNET_CHECK_LAUNCH(ctx, who);
   return RADNET_OK;
@@ -293,6 +309,18 @@ extern "C" int radnet_adam_step_fused(radnet_ctx* ctx, float* p, float* g, float
                                       float beta2, float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len,
                                       const float* scale, const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers) {
   return adam_fused(ctx, "adam_fused", p, g, m, v, n, t, lr, beta1, beta2, eps, grad_scale, zero_grad, bias_off, bias_len, scale, t0, shift, layers, n_layers);
+}
+
+// Adam over the arena's tail [sweep_from, n) and, in the same launch, the Winograd filters of the listed 3x3 layers from weights that are
+// ALREADY updated (radnet_conv_wgrad_multi's optimizer epilogue): the layers' workgroups read the weights instead of stepping them.
+extern "C" int radnet_adam_step_tail(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,
+                                     float beta2, float eps, float grad_scale, int32_t zero_grad, int64_t bias_off, int64_t bias_len,
+                                     const float* scale, const float* t0, float* shift, const radnet_adam_wino* layers, int32_t n_layers,
+                                     int64_t sweep_from) {
+  if (!ctx) return RADNET_ERR_ARG;
+  if (sweep_from <= 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_tail: sweep_from must be positive (radnet_adam_step_fused sweeps the whole arena)");
+  if (shift != nullptr && bias_off < sweep_from) RADNET_FAIL(ctx, RADNET_ERR_ARG, "adam_tail: the bias range starts in front of the sweep");
+  return adam_fused(ctx, "adam_tail", p, g, m, v, n, t, lr, beta1, beta2, eps, grad_scale, zero_grad, bias_off, bias_len, scale, t0, shift, layers, n_layers, sweep_from);
 }
 
 extern "C" int radnet_adam_step_bf16(radnet_ctx* ctx, float* p, float* g, float* m, float* v, int64_t n, int32_t t, float lr, float beta1,

@@ -72,6 +72,26 @@ struct WgradArgs {
   unsigned* counters;    // arrival counter per tile (zero outside a launch)
   int accumulate;        // ordered form: 1 = add the sum to dw's contents, 0 = store it
   int tiles_x, tiles_y;  // grid.x, grid.y of the launch (the pair kernel has a grid of its own)
+  // Optimizer block (conv_wgrad_multi_kernel only; every other kernel ignores it): ow != null -> the writer of a tile's final value
+  // applies the Adam update (adam_update.h) to ow / om / ov [K][ldw] at the tile's place and does NOT store the gradient into dw.
+  float* ow;
+  float* om;
+  float* ov;
+  float lr_t, beta1, beta2, eps, grad_scale;
+  int pad_opt;
+};
+
+// conv_wgrad_multi_kernel (conv_wgrad.hip): up to kWgradMultiMax problems of one tile shape in one launch.  first[p] = first workgroup
+// of problem p, first[n] = the grid; a problem's workgroups number its (k tile, n tile, slice) grid with the k tile running fastest.
+constexpr int kWgradMultiMax = 16;
+struct WgradMultiMap {
+  unsigned first[kWgradMultiMax + 1];
+  unsigned wx[kWgradMultiMax], wy[kWgradMultiMax];
+  int n;
+};
+// the optimizer scalars of a multi launch travel as kernel arguments (they change with every step; the problem table does not)
+struct WgradOptScalars {
+  float lr_t, beta1, beta2, eps, grad_scale;
 };
 
 // conv_bwd_pair_kernel (conv_wgrad.hip): how its grid divides between the two problems
@@ -107,5 +127,6 @@ struct ChainHeader {
 constexpr int kCtrStride = 16;
 
 // the kernels read these bytes as the host wrote them: both compilers must lay them out alike
-static_assert(sizeof(GemmArgs) == 264 && sizeof(TailArgs) == 120 && sizeof(WgradArgs) == 200 && sizeof(PairMap) == 24, "kernel argument layout");
+static_assert(sizeof(GemmArgs) == 264 && sizeof(TailArgs) == 120 && sizeof(WgradArgs) == 248 && sizeof(PairMap) == 24, "kernel argument layout");
+static_assert(sizeof(WgradMultiMap) == 200 && sizeof(WgradOptScalars) == 20, "multi-problem weight-gradient launch layout");
 static_assert(sizeof(ChainStage) == 336 && sizeof(ChainItem) == 48 && sizeof(ChainHeader) == 32, "chain list layout");

@@ -21,6 +21,8 @@ struct PairCapture {
   WgradArgs gw;
   unsigned wx = 0, wy = 0, wz = 0;
   uint64_t a_slab_bytes = 0, w_slab_bytes = 0;      // split-K slabs at the start / ordered wgrad slabs at the end of the workspace
+  int w_bmk = 64, w_bn = 64;                        // the weight gradient's tile and the exact size of its slabs (radnet_conv_wgrad_multi
+  uint64_t w_slab_need = 0;                         // lays the slabs of several problems side by side)
   double flops = 0.0;
 };
 struct PairPause {

@@ -3,6 +3,7 @@
 #include "conv_host.h"
 #include "conv_igemm_body.h"
 #include "conv_wgrad_body.h"
+#include "wgrad_multi_plan.h"
 
 namespace {
 template <int BMK, int BN>
@@ -47,6 +48,24 @@ __global__ void __launch_bounds__(NTHREADS) conv_bwd_pair_kernel(GemmArgs ga, Wg
     const unsigned plane = pm.wx * pm.wy, bz = idx / plane, r = idx - bz * plane, by = r / pm.wx;
     conv_wgrad_body<64, 64>(gw, lds, r - by * pm.wx, by, bz);
   }
+}
+
+// ---- the weight gradients of several layers in ONE launch ---------------------------------------------------------------
+// Up to kWgradMultiMax problems of one tile shape, each with the grid, the slices and the slice order of its single launch
+// (radnet_conv_wgrad_multi lays the table out), one behind the other in a 1-D grid.  A workgroup finds its problem in the prefix
+// table -- wave-uniform, once -- copies the problem's arguments out of the device table and runs conv_wgrad_body on them: a layer's
+// prologue, tail and ordered reduction run beside the K loops of the layers around it instead of in a launch of their own.
+template <int BMK, int BN>
+__global__ void __launch_bounds__(NTHREADS) conv_wgrad_multi_kernel(const WgradArgs* __restrict__ tab, WgradMultiMap mp, WgradOptScalars os) {
+  __shared__ __attribute__((aligned(16))) float lds[wgrad_lds_floats<BMK, BN>()];
+  const unsigned b = blockIdx.x;
+  int p = 0;
+  for (int q = 1; q < mp.n; ++q)
+    if (b >= mp.first[q]) p = q;
+  const unsigned idx = b - mp.first[p], wx = mp.wx[p], plane = wx * mp.wy[p], bz = idx / plane, r = idx - bz * plane, by = r / wx;
+  WgradArgs g = tab[p];
+  g.lr_t = os.lr_t; g.beta1 = os.beta1; g.beta2 = os.beta2; g.eps = os.eps; g.grad_scale = os.grad_scale;
+  conv_wgrad_body<BMK, BN, true>(g, lds, r - by * wx, by, bz);
 }
 
 // Row table of a convolution geometry for the wgrad kernel: entry m = output pixel (image, oh, ow) holds the byte offset
@@ -146,6 +165,8 @@ static int run_wgrad(radnet_ctx* ctx, const radnet_conv_desc* d, int batch, long
       pc->w_ok = bmk == 64 && bn == 64 && batch <= 1;
       pc->gw = g;
       pc->w_slab_bytes = wgrad_slab_bytes;
+      pc->w_bmk = bmk; pc->w_bn = bn;
+      pc->w_slab_need = wgrad_slab_bytes ? wgrad_slab_bytes - 256 : 0;
       pc->wx = grid.x; pc->wy = grid.y; pc->wz = grid.z;
       pc->flops += 2.0 * g.M * g.N * g.K;
       return RADNET_OK;
@@ -280,6 +301,111 @@ extern "C" int radnet_conv_bwd(radnet_ctx* ctx, const radnet_conv_desc* d) {
   else RADNET_LAUNCH(conv_bwd_pair_kernel<64>, dim3(pm.n_a + pm.n_w), dim3(NTHREADS), 0, ctx->stream, ctx->arm0, ctx->arm1, pc.ga, pc.gw, pm);
   RADNET_CHECK_LAUNCH(ctx, "conv_bwd_pair");
   radnet_timing_end_armed(ctx, 4, pc.flops);
+  return RADNET_OK;
+}
+
+radnet_ctx::MultiTables::~MultiTables() {
+  for (auto& e : v)
+    if (e.second) (void)hipFree(e.second);
+}
+
+namespace {
+// The device copy of a problem table: the one made for the same bytes before, or a new allocation (a table is never rewritten).
+const WgradArgs* get_multi_table(radnet_ctx* ctx, const WgradArgs* host, int n) {
+  const size_t bytes = sizeof(WgradArgs) * (size_t)n;
+  auto& v = ctx->multi_tables.v;
+  for (auto& e : v)
+    if (e.first.size() == bytes && memcmp(e.first.data(), host, bytes) == 0) return (const WgradArgs*)e.second;
+  if (v.size() >= 256) {                     // hipFree waits for the device: no launch reads the table any more
+    (void)hipFree(v.front().second);
+    v.erase(v.begin());
+  }
+  void* dev = nullptr;
+  if (hipMalloc(&dev, bytes) != hipSuccess) return nullptr;
+  if (hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(dev);
+    return nullptr;
+  }
+  v.emplace_back(std::vector<char>((const char*)host, (const char*)host + bytes), dev);
+  return (const WgradArgs*)dev;
+}
+}  // namespace
+
+// The weight gradients (and bias gradients) of n layers in as few launches as their tile shapes allow: every problem keeps the tile
+// shape, the slice count and the slice order of its own radnet_conv_wgrad call -- that call's launch policy chooses them, tuning
+// table, forced configuration and autotuner included -- so dw and db hold the bits of the n single calls.  With an optimizer block
+// the writer of each tile's final value applies the Adam step to the weights behind that tile instead of storing the gradient.
+extern "C" int radnet_conv_wgrad_multi(radnet_ctx* ctx, const radnet_conv_desc* descs, int32_t n, const radnet_wgrad_adam* opt) {
+  if (!ctx || n < 0 || (n > 0 && !descs)) return RADNET_ERR_ARG;
+  if (n == 0) return RADNET_OK;
+  if (ctx->pair_capture != nullptr) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_multi: called inside radnet_conv_bwd");
+  const bool adam = opt != nullptr && opt->p != nullptr;
+  if (adam) {
+    if (!opt->g || !opt->m || !opt->v || opt->n <= 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_multi: optimizer block with a null arena");
+    if (opt->t < 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_multi: step counter starts at 1");
+  }
+  std::vector<PairCapture> pcs((size_t)n);
+  std::vector<WgradMultiItem> items((size_t)n);
+  const int timed = ctx->timing;
+  for (int i = 0; i < n; ++i) {
+    radnet_conv_desc d = descs[i];
+    d.dx = nullptr;                            // a weight gradient of its own: the autotuner does not narrow its candidates for a pairing
+    if (adam) {
+      if (d.dw_accumulate == 1) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_multi: problem %d adds to its gradient; the optimizer epilogue needs the whole gradient", i);
+      const int64_t off = d.dw - opt->g, last = (int64_t)(d.kh * d.kw * d.c - 1) * d.ldw + d.n;
+      if (!d.dw || d.dw < opt->g || off + last > opt->n) RADNET_FAIL(ctx, RADNET_ERR_ARG, "conv_wgrad_multi: problem %d's dw lies outside the gradient arena", i);
+    }
+    ctx->timing = 0;
+    ctx->pair_capture = &pcs[i];
+    const int rc = radnet_conv_wgrad(ctx, &d);      // host-side preparation (row table, memsets of overwrite mode, autotuning) happens here
+    ctx->pair_capture = nullptr;
+    ctx->timing = timed;
+    if (rc != RADNET_OK) return rc;
+    PairCapture& pc = pcs[i];
+    if (!pc.have_w) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_multi: problem %d produced no launch", i);
+    const bool ordered = pc.gw.slabs != nullptr;
+    if (adam && !ordered && pc.gw.atomic)
+      RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_multi: problem %d adds its slices with atomics (no final writer); the optimizer epilogue needs ordered reductions", i);
+    items[i] = WgradMultiItem{pc.w_bmk, pc.w_bn, pc.wx, pc.wy, pc.wz, ordered ? pc.w_slab_need : 0, ordered ? pc.wx * pc.wy : 0u};
+  }
+  std::vector<WgradMultiLaunch> plan((size_t)n);
+  const int nl = wgrad_multi_plan(items.data(), n, ctx->ws_bytes, (unsigned)kAuxWgradCounterCount, plan.data(), n);
+  if (nl < 0) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "conv_wgrad_multi: the problems do not fit a launch plan (%d)", nl);
+  WgradOptScalars os{};
+  if (adam) os = WgradOptScalars{radnet_adam_lr_t(opt->lr, opt->beta1, opt->beta2, opt->t), opt->beta1, opt->beta2, opt->eps, opt->grad_scale};
+  for (int l = 0; l < nl; ++l) {
+    const WgradMultiLaunch& L = plan[l];
+    WgradArgs host[kWgradMultiMax];
+    memset(host, 0, sizeof(host));
+    double flops = 0.0;
+    for (int k = 0; k < L.n; ++k) {
+      const PairCapture& pc = pcs[L.problem[k]];
+      WgradArgs& g = host[k];
+      memcpy(&g, &pc.gw, sizeof(g));
+      if (g.slabs != nullptr) {
+        g.slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ctx->ws) + L.slab_off[k]);
+        g.counters = reinterpret_cast<unsigned*>(ctx->aux + kAuxWgradCounters) + L.counter_off[k];
+      }
+      g.ow = g.om = g.ov = nullptr;
+      g.lr_t = g.beta1 = g.beta2 = g.eps = g.grad_scale = 0.f;      // they arrive as kernel arguments
+      g.pad_opt = 0;
+      if (adam) {
+        const int64_t off = g.dw - opt->g;
+        g.ow = opt->p + off; g.om = opt->m + off; g.ov = opt->v + off;
+      }
+      flops += 2.0 * g.M * g.N * g.K;
+    }
+    const WgradArgs* tab = get_multi_table(ctx, host, L.n);
+    if (!tab) RADNET_FAIL(ctx, RADNET_ERR_HIP, "conv_wgrad_multi: cannot place the problem table on the device");
+    const dim3 grid(L.map.first[L.n]), block(NTHREADS);
+    radnet_timing_arm(ctx);
+    if (L.bmk == 128 && L.bn == 128) RADNET_LAUNCH((conv_wgrad_multi_kernel<128, 128>), grid, block, 0, ctx->stream, ctx->arm0, ctx->arm1, tab, L.map, os);
+    else if (L.bmk == 128 && L.bn == 64) RADNET_LAUNCH((conv_wgrad_multi_kernel<128, 64>), grid, block, 0, ctx->stream, ctx->arm0, ctx->arm1, tab, L.map, os);
+    else if (L.bmk == 64 && L.bn == 128) RADNET_LAUNCH((conv_wgrad_multi_kernel<64, 128>), grid, block, 0, ctx->stream, ctx->arm0, ctx->arm1, tab, L.map, os);
+    else RADNET_LAUNCH((conv_wgrad_multi_kernel<64, 64>), grid, block, 0, ctx->stream, ctx->arm0, ctx->arm1, tab, L.map, os);
+    RADNET_CHECK_LAUNCH(ctx, "conv_wgrad_multi");
+    radnet_timing_end_armed(ctx, 2, flops);
+  }
   return RADNET_OK;
 }
 

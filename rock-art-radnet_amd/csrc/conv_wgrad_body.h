@@ -2,13 +2,15 @@
 // dW[k][n] (+)= sum_m im2col(x)[m][k] * (dy[m][n] * gscale[n]).  Output tile BMK (k) x BN (n); the
 // reduction runs over output pixels m in steps of 32, optionally split across blockIdx.z (atomics).
 #pragma once
+#include "adam_update.h"
 #include "conv_device.h"
 
 namespace {
 template <int BMK, int BN>
 constexpr int wgrad_lds_floats() { return 2 * BK * ((BMK + 4) + (BN + 4)); }
 
-template <int BMK, int BN>
+// OPT: the epilogue honours the optimizer block of WgradArgs (conv_wgrad_multi_kernel); the other kernels' code is what it was.
+template <int BMK, int BN, bool OPT = false>
 __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& g, float* __restrict__ lds, const unsigned bid_x, const unsigned bid_y, const unsigned bid_z) {
   constexpr int TM = BMK / 64, TN = BN / 64;
   constexpr int PA = BMK + 4, PB = BN + 4;
@@ -273,6 +275,44 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& g, float* __res
       }
     }
     return;
+  }
+  if constexpr (OPT) {
+    // Adam in the tile epilogue: this workgroup holds the final value of its tile -- its own sum when the launch is not split, the
+    // ordered sum of the slices as their last arriver -- and no launch of the step reads the layer's weights any more (all data
+    // gradients ran before this launch), so it updates w, m, v at the tile's place and the gradient never travels through memory.
+    // Same element order as the stores below; adam_update1 is the routine of adam_kernel, bit for bit.
+    if (g.ow != nullptr) {             // uniform for the problem
+      const unsigned bytes = (unsigned)((size_t)g.K * (size_t)g.ldw * 4u);
+      const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.ow + bp * g.dw_bstride, bytes), rm = make_rsrc(g.om + bp * g.dw_bstride, bytes),
+                                   rv = make_rsrc(g.ov + bp * g.dw_bstride, bytes);
+      const unsigned ldw4 = (unsigned)g.ldw * 4u;
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int n = n0 + wn * (BN / 2) + j * 32 + l31;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const int kb = k0 + wm * (BMK / 2) + i * 32 + 4 * hi;
+          const unsigned voff = (n < g.N && kb < g.K) ? ((unsigned)kb * (unsigned)g.ldw + (unsigned)n) * 4u : kOOB;
+          float pw[16], pm[16], pv[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const unsigned off = voff + (unsigned)((r & 3) + 8 * (r >> 2)) * ldw4;
+            pw[r] = buf_load1(rw, off);
+            pm[r] = buf_load1(rm, off);
+            pv[r] = buf_load1(rv, off);
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const unsigned off = voff + (unsigned)((r & 3) + 8 * (r >> 2)) * ldw4;
+            adam_update1(pw[r], acc[i][j][r], pm[r], pv[r], g.lr_t, g.beta1, g.beta2, g.eps, g.grad_scale);
+            buf_store1(rw, off, pw[r]);
+            buf_store1(rm, off, pm[r]);
+            buf_store1(rv, off, pv[r]);
+          }
+        }
+      }
+      return;
+    }
   }
   // Plain stores / ordered accumulate, straight-line (round 4; the first form decided ordered / accumulate / atomic and the two
   // bounds per accumulator register -- five branches each, and in accumulate mode a load + wait + store round trip per register):

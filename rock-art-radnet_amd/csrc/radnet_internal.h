@@ -72,6 +72,13 @@ struct radnet_ctx {
     ~RowTables();
   };
   std::shared_ptr<RowTables> row_tables = std::make_shared<RowTables>();
+  // radnet_conv_wgrad_multi (conv_wgrad.hip): the device copies of the problem tables its launches read, keyed by their bytes.  A
+  // table is never rewritten -- a launch still in flight may be reading it -- and a training step meets the same few tables again.
+  struct MultiTables {
+    std::vector<std::pair<std::vector<char>, void*>> v;
+    ~MultiTables();
+  };
+  MultiTables multi_tables;
   hipEvent_t tune_ev0 = nullptr, tune_ev1 = nullptr;
   int device = 0;
   hipStream_t stream = nullptr;

@@ -46,24 +46,25 @@ def rpn_to_roi(rpn_layer, regr_layer, C_cfg, use_regr=True, max_boxes=300, overl
     from radnet_hip import runtime as rt
     assert rpn_layer.shape[0] == 1                                        # rpn.py:96
     rows, cols, A = rpn_layer.shape[1:4]
-    ctx = rt.default_context()
     pred = np.zeros((rows * cols, 5 * A), np.float32)
     pred[:, :A] = np.asarray(rpn_layer, dtype=np.float32).reshape(-1, A)
     pred[:, A:] = np.asarray(regr_layer, dtype=np.float32).reshape(-1, 4 * A)
-    pd = rt.to_dev(pred)
-    R = torch.zeros(max_boxes, 4, dtype=torch.int64, device="cuda")
-    Rp = torch.zeros(max_boxes, dtype=torch.float32, device="cuda")
-    Rn = torch.zeros(1, dtype=torch.int32, device="cuda")
-    ws = rt.scratch("proposals", ctx.lib.radnet_proposals_ws_bytes(rows * cols * A))
-    awh = _anchor_wh(C_cfg)
-    rc = ctx.lib.radnet_rpn_to_roi(ctx.h, pd.data_ptr(), 5 * A, rows, cols, A, rt.f64_ptr(awh), float(C_cfg.std_scaling), 1 if use_regr else 0,
-                                   float(overlap_thresh), int(max_boxes), R.data_ptr(), Rp.data_ptr(), Rn.data_ptr(), ws.data_ptr())
-    ctx.check(rc, "radnet_rpn_to_roi")
-    n = int(Rn.cpu()[0])
+    with rt.default_scope() as ctx:      # uploads, launch and read-back on the context's stream, whatever stream the caller is on
+        pd = rt.to_dev(pred)
+        R = torch.zeros(max_boxes, 4, dtype=torch.int64, device="cuda")
+        Rp = torch.zeros(max_boxes, dtype=torch.float32, device="cuda")
+        Rn = torch.zeros(1, dtype=torch.int32, device="cuda")
+        ws = rt.scratch("proposals", ctx.lib.radnet_proposals_ws_bytes(rows * cols * A))
+        awh = _anchor_wh(C_cfg)
+        rc = ctx.lib.radnet_rpn_to_roi(ctx.h, pd.data_ptr(), 5 * A, rows, cols, A, rt.f64_ptr(awh), float(C_cfg.std_scaling), 1 if use_regr else 0,
+                                       float(overlap_thresh), int(max_boxes), R.data_ptr(), Rp.data_ptr(), Rn.data_ptr(), ws.data_ptr())
+        ctx.check(rc, "radnet_rpn_to_roi")
+        n = int(Rn.cpu()[0])
+        R_host = R.cpu().numpy()
     if n <= 0:
         # the reference unpacks the [] its NMS returns for "no boxes" and dies with ValueError (rpn.py:170,391-392)
         raise ValueError("not enough values to unpack (expected 2, got 0)")
-    return R[:n].cpu().numpy()
+    return R_host[:n]
 
 
 def calc_iou(R, img_data, C_cfg, class_mapping):
@@ -79,26 +80,27 @@ def calc_iou(R, img_data, C_cfg, class_mapping):
     n = int(R.shape[0])
     if n == 0 or len(bboxes) == 0:
         return None, None, None, None
-    ctx = rt.default_context()
-    gt = rt.to_dev(np.array([[b["x1"], b["y1"], b["x2"], b["y2"]] for b in bboxes], dtype=np.float64))
-    gc = rt.to_dev(np.array([class_mapping[b["class"]] for b in bboxes], dtype=np.int32))
-    Rd = rt.to_dev(np.asarray(R).round().astype(np.int64))                 # rpn.py:211-214: int(round(.)) of each coordinate
-    keep = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    cls = torch.zeros(n, dtype=torch.int32, device="cuda")
-    box = torch.zeros(n, 4, dtype=torch.int32, device="cuda")
-    t = torch.zeros(n, 4, dtype=torch.float64, device="cuda")
-    iou = torch.zeros(n, dtype=torch.float64, device="cuda")
-    std = np.array(C_cfg.classifier_regr_std, dtype=np.float64)
-    rc = ctx.lib.radnet_roi_targets(ctx.h, Rd.data_ptr(), n, gt.data_ptr(), gc.data_ptr(), len(bboxes), int(width), int(height), int(rw), int(rh),
-                                    float(C_cfg.rpn_stride), float(C_cfg.classifier_min_overlap), float(C_cfg.classifier_max_overlap),
-                                    rt.f64_ptr(std), int(bg), keep.data_ptr(), cls.data_ptr(), box.data_ptr(), t.data_ptr(), iou.data_ptr(), None)
-    ctx.check(rc, "radnet_roi_targets")
-    k = keep.cpu().numpy().astype(bool)
+    with rt.default_scope() as ctx:
+        gt = rt.to_dev(np.array([[b["x1"], b["y1"], b["x2"], b["y2"]] for b in bboxes], dtype=np.float64))
+        gc = rt.to_dev(np.array([class_mapping[b["class"]] for b in bboxes], dtype=np.int32))
+        Rd = rt.to_dev(np.asarray(R).round().astype(np.int64))                 # rpn.py:211-214: int(round(.)) of each coordinate
+        keep = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        cls = torch.zeros(n, dtype=torch.int32, device="cuda")
+        box = torch.zeros(n, 4, dtype=torch.int32, device="cuda")
+        t = torch.zeros(n, 4, dtype=torch.float64, device="cuda")
+        iou = torch.zeros(n, dtype=torch.float64, device="cuda")
+        std = np.array(C_cfg.classifier_regr_std, dtype=np.float64)
+        rc = ctx.lib.radnet_roi_targets(ctx.h, Rd.data_ptr(), n, gt.data_ptr(), gc.data_ptr(), len(bboxes), int(width), int(height), int(rw), int(rh),
+                                        float(C_cfg.rpn_stride), float(C_cfg.classifier_min_overlap), float(C_cfg.classifier_max_overlap),
+                                        rt.f64_ptr(std), int(bg), keep.data_ptr(), cls.data_ptr(), box.data_ptr(), t.data_ptr(), iou.data_ptr(), None)
+        ctx.check(rc, "radnet_roi_targets")
+        k = keep.cpu().numpy().astype(bool)
+        cls_h, box_h, t_h, iou_h = cls.cpu().numpy(), box.cpu().numpy(), t.cpu().numpy(), iou.cpu().numpy()
     if not k.any():
         return None, None, None, None
-    c = cls.cpu().numpy()[k]
-    X = box.cpu().numpy()[k].astype(np.int64)
-    tt = t.cpu().numpy()[k]
+    c = cls_h[k]
+    X = box_h[k].astype(np.int64)
+    tt = t_h[k]
     m = len(c)
     Y1 = np.zeros((m, nc), dtype=np.int64)
     Y1[np.arange(m), c] = 1
@@ -109,7 +111,7 @@ def calc_iou(R, img_data, C_cfg, class_mapping):
         lab[fg, 4 * c[fg] + q] = 1
         coords[fg, 4 * c[fg] + q] = tt[fg, q]
     Y2 = np.concatenate([lab, coords], axis=1)
-    return np.expand_dims(X, 0), np.expand_dims(Y1, 0), np.expand_dims(Y2, 0), iou.cpu().numpy()[k].tolist()
+    return np.expand_dims(X, 0), np.expand_dims(Y1, 0), np.expand_dims(Y2, 0), iou_h[k].tolist()
 
 
 def apply_regr(x, y, w, h, tx, ty, tw, th):
@@ -135,17 +137,18 @@ def non_max_suppression_fast(boxes, probs, overlap_thresh=0.9, max_boxes=300):
     if len(boxes) == 0:
         return []
     probs = np.asarray(probs)
-    ctx = rt.default_context()
-    n = int(boxes.shape[0])
-    bd = rt.to_dev(boxes[:, :4], dtype=np.float64)
-    pd = rt.to_dev(probs, dtype=np.float32)
-    idx = torch.zeros(max(1, min(int(max_boxes), 1024)), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
-    ws = rt.scratch("nms", ctx.lib.radnet_proposals_ws_bytes(n))
-    ctx.call("radnet_nms", bd, pd, n, C.c_double(float(overlap_thresh)), int(min(max_boxes, 1024)), idx, cnt, ws)
-    k = int(cnt.cpu()[0])
+    with rt.default_scope() as ctx:      # (predict's merge tail calls this on whatever stream its caller is on)
+        n = int(boxes.shape[0])
+        bd = rt.to_dev(boxes[:, :4], dtype=np.float64)
+        pd = rt.to_dev(probs, dtype=np.float32)
+        idx = torch.zeros(max(1, min(int(max_boxes), 1024)), dtype=torch.int32, device="cuda")
+        cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+        ws = rt.scratch("nms", ctx.lib.radnet_proposals_ws_bytes(n))
+        ctx.call("radnet_nms", bd, pd, n, C.c_double(float(overlap_thresh)), int(min(max_boxes, 1024)), idx, cnt, ws)
+        k = int(cnt.cpu()[0])
+        idx_h = idx.cpu().numpy()
     if k < 0:
         raise AssertionError("non_max_suppression_fast: box with x1 >= x2 or y1 >= y2")
-    pick = idx.cpu().numpy()[:k]
+    pick = idx_h[:k]
     out_boxes = boxes[pick].astype("int")
     return out_boxes, probs[pick]

@@ -234,6 +234,10 @@ class FasterRCNNEngine:
         self.wino_wgrad = os.environ.get("RADNET_NO_WINOGRAD_WGRAD", "0") != "1"
         # ... and their weight gradients in the Winograd domain, on the transformed input the forward pass left (the rpn_conv1 path)
         self.head_wino_wgrad = self.head_train_wino and self.wino_wgrad and os.environ.get("RADNET_NO_HEAD_WINO_WGRAD", "0") != "1"
+        # Second form of the classifier's backward: all data gradients first, then every weight gradient in one launch per
+        # tile shape with Adam #2 in the tile epilogue (radnet_conv_wgrad_multi).  Only where a step's gradient is complete inside one
+        # program and goes straight into Adam -- TrainStep decides per step; RADNET_HEAD_DEFERRED_WGRAD=0 keeps the paired launches.
+        self.head_deferred_wgrad = (self.HEAD_DEFERRED_WGRAD and precision == "fp32" and os.environ.get("RADNET_HEAD_DEFERRED_WGRAD", "1") != "0")
         self.ws = torch.empty(256 << 20, dtype=torch.uint8, device=self.dev)         # split-K partials
         self.ctx.check(self.lib.radnet_set_workspace(self.ctx.h, self.ws.data_ptr(), self.ws.numel()), "set_workspace")
         # 0 off / 1 measure every new GEMM shape / 2 adopt the nearest measured M first (variable tile sizes, lib header)
@@ -610,6 +614,7 @@ class FasterRCNNEngine:
     HEAD_WINO_WGRAD_MIN_ROIS = int(os.environ.get("RADNET_HEAD_WINO_WGRAD_MIN_ROIS", "40"))
     CROP_AHEAD = True                  # TrainStep may issue head_crop() ahead of head_forward(cropped=True)
     HEAD_TRAIN_WINOGRAD = True         # classifier 3x3 convs: Winograd forward in training too (engine_cont keeps the direct form)
+    HEAD_DEFERRED_WGRAD = True         # the stage-5 head may run the deferred weight-gradient form (engine_cont / engine_vgg: never)
     FROZEN_BASE_FUSION = True          # nn_base's stage 2 is frozen in every mode this engine runs (train.py, cont_train.py: stages 3-4 only)
 
     _fuse_bottlenecks = staticmethod(prog.fuse_bottlenecks)
@@ -1259,6 +1264,11 @@ class FasterRCNNEngine:
         plan = dict(R=R, rois=rois, pooled=pooled, fwd=fwd, bwd=bwd, bwd_parts=bwd_parts, blocks=blocks, y5=cur, hw=h * w, M=M, feat=feat, pcls=pcls,
                     tail_scratch=tail_scratch, live=live, live_host=[1] * groups, wg_scratch=shared_wg,
                     pregr=pregr, y1=y1, y2=y2, dz=dz, dfeat=dfeat, g_last=g_first, F=F, fh=fh, fw=fw, keep=keep, groups=groups)
+        # the same backward with the weight gradients deferred to one launch per tile shape behind all data gradients: every layer's dy
+        # (g_out / g_b / g_a of each block, g_prev between blocks) has its own buffer above, so they are still there at the end
+        form = prog.deferred_wgrad_form(bwd) if self.head_deferred_wgrad else None
+        if form is not None and len(form[1]) == len(self.head_conv_names):
+            plan["bwd_dgrad"], plan["bwd_wgrad"] = form
         self._plans[key] = plan
         return plan
 
@@ -1324,7 +1334,45 @@ class FasterRCNNEngine:
         self.ctx.call("radnet_dense_heads_fwd", hp["feat"], hp["R"], 2048, self.dense_w, self.dense_ld, self.dense_b, self.nc, self.nreg,
                       hp["pcls"], hp["pregr"])
 
-    def head_backward(self, hp, accumulate=False, loss_out=None, on_part=None):
+    def head_deferred_ok(self, hp):
+        """True when this plan's backward may run in the deferred weight-gradient form (head_backward(defer_wgrad=True) followed by
+        head_update_deferred): the plan has the form, the reductions are ordered (a split weight gradient needs a last writer), Adam's
+        tail can refresh the folded shifts in its own launch, and every kernel gradient is written whole (not added to an earlier one)."""
+        return (self.head_deferred_wgrad and "bwd_wgrad" in hp and self.head_bias_len > 0 and self.head_bias_off % 4 == 0 and self.head_bias_len % 4 == 0
+                and int(self.lib.radnet_get_deterministic(self.ctx.h)) == 1 and all(d.dw_accumulate != 1 for d in hp["bwd_wgrad"]))
+
+    def head_update_deferred(self, hp, grad_scale=1.0):
+        """Behind head_backward(defer_wgrad=True): the weight gradients of every stage-5 conv in one launch per tile shape, each tile's
+        writer applying Adam #2 to the kernels behind it (radnet_conv_wgrad_multi: the kernel part of the gradient arena is neither
+        written nor read and stays zero); then ONE launch for what is left of Adam #2 (radnet_adam_step_tail): Adam over the arena's tail --
+        biases with their folded shifts, dense heads -- and the Winograd filters of the 3x3 convs from the new kernels (without a dense
+        3x3 layout: radnet_adam_step_affine on the tail, then the filter transforms).  Same step counter, same bits as adam(head_arena)."""
+        arena = self.head_arena
+        arena.t += 1
+        modes = tuple(d.dw_accumulate for d in hp["bwd_wgrad"])
+        ent = hp.get("_wgrad_arr")
+        if ent is None or ent[0] != modes:
+            ent = hp["_wgrad_arr"] = (modes, prog.desc_array(hp["bwd_wgrad"]))
+        opt = L.WgradAdam()
+        opt.p, opt.g, opt.m, opt.v, opt.n, opt.t = arena.p.data_ptr(), arena.g.data_ptr(), arena.m.data_ptr(), arena.v.data_ptr(), arena.n, arena.t
+        opt.lr, opt.beta1, opt.beta2, opt.eps, opt.grad_scale = self.lr, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, grad_scale
+        self.ctx.check(self.lib.radnet_conv_wgrad_multi(self.ctx.h, ent[1], len(modes), C.byref(opt)), "radnet_conv_wgrad_multi")
+        off = self.head_bias_off
+        wino = self._head_adam_wino() if self.head_train_wino else None
+        if wino is not None:          # one launch: Adam over the tail, the folded shifts, and the filters of the 3x3 convs from the new kernels
+            self.ctx.call("radnet_adam_step_tail", arena.p, arena.g, arena.m, arena.v, C.c_int64(arena.n), arena.t, C.c_float(self.lr),
+                          C.c_float(ADAM_BETA1), C.c_float(ADAM_BETA2), C.c_float(ADAM_EPS), C.c_float(grad_scale), 1, C.c_int64(off),
+                          C.c_int64(self.head_bias_len), self.head_scale, self.head_t0, self.head_shift, wino[0], wino[1], C.c_int64(off))
+            return
+        self.ctx.call("radnet_adam_step_affine", arena.p[off:], arena.g[off:], arena.m[off:], arena.v[off:], C.c_int64(arena.n - off), arena.t,
+                      C.c_float(self.lr), C.c_float(ADAM_BETA1), C.c_float(ADAM_BETA2), C.c_float(ADAM_EPS), C.c_float(grad_scale), 1,
+                      C.c_int64(0), C.c_int64(self.head_bias_len), self.head_scale, self.head_t0, self.head_shift)
+        if self.head_train_wino:
+            self._refresh_winograd(list(self.INFERENCE_WINOGRAD_LAYERS))
+        else:
+            self._inference_filters_stale = True
+
+    def head_backward(self, hp, accumulate=False, loss_out=None, on_part=None, defer_wgrad=False):
         """losses (losses.py:69-95) + gradients of every stage-5 conv and both dense heads into the head grad arena.
         on_part(lo, hi): called after each block of the backward program (last block first) with the slice [lo, hi) of
         the flat gradient arena that block has just completed -- the data-parallel trainer starts that slice's all-reduce
@@ -1350,6 +1398,9 @@ class FasterRCNNEngine:
         self.ctx.call("radnet_dense_heads_bwd", hp["feat"], hp["dz"], hp["R"], 2048, self.dense_w, self.dense_ld, self.nc + self.nreg,
                       self.dense_dw, self.dense_db, hp["dfeat"], 1 if accumulate else 0)
         self.ctx.call("radnet_avgpool_bwd_relu", hp["dfeat"], hp["y5"], hp["R"], hp["hw"], 2048, hp["g_last"])
+        if defer_wgrad:                       # the data gradients only; head_update_deferred() runs the weight gradients (with Adam #2)
+            self._run(hp["bwd_dgrad"])
+            return
         if on_part is None or "bwd_parts" not in hp:
             self._run(hp["bwd"])
             return

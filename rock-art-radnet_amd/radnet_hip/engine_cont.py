@@ -24,7 +24,8 @@ from .engine import PRECISIONS, RES_STAGES, Arena, FasterRCNNEngine
 
 class ContEngine(FasterRCNNEngine):
     HEAD_TRAIN_WINOGRAD = False        # cont_train.py mode: gradients flow through these layers into two optimizers; direct form kept
-    WORKLOAD = "cont"            # one lane, other launch mix: the pipelined step's in-situ tables do not apply (measured: -1 %)
+    HEAD_DEFERRED_WGRAD = False        # ... and their weights are read by more than the head's own program
+    WORKLOAD = "cont"           # one lane, other launch mix: the pipelined step's in-situ tables do not apply (measured: -1 %)
     supports_batched = False     # cont_train.py's step runs one image at a time (both optimizers move the shared stages)
     # rpn_conv1 keeps F(2x2,3x3) here: its weight gradient is formed in the Winograd domain and flows on into stages 3 / 4, whose first Adam
     # steps divide by |g| + 1e-7 -- F(4x4)'s 15x larger fp32 rounding would show in the updates of small-gradient weights.  The ten

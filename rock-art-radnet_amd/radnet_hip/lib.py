@@ -103,6 +103,12 @@ class AdamWino(C.Structure):
     _fields_ = [("off", C.c_int64), ("c", C.c_int32), ("n", C.c_int32), ("u", C.c_void_p)]
 
 
+class WgradAdam(C.Structure):
+    """Mirror of `radnet_wgrad_adam`: the optimizer block of radnet_conv_wgrad_multi (Adam in the weight gradient's tile epilogue)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("t", C.c_int32),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("grad_scale", C.c_float)]
+
+
 class AdamBf16(C.Structure):
     """Mirror of `radnet_adam_bf16`: a conv kernel [k][ldw] inside an optimizer arena and its bf16 image [n][ldk] (bf16-mixed training)."""
     _fields_ = [("off", C.c_int64), ("k", C.c_int32), ("n", C.c_int32), ("ldw", C.c_int32), ("wt", C.c_void_p), ("ldk", C.c_int32)]
@@ -219,10 +225,13 @@ def load_library():
         "radnet_winograd4_filter_grad": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
         "radnet_adam_step_fused": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32,
                                             C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(AdamWino), i32]),
+        "radnet_adam_step_tail": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32,
+                                           C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(AdamWino), i32, C.c_int64]),
         "radnet_adam_step_bf16": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32,
                                            C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(AdamBf16), i32]),
         "radnet_conv_wgrad": (C.c_int, [vp, C.POINTER(ConvDesc)]),
         "radnet_conv_bwd": (C.c_int, [vp, C.POINTER(ConvDesc)]),
+        "radnet_conv_wgrad_multi": (C.c_int, [vp, C.POINTER(ConvDesc), i32, C.POINTER(WgradAdam)]),
         "radnet_conv_fwd_pair": (C.c_int, [vp, C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
         "radnet_conv_bottleneck": (C.c_int, [vp, C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
         "radnet_colsum": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, i32]),

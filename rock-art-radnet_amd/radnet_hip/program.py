@@ -225,6 +225,32 @@ def backward_program(ops, precision, dgrad_image):
     return fuse_bias_grads(bf16_backward(ops, precision, dgrad_image))
 
 
+def deferred_wgrad_form(ops):
+    """The second form of a backward program whose ops are fp32 ("wgrad", d) / ("dgrad", d) only (bias gradients already folded into
+    the weight gradients, fuse_bias_grads): (the data gradients as a program of their own, in their order; the weight-gradient
+    descriptors in program order, for ONE radnet_conv_wgrad_multi call behind it), or None for a program with any other op -- a
+    Winograd-domain weight gradient, a column sum left on its own, a bf16 kind.  Valid where every dy and every forward input of the
+    program has its own buffer that nothing rewrites before the program ends: the weight gradients then read what they read in place.
+    The descriptors are the program's own objects, so set_accumulate on `ops` reaches both forms."""
+    if not ops or any(kind not in ("wgrad", "dgrad") for kind, _ in ops):
+        return None
+    wgrads = [p for kind, p in ops if kind == "wgrad"]
+    if not wgrads:
+        return None
+    for k, (kind, p) in enumerate(ops):         # a data gradient behind a weight gradient must not write what that one reads
+        if kind == "wgrad" and any(q.dx in (p.dy, p.x) for kq, q in ops[k + 1:] if kq == "dgrad" and q.dx):
+            return None
+    return [op for op in ops if op[0] == "dgrad"], wgrads
+
+
+def desc_array(descs):
+    """Copies of the descriptors as one radnet_conv_desc[] (radnet_conv_wgrad_multi)."""
+    arr = (L.ConvDesc * len(descs))()
+    for i, d in enumerate(descs):
+        arr[i] = d
+    return arr
+
+
 # ---------------------------------------------------------------------------------------------- compile
 def _ptr(v):
     return v.data_ptr() if hasattr(v, "data_ptr") else v

@@ -1,5 +1,6 @@
 """Process-wide default device objects for the function-style API of the drop-in `faster_rcnn` package
 (rpn.rpn_to_roi, rpn.calc_iou, utils.calc_region_props, ... take NumPy arrays and need a context to run on)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -35,6 +36,31 @@ def default_context():
         _local.stream = torch.cuda.Stream(device=dev)
         _local.ctx = L.Context(dev, stream_handle=_local.stream.cuda_stream)
     return _local.ctx
+
+
+@contextlib.contextmanager
+def default_scope():
+    """`with default_scope() as ctx:` -- the calling thread's default context with the stream it launches on made torch's current stream
+    for the block.  The function-style API allocates, uploads and reads back with torch and launches through the context; when the
+    caller sits on another stream (RADNet.predict on an image made on a side stream) the two would otherwise be unordered -- a result
+    buffer zeroed on the caller's stream after the kernel wrote it, a count read before it was written.  The context's stream first
+    waits for the caller's, and the caller's waits for it at the end, so device inputs and outputs may cross the block."""
+    ctx = default_context()
+    if not torch.cuda.is_available():
+        yield ctx
+        return
+    cur = torch.cuda.current_stream(ctx.device_index)
+    if int(cur.cuda_stream) == int(ctx.stream_handle or 0):
+        yield ctx
+        return
+    own = (torch.cuda.ExternalStream(ctx.stream_handle, device=ctx.device_index) if ctx.stream_handle
+           else torch.cuda.default_stream(ctx.device_index))
+    own.wait_stream(cur)
+    try:
+        with torch.cuda.stream(own):
+            yield ctx
+    finally:
+        cur.wait_stream(own)
 
 
 _owner_device = None

@@ -592,6 +592,12 @@ class TrainStep:
         slices = eng.head_exchange_slices() if hasattr(eng, "head_exchange_slices") else None
         bucketed = self.defer_head_update and (self.world > 1 or FORCE_COLLECTIVES) and slices is not None and not self.native_comm
         works = []
+        # Deferred weight-gradient form of the head backward (engine.head_update_deferred): only where this step's gradient is complete
+        # inside ONE backward program and goes straight into Adam #2 -- one rank, nothing exchanged, no deferred update, and not the
+        # per-GPU batch that runs its images through separate programs and adds their gradients up.
+        fuse_ok = (self.world == 1 and not FORCE_COLLECTIVES and not self.defer_head_update and not self.native_comm
+                   and (bool(st.get("stacked")) or nloc == 1) and hasattr(eng, "head_deferred_ok"))
+        fused_hp = None
 
         def exchange(lo, hi):
             works.append(allreduce_grad_arena_start(eng.head_arena.g[lo:hi], self.world, self.group_head))
@@ -619,7 +625,11 @@ class TrainStep:
                 self._finish_head_update()               # deferred Adam #2 of the previous step: head weights are read next
                 eng.head_forward(hp, training=True, loss_out=self._det_l[slot], group_live=[p is not None for p in picks], **crop_kw)
                 eng.set_accumulate(hp["bwd"], False, prezeroed=True)
-                eng.head_backward(hp, accumulate=True, loss_out=slots, on_part=exchange if bucketed else None)
+                if fuse_ok and eng.head_deferred_ok(hp):
+                    fused_hp = hp
+                    eng.head_backward(hp, accumulate=True, loss_out=slots, defer_wgrad=True)
+                else:
+                    eng.head_backward(hp, accumulate=True, loss_out=slots, on_part=exchange if bucketed else None)
                 for i in det_rows:
                     self._log_losses(self._rpn_l[slot][i], self._det_l[slot][i])
             for i, bp in enumerate(st["plans"] if not st.get("stacked") else []):
@@ -631,7 +641,10 @@ class TrainStep:
                 self._finish_head_update()               # deferred Adam #2 of the previous step: head weights are read next
                 eng.head_forward(hp, training=True, loss_out=self._det_l[slot][n_head], **crop_kw)
                 eng.set_accumulate(hp["bwd"], n_head > 0, prezeroed=True)
-                if bucketed and i == live[-1]:
+                if fuse_ok and eng.head_deferred_ok(hp):
+                    fused_hp = hp
+                    eng.head_backward(hp, accumulate=True, loss_out=self._det_l[slot][n_head], defer_wgrad=True)
+                elif bucketed and i == live[-1]:
                     eng.head_backward(hp, accumulate=True, loss_out=self._det_l[slot][n_head], on_part=exchange)
                 else:
                     eng.head_backward(hp, accumulate=True, loss_out=self._det_l[slot][n_head])
@@ -639,7 +652,9 @@ class TrainStep:
                 n_head += 1
             if n_head > 0 or self.world > 1:
                 self._finish_head_update()               # only still pending when every local image skipped its head phase
-                if bucketed:
+                if fused_hp is not None:                 # the weight gradients, Adam #2 in their epilogue, the Adam tail, the Winograd filters
+                    eng.head_update_deferred(fused_hp, grad_scale=1.0 / ntot)
+                elif bucketed:
                     if not works:                        # every local image skipped its classifier step: the other ranks
                         for lo, hi in slices:            # still exchange slice by slice -- same collectives, zeros from here
                             exchange(lo, hi)
