@@ -199,7 +199,10 @@ int radnet_conv_fwd_pair(radnet_ctx* ctx, const radnet_conv_desc* d1, const radn
  * layer's channels for its rows and goes on with the pointwise convolutions for the same rows through LDS: db->y is NOT written
  * (frozen layers only -- nothing can be differentiated through the block afterwards), dc->y once, da->x is not read back.  Used where it
  * measured faster than the separate launches (decided once per shape, kept in the tuning table); radnet_conv_fwd(db), (dc), (da) -- which
- * do write db->y -- for every other geometry, forced configs, autotuning off, RADNET_NO_BNECK_FUSE=1. */
+ * do write db->y -- for every other geometry, forced configs, autotuning off, RADNET_NO_BNECK_FUSE=1.  The separate launches are what
+ * this call means: a descriptor has no pitch for x, so they read db->y (and dc->y, with da) as a DENSE matrix whatever ldy it was
+ * written with.  The one-launch form is therefore taken only for dense intermediates -- db->ldy == db->n, and dc->ldy == dc->n when da
+ * is given (without da, dc->ldy may be any pitch >= n) -- and only while M * max(dc->ldy, dc->ld_add, da->ldy) * 4 < 2^31. */
 int radnet_conv_bottleneck(radnet_ctx* ctx, const radnet_conv_desc* db, const radnet_conv_desc* dc, const radnet_conv_desc* da);
 
 /* ---- inference convolution on bf16 matrix cores (csrc/conv_bf16.hip) -----------------------------

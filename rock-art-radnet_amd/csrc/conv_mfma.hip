@@ -489,7 +489,11 @@ extern "C" int radnet_conv_bottleneck(radnet_ctx* ctx, const radnet_conv_desc* d
        db->c % BK == 0 && db->oh == db->h && db->ow == db->w_;
   ok = ok && pointwise(dc, db) && dc->n % 64 == 0 && dc->ldw >= dc->n && dc->ldy >= dc->n && (!dc->addend || dc->ld_add >= dc->n);
   ok = ok && (!da || (pointwise(da, dc) && da->n == 64 && !da->addend && da->ldw >= 64 && da->ldy >= 64));
-  ok = ok && (uint64_t)M * (uint64_t)std::max(dc->ldy, dc->ld_add) * 4ull < (1ull << 31);
+  // radnet_conv_desc has no pitch for x: the separate launches read a pitched db->y (dc->y, with da) as a DENSE matrix, the fused kernel
+  // hands the tile on through LDS and never sees the pitch.  Only dense intermediates mean the same thing to both.
+  ok = ok && db->ldy == db->n && (!da || dc->ldy == dc->n);
+  // the tail's byte offsets into dc->y, dc->addend and da->y are 32-bit
+  ok = ok && (uint64_t)M * (uint64_t)std::max(std::max(dc->ldy, dc->ld_add), da ? da->ldy : 0) * 4ull < (1ull << 31);
   if (!ok) return separate();
   GemmArgs g;
   int rc = fwd_args(ctx, db, g);

@@ -849,10 +849,11 @@ def test_copy_bytes_between_pinned_host_and_device(ctx):
 
 
 @pytest.mark.parametrize("case", [(3, 14, 14, 1024, 512, 2048, 2), (1, 21, 30, 256, 128, 512, 2), (2, 9, 11, 64, 64, 96, 1)])
-def test_conv_fwd_pair_equals_the_two_convolutions(ctx, case):
+def test_conv_fwd_pair_equals_the_two_convolutions(ctx, tmp_path, case):
     """radnet_conv_fwd_pair (round 4: branch2a + shortcut conv of a conv_block, same input, as ONE launch where that measures faster):
-    the first call decides (measures the two launches against the paired launch on every tile it has), later calls use the
-    decision; both outputs against the oracle either way, ragged N and M edges included."""
+    the decision is pinned through a tuning-table entry (kind 32) on an autotuning context -- the paired launch on each of its three
+    tiles, then the two launches -- and the class-0 launch count shows which form ran (a context with autotuning off, like this
+    module's, never takes the paired form); both outputs against the oracle either way, ragged N and M edges included."""
     from radnet_hip import lib as L
     from oracle import dense
     nb, h, w, cin, n1, n2, stride = case
@@ -873,12 +874,29 @@ def test_conv_fwd_pair_equals_the_two_convolutions(ctx, case):
         keep += [wd, sd, bd]
         descs.append(conv_desc(L, keep[0], wd, y, nb, h, w, cin, oh, ow, 1, stride, 0, n, n, sd, bd, None, 1 if relu else 0))
         outs.append((y, ref))
-    for rep in range(3):
-        for y, _ in outs:
-            y.fill_(float("nan"))
-        ctx.check(ctx.lib.radnet_conv_fwd_pair(ctx.h, C.byref(descs[0]), C.byref(descs[1])), "conv_fwd_pair")
-        for y, ref in outs:
-            close(y.cpu().numpy(), ref)
+    c2 = L.Context(0)
+    c2.check(c2.lib.radnet_set_workspace(c2.h, ctx._ws.data_ptr(), ctx._ws.numel()), "ws")
+    c2.check(c2.lib.radnet_set_autotune(c2.h, 1), "autotune")
+    c2.timing(True)
+    M = nb * oh * ow
+    singles = "".join("0 %d %d %d %d 1 %d 64 64 1 0.01 4\n" % (M, n, cin, cin, stride) for n in (n1, n2))      # nothing is measured
+    for i, (a, b, slices) in enumerate([(64, 64, 1), (32, 64, 1), (32, 32, 1), (64, 64, 2)]):
+        table = tmp_path / ("t%d.txt" % i)
+        table.write_text("# radnet tuned GEMM launch shapes v2\n%s32 %d %d %d %d 1 %d %d %d %d 0.01 4\n"
+                         % (singles, M, n1 * 65536 + n2, cin, cin, stride, a, b, slices))
+        c2.check(c2.lib.radnet_tune_load(c2.h, str(table).encode()), "tune_load")
+        shapes = c2.lib.radnet_tuned_shapes(c2.h)
+        for rep in range(3):
+            for y, _ in outs:
+                y.fill_(float("nan"))
+            torch.cuda.synchronize()
+            c2.timing_reset()
+            c2.check(c2.lib.radnet_conv_fwd_pair(c2.h, C.byref(descs[0]), C.byref(descs[1])), "conv_fwd_pair")
+            assert c2.timing_read(0)[1] == slices, ("launches", a, b, slices)
+            for y, ref in outs:
+                close(y.cpu().numpy(), ref)
+        assert c2.lib.radnet_tuned_shapes(c2.h) == shapes == 3
+    c2.close()
 
 
 @pytest.mark.parametrize("rows", [64, 32])
