@@ -723,6 +723,54 @@ int radnet_draw_list_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int
 /* Host only (no context, no device, like radnet_png_plan_segments): the 8 row bytes of the glyph of `code`, top row first; the dot
  * of column c is (row >> (4 - c)) & 1.  RADNET_ERR_ARG for a code outside 0x20..0x7E or a null pointer (nothing is written). */
 int radnet_draw_glyph_rows(int32_t code, uint8_t rows[8]);
+/* A SCENE: radnet_draw_list_u8's ordered list with two more kinds and with transparency, painted in one launch by a kernel of
+ * its own (csrc/draw_scene.hip); what the precision/recall figure and the label views need (faster_rcnn/figures.py).  The arguments
+ * and the host / device twin tables are radnet_draw_list_u8's.
+ *   kinds RADNET_PRIM_RECT and RADNET_PRIM_TEXT: exactly radnet_draw_list_u8's pixel sets and checks.
+ *   kind RADNET_PRIM_LINE: the segment from (x1, y1) to (x2, y2); a = t >= 1 the thickness; b the dash: 0 solid, else
+ *     on = b & 0xFFFF and off = (b >> 16) & 0xFFFF, both >= 1.  The line is x-major when |x2 - x1| >= |y2 - y1|, else y-major, and
+ *     the endpoints are ordered by the major coordinate first (a -> b, xa <= xb), so the pixel set does not depend on the order
+ *     they come in.  x-major, for every x in [xa, xb]:  yc = ya + floor((2 (x - xa)(yb - ya) + (xb - xa)) / (2 (xb - xa)))  -- floor
+ *     division, an exact half rounds up; a point (xa = xb) has yc = ya -- and the rows yc - (t - 1) / 2 .. yc + t / 2 are in the
+ *     set (integer division: t pixels across the major direction, no caps beyond the endpoints).  y-major mirrors this.  With a
+ *     dash a pixel of the set is painted iff floormod(its major coordinate, on + off) < on: the phase is the IMAGE's, so the
+ *     pieces of a polyline join without a seam.
+ *   kind RADNET_PRIM_DISC: centre (x1, y1), x2 = r >= 0 the radius, y2 = 0, b = 0.  With D(rho) = {dx^2 + dy^2 <= rho^2 + rho}:
+ *     a < 0 is the filled disc D(r) (r = 0: one pixel); a = t > 0, hw = t / 2, is the ring D(r + hw) minus D(r - hw - 1) when
+ *     r - hw >= 1 and all of D(r + hw) otherwise.
+ *   Line endpoints, disc centres and radii lie within +-RADNET_DRAW_SCENE_MAX_COORD, which keeps every product exact in 64 bits.
+ * TRANSPARENCY: bits 24..31 of bgr are tau; tau = 0 is opaque, so a table radnet_draw_list_u8 accepts means the same here.  A
+ * covered pixel becomes per channel (c * (255 - tau) + d * tau + 127) / 255 in integer division, c the entry's colour and d the
+ * pixel's value after the earlier entries: the entries compose in list order.  One thread owns a pixel, loads it at most once
+ * (when the first translucent entry hits it and no opaque one did before), and stores it once, only if an entry covered it.
+ * Against OpenCV, all unpinned as for the rectangles: cv2.line's thick lines have round caps and its thin ones another rounding;
+ * cv2.circle draws midpoint circles; cv2.addWeighted rounds a float where this rounds an integer quotient.
+ * The host copies are validated by radnet_draw_scene_check before the launch; a violation is RADNET_ERR_ARG naming the entry's
+ * index and nothing is modified: an unknown kind; a line with t < 1, with a dash whose on or off is 0 while b != 0, or with an
+ * endpoint beyond the bound; a disc with a = 0, r < 0, y2 != 0, b != 0 or a centre or radius beyond the bound; what
+ * radnet_draw_list_u8 refuses for rectangles and text, except that bits 24..31 of bgr are allowed; likewise a null pointer, an empty
+ * image and pitch_bytes < 3 * w.  count == 0 is RADNET_OK without a launch, whatever the pointers.
+ * One launch with the tile, batch and cull scheme of radnet_draw_rects_u8; a line is culled by the box of its major extent by its
+ * minor extent widened by the thickness, a disc by the box of its outer radius; every coverage test is O(1) per pixel and entry.
+ * No atomics, no floating point. */
+#define RADNET_PRIM_LINE 2
+#define RADNET_PRIM_DISC 3
+/* 1 << 24 */
+#define RADNET_DRAW_SCENE_MAX_COORD 16777216
+int radnet_draw_scene_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int64_t pitch_bytes, const radnet_prim* prims_host,
+                         const radnet_prim* prims_dev, int32_t count, const uint8_t* chars_host, const uint8_t* chars_dev, int32_t n_chars);
+/* Host only (csrc/draw_scene_check.cpp; no context, no device, like radnet_png_plan_segments): the checks of a scene's table and
+ * character pool stated above.  RADNET_OK, or RADNET_ERR_ARG with the index of the first bad entry in *bad_entry (-1 when the
+ * arguments themselves are at fault: count < 0, a null table with count > 0, n_chars < 0, a null pool with n_chars > 0) and a
+ * sentence naming it in msg (at most msg_cap bytes with the terminator).  bad_entry and msg may be null.  count == 0 is RADNET_OK
+ * whatever the pointers.  Reads exactly count entries and, of the pool, only the runs the text entries refer to. */
+int radnet_draw_scene_check(const radnet_prim* prims, int32_t count, const uint8_t* chars, int32_t n_chars, int32_t* bad_entry, char* msg,
+                            int32_t msg_cap);
+/* cv2.cvtColor(BGR2GRAY) followed by GRAY2BGR as one pointwise launch: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14 (OpenCV's
+ * published 14-bit coefficients) written to all three channels of dst.  src and dst are uint8 [h][w][3] device images with rows
+ * src_pitch and dst_pitch bytes apart (each >= 3 * w; the padding is neither read nor written); src == dst (with equal pitches) is
+ * allowed, any other overlap is not.  A null pointer, h or w below 1 or a short pitch is RADNET_ERR_ARG and nothing is launched. */
+int radnet_grey3_u8(radnet_ctx* ctx, const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int64_t src_pitch, int64_t dst_pitch);
 int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes);
 /* y = x * alpha (n floats); used to average gradients after all-reduce.  n = 0 launches nothing; RADNET_ERR_ARG for n < 0. */
 int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha);

@@ -625,6 +625,97 @@ def draw_list_device(img, prims, inplace=False, ctx=None):
     return AD.hand_over(out, side)
 
 
+PRIM_LINE, PRIM_DISC = 2, 3                                                                      # RADNET_PRIM_LINE, RADNET_PRIM_DISC
+
+
+def scene_table(prims):
+    """(table, chars): radnet_draw_scene_u8's table (PRIM rows) and character pool for a sequence of
+    ("rect", x1, y1, x2, y2, thickness, b, g, r), ("text", x, y, string, scale, b, g, r), ("line", x1, y1, x2, y2, t, b, g, r) and
+    ("disc", cx, cy, radius, t, b, g, r) -- t < 0 fills the disc --, each optionally followed by a dict with "dash": (on, off), lines
+    only, and "transparency": 0..255 (0 opaque).  Host only; include/radnet_hip.h states the pixel sets and the mixing rule."""
+    rows, pool = [], bytearray()
+    for p in prims:
+        opts = {}
+        if len(p) and isinstance(p[-1], dict):
+            p, opts = p[:-1], p[-1]
+        where = "draw_scene_device: entry %d" % len(rows)
+        if set(opts) - {"dash", "transparency"} or ("dash" in opts and p[0] != "line"):
+            raise ValueError("%s (%r) has the options %r" % (where, p[0], sorted(opts)))
+        tau = int(opts.get("transparency", 0))
+        if not 0 <= tau <= 255:
+            raise ValueError("%s has the transparency %d" % (where, tau))
+        if p[0] == "rect":
+            _, x1, y1, x2, y2, thickness, b, g, r = p
+            row = (PRIM_RECT, int(x1), int(y1), int(x2), int(y2), int(thickness), 0)
+        elif p[0] == "text":
+            _, x, y, string, scale, b, g, r = p
+            run = label_bytes(string)
+            row = (PRIM_TEXT, int(x), int(y), int(scale), 0, len(pool), len(run))
+            pool += run
+        elif p[0] == "line":
+            _, x1, y1, x2, y2, thickness, b, g, r = p
+            dash = 0
+            if "dash" in opts:
+                on, off = (int(v) for v in opts["dash"])
+                if not (1 <= on <= 0xFFFF and 1 <= off <= 0xFFFF):
+                    raise ValueError("%s has the dash (%d, %d)" % (where, on, off))
+                dash = on | off << 16
+            row = (PRIM_LINE, int(x1), int(y1), int(x2), int(y2), int(thickness), dash)
+        elif p[0] == "disc":
+            _, cx, cy, radius, thickness, b, g, r = p
+            row = (PRIM_DISC, int(cx), int(cy), int(radius), 0, int(thickness), 0)
+        else:
+            raise ValueError("%s is %r, none of 'rect', 'text', 'line' and 'disc'" % (where, p[0]))
+        rows.append(row[:6] + (_int32(row[6]), _int32(_bgr(b, g, r) | tau << 24)))
+    return np.array(rows, PRIM).reshape(-1), np.frombuffer(bytes(pool), np.uint8)
+
+
+def _int32(v):
+    """The int32 with the bits of a value below 2^32 (a dash or a colour with bit 31 set)."""
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def draw_scene_device(img, prims, inplace=False, ctx=None):
+    """radnet_draw_scene_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): `prims` as scene_table takes
+    them, draw_list_device's rectangles and text plus lines and discs, any of them translucent, painted in order in ONE launch, each
+    entry mixing with what the earlier ones left.  Returns the device image, a clone unless inplace.  An empty list launches nothing.
+    ctx and the stream rules are draw_rects_device's."""
+    import torch
+    from . import augmentation_device as AD
+    if isinstance(img, np.ndarray):
+        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
+    check_device_image(img)
+    table, chars = scene_table(prims)
+    producer = torch.cuda.current_stream()
+    with AD.feed_stream(ctx) as (ctx, side):
+        if side is not None:
+            side.wait_stream(producer)
+        out = img if inplace else img.clone()
+        if len(table):
+            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
+            chars_dev = torch.from_numpy(chars.copy()).cuda() if len(chars) else None
+            ctx.call("radnet_draw_scene_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, table_dev, len(table),
+                     chars.ctypes.data if len(chars) else None, chars_dev, len(chars))
+    return AD.hand_over(out, side)
+
+
+def grey3_device(img, inplace=False, ctx=None):
+    """radnet_grey3_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): cv2.cvtColor(BGR2GRAY) and back to
+    three equal channels in one launch.  Returns the device image, a new one unless inplace."""
+    import torch
+    from . import augmentation_device as AD
+    if isinstance(img, np.ndarray):
+        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
+    check_device_image(img)
+    producer = torch.cuda.current_stream()
+    with AD.feed_stream(ctx) as (ctx, side):
+        if side is not None:
+            side.wait_stream(producer)
+        out = img if inplace else torch.empty_like(img)
+        ctx.call("radnet_grey3_u8", img, out, img.shape[0], img.shape[1], 3 * img.shape[1], 3 * img.shape[1])
+    return AD.hand_over(out, side)
+
+
 def _bgr(b, g, r):
     """b | g << 8 | r << 16 of three colour values in 0..255 (radnet_prim.bgr)."""
     b, g, r = int(b), int(g), int(r)

@@ -282,6 +282,9 @@ def load_library():
         "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
         "radnet_draw_list_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
         "radnet_draw_glyph_rows": (C.c_int, [i32, vp]),
+        "radnet_draw_scene_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
+        "radnet_draw_scene_check": (C.c_int, [vp, i32, vp, i32, C.POINTER(i32), C.c_char_p, i32]),
+        "radnet_grey3_u8": (C.c_int, [vp, vp, vp, i32, i32, i64, i64]),
         "radnet_fill_zero": (C.c_int, [vp, vp, u64]),
         "radnet_copy_bytes": (C.c_int, [vp, vp, vp, C.c_uint64]),
         "radnet_program_run": (C.c_int, [vp, C.POINTER(Op), i32]),
@@ -322,6 +325,20 @@ def glyph_rows(code):
     if rc != 0:
         raise RadnetError("radnet_draw_glyph_rows: no glyph for the code 0x%02X (the font has 0x20..0x7E)" % int(code))
     return bytes(rows)
+
+
+def draw_scene_check(table, chars=b"", count=None, n_chars=None):
+    """radnet_draw_scene_check (host only, no context, no device) on a table of radnet_prim rows -- a NumPy array of 8 int32 per
+    entry, or None for a null table -- and a character pool (bytes, or None for a null pool): (rc, index of the bad entry or -1,
+    the message).  count and n_chars default to the sizes of what is passed."""
+    import numpy as np
+    rows = np.zeros((0, 8), np.int32) if table is None else np.ascontiguousarray(table).view(np.int32).reshape(-1, 8)
+    pool = np.frombuffer(bytes(chars or b""), np.uint8)
+    bad, msg = C.c_int32(-2), C.create_string_buffer(256)
+    rc = load_library().radnet_draw_scene_check(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count),
+                                                pool.ctypes.data if len(pool) else None, len(pool) if n_chars is None else int(n_chars),
+                                                C.byref(bad), msg, len(msg))
+    return rc, bad.value, msg.value.decode()
 
 
 def _ptr(t):
