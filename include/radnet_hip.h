@@ -771,6 +771,51 @@ int radnet_draw_scene_check(const radnet_prim* prims, int32_t count, const uint8
  * src_pitch and dst_pitch bytes apart (each >= 3 * w; the padding is neither read nor written); src == dst (with equal pitches) is
  * allowed, any other overlap is not.  A null pointer, h or w below 1 or a short pitch is RADNET_ERR_ARG and nothing is launched. */
 int radnet_grey3_u8(radnet_ctx* ctx, const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int64_t src_pitch, int64_t dst_pitch);
+/* SCORE MAPS AS PICTURES (csrc/heat.hip): the RPN's objectness over a scan, the imshow + colorbar views of train.py:338-347 and
+ * RADNet.py:362-367 (faster_rcnn/figures.py: objectness_view, score_map_figure).
+ *
+ * radnet_score_levels_u8: fp32 scores to uint8 levels, one level per row of a score matrix (one per feature-map cell of
+ * radnet_rpn_forward's `pred`, ld = 64, the anchors' scores in columns [0, A)).  For every row m < M: s = the maximum of
+ * pred[m * ld + first .. first + count), NaNs skipped as fmaxf skips them; level = clamp(floor(s * 255.0f + 0.5f), 0, 255), the
+ * product and the sum each rounded to fp32 (no FMA); a row of NaNs only gives 0, +inf gives 255, -inf gives 0.  levels[m] is
+ * written for every m < M; nothing else is read or written (not the other columns of a row either).  RADNET_ERR_ARG, naming what
+ * is wrong, for a null pointer, M < 1, first < 0, count < 1 or ld < first + count; nothing is launched then. */
+int radnet_score_levels_u8(radnet_ctx* ctx, const float* pred, int32_t ld, int32_t M, int32_t first, int32_t count, uint8_t* levels);
+/* radnet_heat_paint_u8: uint8 maps from a byte pool painted through a colour table into a uint8 [h][w][3] device image (rows
+ * pitch_bytes apart) IN PLACE, in one launch.  A placement holds a destination rectangle [x0, x0 + w) x [y0, y0 + h) in image
+ * pixels, which may leave the image on any side, and a map of mh rows of mw bytes at pool + offset.  For the pixel (X, Y) of the
+ * image: every placement whose rectangle holds it gives the map byte at row ((Y - y0) * mh) / h, column ((X - x0) * mw) / w (floor
+ * division, the operands are never negative): nearest cells, no interpolation.  The pixel's level is the MAXIMUM over those
+ * placements, which does not depend on their order: overlapping tiles need no ordering and no atomics.  A pixel no placement holds,
+ * or whose level is below min_level, is not written (nor is the pitch padding).  Otherwise with c = lut_bgr[3 * level ..] (b, g, r)
+ * every channel becomes (c * (255 - tau) + d * tau + 127) / 255, d the pixel's value: radnet_draw_scene_u8's mix; tau = 0 stores c
+ * without loading the pixel.  A pixel is loaded at most once and stored at most once.
+ * img, pool (pool_len bytes), places_dev and lut_bgr (256 * 3 bytes) are device pointers; places_host holds the SAME table on the
+ * host (the caller uploads it; this entry copies nothing) and is validated by radnet_heat_check before the launch.  A violation
+ * there, a null pointer, an empty image, pool_len < 0, tau or min_level outside 0..255 or pitch_bytes < 3 * w is RADNET_ERR_ARG
+ * naming what is wrong, and nothing is modified.  count == 0 is RADNET_OK without a launch, whatever the pointers.
+ * One launch with the tile, batch and cull scheme of radnet_draw_rects_u8 (a workgroup per 32 x 8 pixels, the table through LDS in
+ * batches of RADNET_DRAW_RECT_BATCH entries culled against the tile); the colour table sits in LDS; integers only. */
+typedef struct radnet_heat_place {
+  int32_t x0, y0, w, h; /* the destination rectangle */
+  int32_t mw, mh;       /* the map's columns and rows */
+  int64_t offset;       /* of the map's first byte in the pool */
+} radnet_heat_place;    /* 32 bytes */
+/* 1 << 20 */
+#define RADNET_HEAT_MAX_EXTENT 1048576
+#define RADNET_HEAT_MAX_MAP 2047
+int radnet_heat_paint_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int64_t pitch_bytes, const uint8_t* pool, int64_t pool_len,
+                         const radnet_heat_place* places_host, const radnet_heat_place* places_dev, int32_t count, const uint8_t* lut_bgr,
+                         int32_t tau, int32_t min_level);
+/* Host only (csrc/heat_check.cpp; no context, no device, like radnet_draw_scene_check): the checks of a placement table for an
+ * image of h x w pixels and a pool of pool_len bytes.  Per entry 1 <= w, h <= RADNET_HEAT_MAX_EXTENT and 1 <= mw, mh <=
+ * RADNET_HEAT_MAX_MAP (every product of the cell formula then fits 31 bits), |x0|, |y0| <= RADNET_DRAW_SCENE_MAX_COORD, offset >= 0
+ * and offset + mw * mh <= pool_len.  RADNET_OK, or RADNET_ERR_ARG with the index of the first bad entry in *bad_entry (-1 when the
+ * arguments themselves are at fault: count < 0, a null table with count > 0, pool_len < 0, h or w below 1) and a sentence naming
+ * the entry and the field in msg (at most msg_cap bytes with the terminator).  bad_entry and msg may be null.  count == 0 with
+ * sound arguments is RADNET_OK whatever the table pointer.  Reads exactly count entries. */
+int radnet_heat_check(const radnet_heat_place* places, int32_t count, int64_t pool_len, int32_t h, int32_t w, int32_t* bad_entry, char* msg,
+                      int32_t msg_cap);
 int radnet_fill_zero(radnet_ctx* ctx, void* p, uint64_t bytes);
 /* y = x * alpha (n floats); used to average gradients after all-reduce.  n = 0 launches nothing; RADNET_ERR_ARG for n < 0. */
 int radnet_scale(radnet_ctx* ctx, float* x, int64_t n, float alpha);

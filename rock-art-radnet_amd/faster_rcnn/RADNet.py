@@ -4,6 +4,7 @@
     .predict(images) -> [{'class','prob','x1','y1','x2','y2'}, ...]     RADNet.py:502-718
     .predict_from_path(path)                                           RADNet.py:482-500
     .draw_detections(img, dets) / .write_predictions(dets, img, dir)   predict.py:90-181 (boxes and files; no text labels)
+    .predict_region_proposals(img) / .objectness_maps(img)             RADNet.py:310-480 (the RPN alone; score maps as levels)
     .format_img / .apply_spatial_pyramid_pooling / .final_nms / .get_real_coordinates
     load_radnet(config_path)                                           RADNet.py:721-775
 
@@ -106,18 +107,21 @@ class RADNet():
         """Back to source-image pixels: floor-division by the resize ratio, then round (RADNet.py:44-51)."""
         return tuple(int(round(v // ratio)) for v in (x1, y1, x2, y2))
 
+    def _network_size(self, height, width):
+        """(ratio, new_w, new_h) of RADNet.py:53-74 for an image of height x width: short side -> C.img_size, long side truncated."""
+        side = float(self.C.img_size)
+        if width <= height:
+            ratio = side / width
+            return ratio, int(side), int(ratio * height)
+        ratio = side / height
+        return ratio, int(ratio * width), int(side)
+
     def format_img_size(self, img, keep_on_device=False, ctx=None):
         """Short side -> C.img_size, long side truncated (RADNet.py:53-74); bicubic resize on the device.
         keep_on_device: return the resized uint8 image as a device tensor (the device-resident tile path).  An ImageWindow (a tile
         of an image that is already on the device) becomes one resize_cubic_window launch on the lane this is called from."""
-        side = float(self.C.img_size)
         height, width = img.shape[:2]
-        if width <= height:
-            ratio = side / width
-            new_w, new_h = int(side), int(ratio * height)
-        else:
-            ratio = side / height
-            new_w, new_h = int(ratio * width), int(side)
+        ratio, new_w, new_h = self._network_size(height, width)
         if isinstance(img, ImageWindow):
             if not keep_on_device:
                 raise TypeError("format_img_size: an ImageWindow is resized on the device (keep_on_device=True)")
@@ -463,6 +467,92 @@ class RADNet():
             images = [utils_io.get_image(img_path, C.img_types, random_type=False, to_host=to_host)]
         return self.predict(images)
 
+    # ---- the RPN alone: objectness maps and proposals over a scan (RADNet.py:310-480, train.py:338-347) ------------------------
+    def _rpn_walk(self, img, what):
+        """The windows of predict's walk for the two RPN-only passes: (engine, device image, windows, offsets).  Engine-backed
+        models only; `img` is a NumPy array, uploaded once, or a device image (check_device_image)."""
+        eng = self._engine()
+        if eng is None or not hasattr(self.model_rpn, "propose_launch") or not hasattr(eng, "main_stream"):
+            raise TypeError("%s needs the engine-backed models of load_radnet / models.build_models: it reads the RPN's scores on the device, and "
+                            "there is no CPU fallback for duck-typed models" % what)
+        if isinstance(img, np.ndarray):
+            import torch
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+                raise ValueError("%s: a host image must be a uint8 [H][W][3] array, not %s %s" % (what, img.dtype, img.shape))
+            img = torch.from_numpy(np.ascontiguousarray(img)).cuda()
+        else:
+            check_device_image(img)
+        work, offs = tile_windows(img, self.C, eng.mark())      # the image's bytes are valid behind the caller's stream up to here
+        return eng, img, work, offs
+
+    def objectness_maps(self, img, anchors=None):
+        """Where the RPN believes there is an object: per window of predict's walk (tile_windows: the tiles in the reference's
+        order, then the full image when C.include_full_img) the maximum sigmoid score over the anchors `anchors` -- None: all A
+        of them; or a (first, count) range -- of every feature-map cell, as a uint8 level (radnet_score_levels_u8:
+        floor(s * 255 + 0.5), figures.to_levels).  Returns a ScoreMaps: every window's [fh][fw] map in one device pool, and the
+        placements that lay them over the scan (figures.objectness_view, heat_paint_device).  The passes run on the engine's main
+        stream, on one lane, one window after the other; nothing but the maps, a few KB each, ever needs to come down (to_host())."""
+        import torch
+        eng, img, work, offs = self._rpn_walk(img, "objectness_maps")
+        first, count = (0, eng.A) if anchors is None else (int(anchors[0]), int(anchors[1]))
+        if first < 0 or count < 1 or first + count > eng.A:
+            raise ValueError("objectness_maps: the anchors [%d, %d + %d) of %d" % (first, first, count, eng.A))
+        from radnet_hip.engine import RPN_LD
+        with torch.cuda.stream(eng.main_stream):
+            sizes = []
+            for win in work:                                    # the plans know their feature maps before anything runs
+                _, new_w, new_h = self._network_size(win.wh, win.ww)
+                bp = eng._plan_base(1, new_h, new_w, 0)
+                sizes.append((bp["fh"], bp["fw"]))
+            places, total = score_map_places(work, sizes)
+            pool = torch.empty(max(1, total), dtype=torch.uint8, device=img.device)
+            for win, (fh, fw), place in zip(work, sizes, places):
+                start = place[6]
+                img_dev, _ = self.format_img_size(win, keep_on_device=True, ctx=eng.ctx)
+                rp = eng.rpn_forward(self.model_rpn._s.base_from_u8(img_dev, 0))
+                assert (rp["fh"], rp["fw"]) == (fh, fw)
+                # enqueued on the stream the forward ran on, so it reads rp["pred"] before the next window's forward -- the same
+                # plan and the same buffer whenever two windows have one size -- overwrites it
+                eng.ctx.call("radnet_score_levels_u8", rp["pred"], RPN_LD, fh * fw, first, count, pool[start:start + fh * fw])
+            # the buffer sets are predict's: its side lane does not wait for this stream, so the pass is over when this returns
+            eng.main_stream.synchronize()
+        pool.record_stream(torch.cuda.current_stream())
+        return ScoreMaps(pool, places, tuple(int(v) for v in img.shape[:2]))
+
+    def predict_region_proposals(self, img, gt_bboxes=None):
+        """RADNet.py:310-480 made to run: what the RPN proposes over a scan, without the classifier.  The walk is predict's
+        (tile_windows); per window the base network, the RPN and rpn_to_roi with overlap_thresh 0.7 run on the device, the valid
+        proposals and their scores come down, the boxes are multiplied by C.rpn_stride, passed through
+        get_real_coordinates(ratio, ...) and moved by the window's offset.  Returns
+        [{'class': 'object', 'prob': np.float32, 'x1': np.int64, 'y1': .., 'x2': .., 'y2': ..}, ...] in window order, then in
+        proposal order (best score first); a window with no valid box contributes nothing.  Engine-backed models only.
+        Deviations from the reference, on purpose:
+          * `prob` is the proposal's RPN score where the reference writes 1.0;
+          * the full-image branch uses the same x1, y1, x2, y2 times stride arithmetic as the tiles, where the reference's branch
+            mixes x, y, w, h without the stride and zeroes the scores of anchors 6..8;
+          * `gt_bboxes` is accepted for call compatibility and unused: its only consumer upstream is get_map, which is not
+            defined there (the reason the reference's own driver, test_rpn.py, cannot run), so only the list is returned;
+          * no matplotlib pop-ups: figures.score_map_figure and figures.objectness_view draw the score maps, on request."""
+        import torch
+        eng, img, work, offs = self._rpn_walk(img, "predict_region_proposals")
+        stride = self.C.rpn_stride
+        dets = []
+        with torch.cuda.stream(eng.main_stream):
+            for win, (ox, oy) in zip(work, offs):
+                img_dev, ratio = self.format_img_size(win, keep_on_device=True, ctx=eng.ctx)
+                rp = eng.rpn_forward(self.model_rpn._s.base_from_u8(img_dev, 0))
+                R, Rn = eng.proposals(rp, overlap_thresh=0.7)
+                n = int(Rn.cpu()[0])                            # waits for this window: the next one reuses R, Rp and Rn
+                if n <= 0:
+                    continue
+                boxes, scores = R[:n].cpu().numpy() * stride, rp["Rp"][:n].cpu().numpy()
+                for (x1, y1, x2, y2), p in zip(boxes, scores):
+                    rx1, ry1, rx2, ry2 = self.get_real_coordinates(ratio, x1, y1, x2, y2)
+                    dets.append({'class': 'object', 'prob': np.float32(p), 'x1': np.int64(ox + rx1), 'y1': np.int64(oy + ry1),
+                                 'x2': np.int64(ox + rx2), 'y2': np.int64(oy + ry2)})
+            eng.main_stream.synchronize()
+        return dets
+
     # ---- the outputs of the predict driver (predict.py:90-181) -----------------------------------------------
     PREDICTION_MAPS = (("all_predictions.png", (255, 255, 255), None),
                        ("boat_predictions.png", (28, 26, 228), ("boat",)),
@@ -713,6 +803,88 @@ def grey3_device(img, inplace=False, ctx=None):
             side.wait_stream(producer)
         out = img if inplace else torch.empty_like(img)
         ctx.call("radnet_grey3_u8", img, out, img.shape[0], img.shape[1], 3 * img.shape[1], 3 * img.shape[1])
+    return AD.hand_over(out, side)
+
+
+HEAT_PLACE = np.dtype([(k, np.int32) for k in ("x0", "y0", "w", "h", "mw", "mh")] + [("offset", np.int64)])      # radnet_heat_place, 32 bytes
+
+
+class ScoreMaps:
+    """What RADNet.objectness_maps returns.  pool: a device uint8 tensor, the windows' level maps one after the other; places: per
+    window the tuple (x0, y0, w, h, fw, fh, offset) heat_table takes -- the window's rectangle in scan pixels, its map of fh rows of
+    fw levels and where that starts in the pool; shape: (H, W) of the scan."""
+    __slots__ = ("pool", "places", "shape")
+
+    def __init__(self, pool, places, shape):
+        self.pool, self.places, self.shape = pool, [tuple(int(v) for v in p) for p in places], tuple(shape)
+
+    def to_host(self):
+        """The maps as a list of [fh][fw] uint8 arrays, in window order: one download of the pool."""
+        flat = self.pool.cpu().numpy()
+        return [flat[off:off + fh * fw].reshape(fh, fw).copy() for (_, _, _, _, fw, fh, off) in self.places]
+
+
+def score_map_places(windows, sizes):
+    """(places, pool length) for the windows of tile_windows and their feature maps' (fh, fw): per window the placement
+    (x0, y0, ww, wh, fw, fh, offset) that lays its map over its rectangle of the scan, the maps one after the other.  Host only."""
+    places, total = [], 0
+    for win, (fh, fw) in zip(windows, sizes):
+        places.append((win.x0, win.y0, win.ww, win.wh, int(fw), int(fh), total))
+        total += int(fh) * int(fw)
+    return places, total
+
+
+def heat_table(places):
+    """radnet_heat_paint_u8's table (HEAT_PLACE rows, 32 bytes each) for a sequence of (x0, y0, w, h, mw, mh, offset): the
+    destination rectangle [x0, x0 + w) x [y0, y0 + h) in image pixels, the map's columns and rows, its first byte in the pool.
+    Host only; include/radnet_hip.h states the pixel rule."""
+    rows = []
+    for p in places:
+        if len(p) != 7:
+            raise ValueError("heat_paint_device: entry %d has %d values, not (x0, y0, w, h, mw, mh, offset)" % (len(rows), len(p)))
+        rows.append(tuple(int(v) for v in p))
+    return np.array(rows, HEAT_PLACE).reshape(-1)
+
+
+def heat_paint_device(img, pool, places, lut=None, transparency=0, min_level=0, inplace=False, ctx=None):
+    """radnet_heat_paint_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): the maps of `places`
+    (heat_table's tuples) out of `pool` -- a uint8 cuda tensor, or host bytes / a NumPy array, which are uploaded -- through the colour
+    table `lut` (256 x 3 uint8 (b, g, r); None: figures.heat_lut()), in ONE launch: a pixel takes the maximum level of the placements
+    that hold it, nearest cells; below min_level it stays as it is, else the colour is mixed in with `transparency` 0..255 (0
+    opaque).  Returns the device image, a clone unless inplace.  An empty list launches nothing.  ctx and the stream rules are
+    draw_rects_device's."""
+    import torch
+    from . import augmentation_device as AD
+    if isinstance(img, np.ndarray):
+        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
+    check_device_image(img)
+    table = heat_table(places)
+    tau, min_level = int(transparency), int(min_level)
+    if not 0 <= tau <= 255:
+        raise ValueError("heat_paint_device: the transparency %d" % tau)
+    if not 0 <= min_level <= 255:
+        raise ValueError("heat_paint_device: min_level = %d" % min_level)
+    if lut is None:
+        from . import figures
+        lut = figures.heat_lut()
+    lut = np.ascontiguousarray(lut)
+    if lut.dtype != np.uint8 or lut.shape != (256, 3):
+        raise ValueError("heat_paint_device: the colour table must be 256 x 3 uint8, not %s %s" % (lut.shape, lut.dtype))
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda):
+        host = np.frombuffer(bytes(pool), np.uint8) if isinstance(pool, (bytes, bytearray)) else np.ascontiguousarray(pool, dtype=np.uint8).reshape(-1)
+        pool = torch.from_numpy(host.copy()).cuda() if len(host) else torch.zeros(1, dtype=torch.uint8, device=img.device)[:0]
+    if pool.dtype != torch.uint8 or not pool.is_contiguous():
+        raise TypeError("heat_paint_device: the pool must be a contiguous uint8 tensor, not %s" % (pool.dtype,))
+    producer = torch.cuda.current_stream()
+    with AD.feed_stream(ctx) as (ctx, side):
+        if side is not None:
+            side.wait_stream(producer)
+        out = img if inplace else img.clone()
+        if len(table):
+            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
+            lut_dev = torch.from_numpy(lut.reshape(-1).copy()).cuda()
+            ctx.call("radnet_heat_paint_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], pool, pool.numel(), table.ctypes.data, table_dev, len(table),
+                     lut_dev, tau, min_level)
     return AD.hand_over(out, side)
 
 

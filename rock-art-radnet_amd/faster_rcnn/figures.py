@@ -3,7 +3,10 @@ lines, discs, rectangles and text painted in list order in ONE launch, transluce
 
   * the precision/recall figure of the test driver (test.py:231-256): precision_recall_scene lays it out on the host,
     precision_recall_figure paints it on the device; evaluate.evaluate_scans(pr_plot=True) writes it to viz/precision_recall.png;
-  * the label sanity views of test_data.py:214-318: positive_anchor_view and ground_truth_view.
+  * the label sanity views of test_data.py:214-318: positive_anchor_view and ground_truth_view;
+  * the score-map views of train.py:338-347 and RADNet.py:362-367 (imshow + colorbar per anchor): score_map_figure, and what they
+    were looked at for, the RPN's objectness over a whole scan: objectness_view over RADNet.objectness_maps.  These go through
+    radnet_heat_paint_u8 (RADNet.heat_paint_device): uint8 level maps through a colour table, nearest cells, the package's own ramp.
 
 What differs from the reference's pictures, on purpose and unpinned: the text is the package's own dot-matrix font (no Hershey, no
 TrueType, and NO ROTATED TEXT: the precision label stands horizontally above the top-left corner of the axes, where matplotlib writes it
@@ -110,6 +113,103 @@ def precision_recall_figure(curves, mAP, size=1200, ctx=None):
     prims = precision_recall_scene(curves, mAP, size)
     canvas = torch.full((int(size), int(size), 3), 255, dtype=torch.uint8, device="cuda")
     return R.draw_scene_device(canvas, prims, inplace=True, ctx=ctx)
+
+
+# ---- score maps: the imshow + colorbar views of train.py:338-347 and RADNet.py:362-367, and the objectness of a whole scan ------------
+# (level, b, g, r): the package's own ramp from dark violet over blue and green to yellow, rising in luma so that it reads in grey
+# too.  It follows the idea of matplotlib's viridis and is unpinned against it: not its table, not its 256 colours.
+HEAT_ANCHORS = ((0, 84, 4, 68), (85, 140, 90, 50), (170, 100, 180, 60), (255, 40, 230, 250))
+
+
+def heat_lut(anchors=HEAT_ANCHORS):
+    """The 256 x 3 uint8 (b, g, r) colour table of radnet_heat_paint_u8, interpolated in integers between the (level, b, g, r)
+    anchors: (c0 * (l1 - l) + c1 * (l - l0) + (l1 - l0) // 2) // (l1 - l0) for l0 <= l <= l1.  The anchors' levels rise strictly
+    from 0 to 255."""
+    anchors = [tuple(int(v) for v in a) for a in anchors]
+    levels = [a[0] for a in anchors]
+    if len(anchors) < 2 or levels[0] != 0 or levels[-1] != 255 or any(b <= a for a, b in zip(levels[:-1], levels[1:])):
+        raise ValueError("heat_lut: the anchors' levels must rise strictly from 0 to 255, not %r" % (levels,))
+    if any(len(a) != 4 or not all(0 <= c <= 255 for c in a[1:]) for a in anchors):
+        raise ValueError("heat_lut: an anchor is (level, b, g, r) with colours in 0..255")
+    lut = np.zeros((256, 3), np.uint8)
+    for (l0, *c0), (l1, *c1) in zip(anchors[:-1], anchors[1:]):
+        for level in range(l0, l1 + 1):
+            lut[level] = [(a * (l1 - level) + b * (level - l0) + (l1 - l0) // 2) // (l1 - l0) for a, b in zip(c0, c1)]
+    return lut
+
+
+def to_levels(values):
+    """radnet_score_levels_u8's level rule for host arrays: clamp(floor(v * 255 + 0.5), 0, 255) with the product and the sum each
+    rounded to float32; NaN gives 0.  uint8, the shape of `values`."""
+    v = np.asarray(values, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = np.floor((v * np.float32(255.0)).astype(np.float32) + np.float32(0.5))
+    return np.where(t >= 0, np.minimum(t, np.float32(255.0)), np.float32(0.0)).astype(np.uint8)      # NaN compares false
+
+
+def objectness_view(img, maps, transparency=102, min_level=0, grey=True, lut=None, ctx=None):
+    """The RPN's objectness over a scan: a grey copy of `img` (radnet_grey3_u8; grey=False: a plain copy) with the maps of
+    RADNet.objectness_maps(img) laid over their windows in ONE radnet_heat_paint_u8 launch -- where windows overlap the larger
+    level shows, a cell covers its share of the window (nearest cells, no interpolation), levels below min_level leave the scan
+    visible.  Returns a new device image; img (a cuda tensor, or a NumPy array, which is uploaded) stays as it was."""
+    from . import RADNet as R
+    if tuple(img.shape[:2]) != tuple(maps.shape):
+        raise ValueError("objectness_view: maps of a %s scan over an image of %s" % (tuple(maps.shape), tuple(img.shape[:2])))
+    base = R.grey3_device(img, ctx=ctx) if grey else img                  # grey3_device makes a new image, heat_paint_device a clone
+    return R.heat_paint_device(base, maps.pool, maps.places, lut=lut, transparency=transparency, min_level=min_level, inplace=bool(grey), ctx=ctx)
+
+
+def score_map_scene(shape, title="", size=600):
+    """Where the parts of the size x size score-map figure stand, for a map of shape (mh, mw).  Host only.  Returns a dict:
+    `map` and `bar`, the destination rectangles (x0, y0, w, h) of the map -- the largest one of the map's aspect ratio inside the
+    axes area, centred in it -- and of the colour bar to its right, as tall as the map; `prims`, the scene list painted over
+    them: the two frames, the bar's ticks and labels 0.0 .. 1.0 (1.0 at the top) and the title, centred above the map."""
+    mh, mw = (int(v) for v in shape)
+    n = int(size)
+    if mh < 1 or mw < 1:
+        raise ValueError("score_map_scene: a map of %d x %d" % (mh, mw))
+    if n < 120:
+        raise ValueError("score_map_scene: a figure of %d pixels has no room for its labels" % n)
+    unit, s = max(1, n // 600), max(1, n // 300)
+    ax0, ax1, ay0, ay1 = int(round(0.08 * n)), int(round(0.72 * n)), int(round(0.14 * n)), int(round(0.92 * n))
+    aw, ah = ax1 - ax0, ay1 - ay0
+    if aw * mh <= ah * mw:                                   # the width binds
+        w, h = aw, max(1, (aw * mh + mw // 2) // mw)
+    else:
+        w, h = max(1, (ah * mw + mh // 2) // mh), ah
+    x0, y0 = ax0 + (aw - w) // 2, ay0 + (ah - h) // 2
+    bx0, bw = int(round(0.78 * n)), max(2, int(round(0.04 * n)))
+    tick = max(2, n // 200)
+    prims = [("rect", x0 - unit, y0 - unit, x0 + w - 1 + unit, y0 + h - 1 + unit, unit) + BLACK,
+             ("rect", bx0 - unit, y0 - unit, bx0 + bw - 1 + unit, y0 + h - 1 + unit, unit) + BLACK]
+    for k in range(6):
+        label = "%.1f" % (k / 5)
+        py = int(to_pixels([k / 5], y0, h, flip=True)[0])
+        prims.append(("line", bx0 + bw, py, bx0 + bw + tick, py, unit) + BLACK)
+        prims.append(("text", bx0 + bw + tick + 2 * s, py + 3 * s, label, s) + BLACK)
+    if title:
+        prims.append(("text", max(0, x0 + w // 2 - _text_width(str(title), s) // 2), max(8 * s, y0 - 4 * s - unit), str(title), s) + BLACK)
+    return dict(size=n, map=(x0, y0, w, h), bar=(bx0, y0, bw, h), prims=prims)
+
+
+def score_map_figure(values, title="", size=600, lut=None, ctx=None):
+    """The imshow + colorbar view of one score map (train.py:338-347, RADNet.py:362-367) on the device: `values`, a [mh][mw] array
+    of scores in [0, 1] (say Y1[0, :, :, i]), through to_levels; a white size x size canvas; ONE radnet_heat_paint_u8 launch that
+    places the map in the axes box (aspect ratio kept, nearest cells) and a 256-level ramp beside it as the colour bar; ONE
+    radnet_draw_scene_u8 launch for the frames, the ticks and the title (score_map_scene).  Returns the device image
+    (utils_io.imwrite writes it).  Not matplotlib's picture: the package's own ramp and font, no interpolation, no window."""
+    import torch
+    from . import RADNet as R
+    levels = to_levels(values.cpu().numpy() if hasattr(values, "cpu") else values)
+    if levels.ndim != 2:
+        raise ValueError("score_map_figure: a map has rank 2, not %d" % levels.ndim)
+    mh, mw = levels.shape
+    scene = score_map_scene((mh, mw), title, size)
+    pool = np.concatenate([levels.reshape(-1), np.arange(255, -1, -1, dtype=np.uint8)])      # the bar: 256 rows of one level, 255 on top
+    places = [scene["map"] + (mw, mh, 0), scene["bar"] + (1, 256, mh * mw)]
+    canvas = torch.full((scene["size"], scene["size"], 3), 255, dtype=torch.uint8, device="cuda")
+    canvas = R.heat_paint_device(canvas, pool, places, lut=lut, inplace=True, ctx=ctx)
+    return R.draw_scene_device(canvas, scene["prims"], inplace=True, ctx=ctx)
 
 
 def positive_anchor_scene(Y, C, n_pos):

@@ -285,6 +285,9 @@ def load_library():
         "radnet_draw_scene_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
         "radnet_draw_scene_check": (C.c_int, [vp, i32, vp, i32, C.POINTER(i32), C.c_char_p, i32]),
         "radnet_grey3_u8": (C.c_int, [vp, vp, vp, i32, i32, i64, i64]),
+        "radnet_score_levels_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
+        "radnet_heat_paint_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, i64, vp, vp, i32, vp, i32, i32]),
+        "radnet_heat_check": (C.c_int, [vp, i32, i64, i32, i32, C.POINTER(i32), C.c_char_p, i32]),
         "radnet_fill_zero": (C.c_int, [vp, vp, u64]),
         "radnet_copy_bytes": (C.c_int, [vp, vp, vp, C.c_uint64]),
         "radnet_program_run": (C.c_int, [vp, C.POINTER(Op), i32]),
@@ -338,6 +341,18 @@ def draw_scene_check(table, chars=b"", count=None, n_chars=None):
     rc = load_library().radnet_draw_scene_check(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count),
                                                 pool.ctypes.data if len(pool) else None, len(pool) if n_chars is None else int(n_chars),
                                                 C.byref(bad), msg, len(msg))
+    return rc, bad.value, msg.value.decode()
+
+
+def heat_check(table, pool_len, h, w, count=None):
+    """radnet_heat_check (host only, no context, no device) on a table of radnet_heat_place rows -- a NumPy array of 32 bytes per
+    entry, or None for a null table -- for an image of h x w pixels and a pool of pool_len bytes: (rc, index of the bad entry or
+    -1, the message).  count defaults to the table's length."""
+    import numpy as np
+    rows = np.zeros((0, 32), np.uint8) if table is None else np.ascontiguousarray(table).view(np.uint8).reshape(-1, 32)
+    bad, msg = C.c_int32(-2), C.create_string_buffer(256)
+    rc = load_library().radnet_heat_check(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(pool_len), int(h),
+                                          int(w), C.byref(bad), msg, len(msg))
     return rc, bad.value, msg.value.decode()
 
 
