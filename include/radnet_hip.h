@@ -723,8 +723,8 @@ int radnet_draw_list_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int
 /* Host only (no context, no device, like radnet_png_plan_segments): the 8 row bytes of the glyph of `code`, top row first; the dot
  * of column c is (row >> (4 - c)) & 1.  RADNET_ERR_ARG for a code outside 0x20..0x7E or a null pointer (nothing is written). */
 int radnet_draw_glyph_rows(int32_t code, uint8_t rows[8]);
-/* A SCENE: radnet_draw_list_u8's ordered list with two more kinds and with transparency, painted in one launch by a kernel of
- * its own (csrc/draw_scene.hip); what the precision/recall figure and the label views need (faster_rcnn/figures.py).  The arguments
+/* A SCENE: radnet_draw_list_u8's ordered list with two more kinds and with transparency, painted in one launch by an instantiation
+ * of its own of the painters' kernel body (csrc/draw.hip); what the precision/recall figure and the label views need (faster_rcnn/figures.py).  The arguments
  * and the host / device twin tables are radnet_draw_list_u8's.
  *   kinds RADNET_PRIM_RECT and RADNET_PRIM_TEXT: exactly radnet_draw_list_u8's pixel sets and checks.
  *   kind RADNET_PRIM_LINE: the segment from (x1, y1) to (x2, y2); a = t >= 1 the thickness; b the dash: 0 solid, else

@@ -3,12 +3,13 @@
 // include/radnet_hip.h; the placement table is validated on the host by heat_check.cpp.  Compiled with -ffp-contract=off like the
 // other exact units: the level rule rounds its product and its sum separately; the painter has no floating point at all.
 //
-// heat_paint_kernel keeps the scheme of draw_scene_kernel: one workgroup per tile of kDrawTileW x kDrawTileH pixels, one pixel per
-// thread, the table streamed through LDS in batches of RADNET_DRAW_RECT_BATCH entries, thread j marking whether entry j of the batch
-// can touch the tile (uniform over the workgroup, so the walk does not diverge on it).  What a pixel keeps while it walks the table is
-// the MAXIMUM level of the placements that hold it, which no order of the table changes.  After the last batch a pixel that was held
-// and whose level reaches min_level looks its colour up in the table in LDS, loads its three bytes if the mix needs them, and stores
-// once; no atomics, one writer.
+// heat_paint_kernel keeps the scheme of draw.hip's draw_kernel and shares its helpers and its host prologue (draw_device.h): one workgroup
+// per tile of kDrawTileW x kDrawTileH pixels, one pixel per thread, the table streamed through LDS in batches of RADNET_DRAW_RECT_BATCH
+// entries, thread j marking whether entry j of the batch can touch the tile (uniform over the workgroup, so the walk does not diverge on
+// it).  It is a kernel of its own because what a pixel keeps while it walks the table is not a value in table order but the MAXIMUM
+// level of the placements that hold it, which no order of the table changes, and because of its epilogue: after the last batch a pixel
+// that was held and whose level reaches min_level looks its colour up in the table in LDS, loads its three bytes if the mix needs them,
+// and stores once; no atomics, one writer.
 //
 // The cell of a pixel: (X - x0) < w <= 2^20 and mw <= 2047 < 2^11, so (X - x0) * mw < 2^31 in unsigned arithmetic, and the operands
 // are never negative inside the rectangle, so unsigned division is floor division.  x0 + w stays inside int32 (|x0| <= 2^24).
@@ -75,16 +76,7 @@ __global__ void __launch_bounds__(kDrawBatch) heat_paint_kernel(uint8_t* img, in
   }
   if (level < 0 || level < min_level) return;        // level >= 0 only for a pixel inside the image
   int value = lut[3 * level] | (lut[3 * level + 1] << 8) | (lut[3 * level + 2] << 16);
-  if (tau != 0) {
-    const uint8_t* px = img + (long long)y * pitch + (long long)x * 3;
-    const int d = px[0] | (px[1] << 8) | (px[2] << 16);
-    int out = 0;
-    for (int k = 0; k < 24; k += 8) {                // per channel (c (255 - tau) + d tau + 127) / 255, the scene painter's mix
-      const unsigned cc = ((unsigned)value >> k) & 255u, dd = ((unsigned)d >> k) & 255u;
-      out |= (int)((cc * (255u - (unsigned)tau) + dd * (unsigned)tau + 127u) / 255u) << k;
-    }
-    value = out;
-  }
+  if (tau != 0) value = draw_mix(value, draw_load_bgr(img, pitch, x, y), (unsigned)tau);
   draw_store_bgr(img, pitch, x, y, value);
 }
 
@@ -105,22 +97,18 @@ extern "C" int radnet_score_levels_u8(radnet_ctx* ctx, const float* pred, int32_
 extern "C" int radnet_heat_paint_u8(radnet_ctx* ctx, uint8_t* img, int32_t h, int32_t w, int64_t pitch_bytes, const uint8_t* pool, int64_t pool_len,
                                     const radnet_heat_place* places_host, const radnet_heat_place* places_dev, int32_t count, const uint8_t* lut_bgr,
                                     int32_t tau, int32_t min_level) {
-  if (!ctx) return RADNET_ERR_ARG;
-  if (count < 0) RADNET_FAIL(ctx, RADNET_ERR_ARG, "heat_paint: %d placements", count);
-  if (count == 0) return RADNET_OK;
-  if (!img || !pool || !places_host || !places_dev || !lut_bgr || h <= 0 || w <= 0)
-    RADNET_FAIL(ctx, RADNET_ERR_ARG,
-                "heat_paint: a null image, pool, table or colour table, or an empty image (image %p of %d x %d, pool %p, host table %p, device table %p, colours %p)",
-                (void*)img, h, w, (const void*)pool, (const void*)places_host, (const void*)places_dev, (const void*)lut_bgr);
-  if (pitch_bytes < 3 * (int64_t)w) RADNET_FAIL(ctx, RADNET_ERR_ARG, "heat_paint: a pitch of %lld bytes for rows of %d pixels", (long long)pitch_bytes, w);
-  if (tau < 0 || tau > 255) RADNET_FAIL(ctx, RADNET_ERR_ARG, "heat_paint: tau = %d, outside 0..255", tau);
-  if (min_level < 0 || min_level > 255) RADNET_FAIL(ctx, RADNET_ERR_ARG, "heat_paint: min_level = %d, outside 0..255", min_level);
-  char why[200];
-  if (radnet_heat_check(places_host, count, pool_len, h, w, nullptr, why, (int32_t)sizeof(why)) != RADNET_OK) RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s", why);
-  const long long tiles_x = ((long long)w + kDrawTileW - 1) / kDrawTileW, tiles_y = ((long long)h + kDrawTileH - 1) / kDrawTileH;
-  if (tiles_x * tiles_y >= (1ll << 31)) RADNET_FAIL(ctx, RADNET_ERR_UNSUPPORTED, "heat_paint: an image of %d x %d", h, w);
-  hipLaunchKernelGGL(heat_paint_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(kDrawBatch), 0, ctx->stream, img, h, w, (long long)pitch_bytes, pool,
-                     places_dev, count, lut_bgr, tau, min_level, (int)tiles_x);
-  RADNET_CHECK_LAUNCH(ctx, "heat_paint_u8");
-  return RADNET_OK;
+  return draw_front(
+      ctx, "heat_paint", "placements", img, h, w, pitch_bytes, places_host, places_dev, count,
+      [&]() -> int {
+        if (!pool || !lut_bgr) RADNET_FAIL(ctx, RADNET_ERR_ARG, "heat_paint: a null pool or colour table (pool %p, colours %p)", (const void*)pool, (const void*)lut_bgr);
+        if (tau < 0 || tau > 255) RADNET_FAIL(ctx, RADNET_ERR_ARG, "heat_paint: tau = %d, outside 0..255", tau);
+        if (min_level < 0 || min_level > 255) RADNET_FAIL(ctx, RADNET_ERR_ARG, "heat_paint: min_level = %d, outside 0..255", min_level);
+        char why[200];
+        if (radnet_heat_check(places_host, count, pool_len, h, w, nullptr, why, (int32_t)sizeof(why)) != RADNET_OK) RADNET_FAIL(ctx, RADNET_ERR_ARG, "%s", why);
+        return RADNET_OK;
+      },
+      [&](dim3 grid, int tiles_x) {
+        hipLaunchKernelGGL(heat_paint_kernel, grid, dim3(kDrawBatch), 0, ctx->stream, img, h, w, (long long)pitch_bytes, pool, places_dev, count, lut_bgr, tau,
+                           min_level, tiles_x);
+      });
 }

@@ -637,26 +637,53 @@ class RADNet():
 RECT = np.dtype([(k, np.int32) for k in ("x1", "y1", "x2", "y2", "thickness", "b", "g", "r")])      # radnet_rect, 32 bytes
 
 
-def draw_rects_device(img, rects, inplace=False, ctx=None):
-    """radnet_draw_rects_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): `rects` is a sequence of
-    (x1, y1, x2, y2, thickness, b, g, r), painted in order (thickness < 0 fills).  Returns the device image, a clone unless inplace.
-    The table goes up on its own, 32 bytes per rectangle; an empty list launches nothing.  ctx and the stream rules are
-    png.decode_device's."""
+def _paint_device(img, inplace, ctx, paint, clone=True):
+    """What the *_device painters below share.  img: a uint8 [H][W][3] contiguous cuda tensor, or a NumPy array, which is uploaded
+    (and then painted in place).  On the feed stream of `ctx` (png.decode_device's rules), after the caller's stream: out = img if
+    inplace, else a clone of it (clone=False: an uninitialised image of its shape), then paint(ctx, img, out), which uploads what
+    its launch needs and calls it.  Returns out, handed over to the caller's stream."""
     import torch
     from . import augmentation_device as AD
     if isinstance(img, np.ndarray):
         img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
     check_device_image(img)
-    table = np.array([tuple(int(v) for v in r) for r in rects], RECT).reshape(-1)
     producer = torch.cuda.current_stream()
     with AD.feed_stream(ctx) as (ctx, side):
         if side is not None:
             side.wait_stream(producer)
-        out = img if inplace else img.clone()
-        if len(table):
-            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
-            ctx.call("radnet_draw_rects_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, table_dev, len(table))
+        out = img if inplace else (img.clone() if clone else torch.empty_like(img))
+        paint(ctx, img, out)
     return AD.hand_over(out, side)
+
+
+def _upload(array):
+    """A host table or pool as device bytes; None for an empty one."""
+    import torch
+    return torch.from_numpy(array.view(np.uint8).copy()).cuda() if len(array) else None
+
+
+def draw_rects_device(img, rects, inplace=False, ctx=None):
+    """radnet_draw_rects_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): `rects` is a sequence of
+    (x1, y1, x2, y2, thickness, b, g, r), painted in order (thickness < 0 fills).  Returns the device image, a clone unless inplace.
+    The table goes up on its own, 32 bytes per rectangle; an empty list launches nothing.  ctx and the stream rules are
+    png.decode_device's."""
+    table = np.array([tuple(int(v) for v in r) for r in rects], RECT).reshape(-1)
+
+    def paint(ctx, src, out):
+        if len(table):
+            ctx.call("radnet_draw_rects_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, _upload(table), len(table))
+    return _paint_device(img, inplace, ctx, paint)
+
+
+def _draw_prims_device(entry, img, tables, inplace, ctx):
+    """radnet_draw_list_u8 or radnet_draw_scene_u8 with scene_table's (table, chars)."""
+    table, chars = tables
+
+    def paint(ctx, src, out):
+        if len(table):
+            ctx.call(entry, out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, _upload(table), len(table),
+                     chars.ctypes.data if len(chars) else None, _upload(chars), len(chars))
+    return _paint_device(img, inplace, ctx, paint)
 
 
 PRIM = np.dtype([(k, np.int32) for k in ("kind", "x1", "y1", "x2", "y2", "a", "b", "bgr")])      # radnet_prim, 32 bytes
@@ -683,52 +710,27 @@ def draw_list_device(img, prims, inplace=False, ctx=None):
     the string through label_bytes --, painted in order in one launch, the later entry on top (include/radnet_hip.h states the
     pixel sets).  Returns the device image, a clone unless inplace.  The table (32 bytes per entry) and the character pool go up
     on their own; an empty list launches nothing.  ctx and the stream rules are draw_rects_device's."""
-    import torch
-    from . import augmentation_device as AD
-    if isinstance(img, np.ndarray):
-        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
-    check_device_image(img)
-    rows, pool = [], bytearray()
-    for p in prims:
-        if p[0] == "rect":
-            _, x1, y1, x2, y2, thickness, b, g, r = p
-            rows.append((PRIM_RECT, int(x1), int(y1), int(x2), int(y2), int(thickness), 0, _bgr(b, g, r)))
-        elif p[0] == "text":
-            _, x, y, string, scale, b, g, r = p
-            run = label_bytes(string)
-            rows.append((PRIM_TEXT, int(x), int(y), int(scale), 0, len(pool), len(run), _bgr(b, g, r)))
-            pool += run
-        else:
-            raise ValueError("draw_list_device: entry %d is %r, neither 'rect' nor 'text'" % (len(rows), p[0]))
-    table = np.array(rows, PRIM).reshape(-1)
-    chars = np.frombuffer(bytes(pool), np.uint8)
-    producer = torch.cuda.current_stream()
-    with AD.feed_stream(ctx) as (ctx, side):
-        if side is not None:
-            side.wait_stream(producer)
-        out = img if inplace else img.clone()
-        if len(table):
-            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
-            chars_dev = torch.from_numpy(chars.copy()).cuda() if len(chars) else None
-            ctx.call("radnet_draw_list_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, table_dev, len(table),
-                     chars.ctypes.data if len(chars) else None, chars_dev, len(chars))
-    return AD.hand_over(out, side)
+    return _draw_prims_device("radnet_draw_list_u8", img, scene_table(prims, list_only=True), inplace, ctx)
 
 
 PRIM_LINE, PRIM_DISC = 2, 3                                                                      # RADNET_PRIM_LINE, RADNET_PRIM_DISC
 
 
-def scene_table(prims):
+def scene_table(prims, list_only=False):
     """(table, chars): radnet_draw_scene_u8's table (PRIM rows) and character pool for a sequence of
     ("rect", x1, y1, x2, y2, thickness, b, g, r), ("text", x, y, string, scale, b, g, r), ("line", x1, y1, x2, y2, t, b, g, r) and
     ("disc", cx, cy, radius, t, b, g, r) -- t < 0 fills the disc --, each optionally followed by a dict with "dash": (on, off), lines
-    only, and "transparency": 0..255 (0 opaque).  Host only; include/radnet_hip.h states the pixel sets and the mixing rule."""
+    only, and "transparency": 0..255 (0 opaque).  list_only: radnet_draw_list_u8's table, the same rows for what draw_list_device
+    takes -- 'rect' and 'text', no options --, anything else refused in its name.  Host only; include/radnet_hip.h states the pixel
+    sets and the mixing rule."""
     rows, pool = [], bytearray()
     for p in prims:
         opts = {}
-        if len(p) and isinstance(p[-1], dict):
+        if not list_only and len(p) and isinstance(p[-1], dict):      # the list has no options: a dict there is one value too many
             p, opts = p[:-1], p[-1]
-        where = "draw_scene_device: entry %d" % len(rows)
+        where = "%s: entry %d" % ("draw_list_device" if list_only else "draw_scene_device", len(rows))
+        if list_only and p[0] not in ("rect", "text"):
+            raise ValueError("%s is %r, neither 'rect' nor 'text'" % (where, p[0]))
         if set(opts) - {"dash", "transparency"} or ("dash" in opts and p[0] != "line"):
             raise ValueError("%s (%r) has the options %r" % (where, p[0], sorted(opts)))
         tau = int(opts.get("transparency", 0))
@@ -770,40 +772,14 @@ def draw_scene_device(img, prims, inplace=False, ctx=None):
     them, draw_list_device's rectangles and text plus lines and discs, any of them translucent, painted in order in ONE launch, each
     entry mixing with what the earlier ones left.  Returns the device image, a clone unless inplace.  An empty list launches nothing.
     ctx and the stream rules are draw_rects_device's."""
-    import torch
-    from . import augmentation_device as AD
-    if isinstance(img, np.ndarray):
-        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
-    check_device_image(img)
-    table, chars = scene_table(prims)
-    producer = torch.cuda.current_stream()
-    with AD.feed_stream(ctx) as (ctx, side):
-        if side is not None:
-            side.wait_stream(producer)
-        out = img if inplace else img.clone()
-        if len(table):
-            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
-            chars_dev = torch.from_numpy(chars.copy()).cuda() if len(chars) else None
-            ctx.call("radnet_draw_scene_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], table.ctypes.data, table_dev, len(table),
-                     chars.ctypes.data if len(chars) else None, chars_dev, len(chars))
-    return AD.hand_over(out, side)
+    return _draw_prims_device("radnet_draw_scene_u8", img, scene_table(prims), inplace, ctx)
 
 
 def grey3_device(img, inplace=False, ctx=None):
     """radnet_grey3_u8 on a uint8 [H][W][3] contiguous cuda tensor (a NumPy array is uploaded): cv2.cvtColor(BGR2GRAY) and back to
     three equal channels in one launch.  Returns the device image, a new one unless inplace."""
-    import torch
-    from . import augmentation_device as AD
-    if isinstance(img, np.ndarray):
-        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
-    check_device_image(img)
-    producer = torch.cuda.current_stream()
-    with AD.feed_stream(ctx) as (ctx, side):
-        if side is not None:
-            side.wait_stream(producer)
-        out = img if inplace else torch.empty_like(img)
-        ctx.call("radnet_grey3_u8", img, out, img.shape[0], img.shape[1], 3 * img.shape[1], 3 * img.shape[1])
-    return AD.hand_over(out, side)
+    return _paint_device(img, inplace, ctx, lambda ctx, src, out: ctx.call(
+        "radnet_grey3_u8", src, out, src.shape[0], src.shape[1], 3 * src.shape[1], 3 * src.shape[1]), clone=False)
 
 
 HEAT_PLACE = np.dtype([(k, np.int32) for k in ("x0", "y0", "w", "h", "mw", "mh")] + [("offset", np.int64)])      # radnet_heat_place, 32 bytes
@@ -854,10 +830,6 @@ def heat_paint_device(img, pool, places, lut=None, transparency=0, min_level=0, 
     opaque).  Returns the device image, a clone unless inplace.  An empty list launches nothing.  ctx and the stream rules are
     draw_rects_device's."""
     import torch
-    from . import augmentation_device as AD
-    if isinstance(img, np.ndarray):
-        img, inplace = torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
-    check_device_image(img)
     table = heat_table(places)
     tau, min_level = int(transparency), int(min_level)
     if not 0 <= tau <= 255:
@@ -872,20 +844,15 @@ def heat_paint_device(img, pool, places, lut=None, transparency=0, min_level=0, 
         raise ValueError("heat_paint_device: the colour table must be 256 x 3 uint8, not %s %s" % (lut.shape, lut.dtype))
     if not (isinstance(pool, torch.Tensor) and pool.is_cuda):
         host = np.frombuffer(bytes(pool), np.uint8) if isinstance(pool, (bytes, bytearray)) else np.ascontiguousarray(pool, dtype=np.uint8).reshape(-1)
-        pool = torch.from_numpy(host.copy()).cuda() if len(host) else torch.zeros(1, dtype=torch.uint8, device=img.device)[:0]
+        pool = torch.from_numpy(host.copy()).cuda() if len(host) else torch.zeros(1, dtype=torch.uint8, device=img.device if isinstance(img, torch.Tensor) else "cuda")[:0]
     if pool.dtype != torch.uint8 or not pool.is_contiguous():
         raise TypeError("heat_paint_device: the pool must be a contiguous uint8 tensor, not %s" % (pool.dtype,))
-    producer = torch.cuda.current_stream()
-    with AD.feed_stream(ctx) as (ctx, side):
-        if side is not None:
-            side.wait_stream(producer)
-        out = img if inplace else img.clone()
+
+    def paint(ctx, src, out):
         if len(table):
-            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
-            lut_dev = torch.from_numpy(lut.reshape(-1).copy()).cuda()
-            ctx.call("radnet_heat_paint_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], pool, pool.numel(), table.ctypes.data, table_dev, len(table),
-                     lut_dev, tau, min_level)
-    return AD.hand_over(out, side)
+            ctx.call("radnet_heat_paint_u8", out, out.shape[0], out.shape[1], 3 * out.shape[1], pool, pool.numel(), table.ctypes.data, _upload(table), len(table),
+                     _upload(lut.reshape(-1)), tau, min_level)
+    return _paint_device(img, inplace, ctx, paint)
 
 
 def _bgr(b, g, r):

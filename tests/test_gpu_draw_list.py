@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-SENTINEL = 0xA5
-ERR_ARG = -1
+import draw_gpu_helpers as G  # noqa: E402  (needs torch)
+from draw_gpu_helpers import ERR_ARG, canvas  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -39,46 +39,6 @@ def font(R):
     return {code: L.glyph_rows(code) for code in range(D.FIRST, D.LAST + 1)}
 
 
-def list_call(ctx, R, buf, h, w, pitch, rows, pool=b"", count=None, n_chars=None, handle=True, host=True, dev=True, chars_host=True, chars_dev=True):
-    """radnet_draw_list_u8 on a copy of the host buffer `buf` (h rows of `pitch` bytes): (rc, message, the buffer afterwards)."""
-    table = np.array([tuple(r) for r in rows], R.PRIM).reshape(-1)
-    chars = np.frombuffer(bytes(pool), np.uint8).copy()
-    img_dev = torch.from_numpy(buf.copy()).cuda()
-    table_dev = torch.from_numpy(table.view(np.uint8).copy()).cuda() if len(table) else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    pool_dev = torch.from_numpy(chars).cuda() if len(chars) else torch.zeros(4, dtype=torch.uint8, device="cuda")
-    rc = ctx.lib.radnet_draw_list_u8(ctx.h if handle else None, img_dev.data_ptr(), h, w, pitch, table.ctypes.data if host and len(table) else None,
-                                     table_dev.data_ptr() if dev else None, len(table) if count is None else count,
-                                     chars.ctypes.data if chars_host and len(chars) else None, pool_dev.data_ptr() if chars_dev and len(chars) else None,
-                                     len(chars) if n_chars is None else n_chars)
-    msg = ctx.lib.radnet_last_error(ctx.h)
-    ctx.sync()
-    return rc, (msg.decode() if msg else ""), img_dev.cpu().numpy()
-
-
-def canvas(h, w, pad, seed=0):
-    """A noise image in a buffer of h rows of 3 * w + pad bytes, sentinels in the padding."""
-    buf = np.full((h, 3 * w + pad), SENTINEL, np.uint8)
-    buf[:, :3 * w] = np.random.RandomState(seed).randint(0, 256, (h, 3 * w))
-    return buf
-
-
-def expected(buf, h, w, prims, font):
-    want = buf.copy()
-    img = want[:, :3 * w].reshape(h, w, 3).copy()
-    D.paint_list(img, prims, font)
-    want[:, :3 * w] = img.reshape(h, 3 * w)
-    return want
-
-
-def check(ctx, R, font, buf, h, w, pad, prims, what):
-    rows, pool = D.pack(prims)
-    rc, msg, got = list_call(ctx, R, buf, h, w, 3 * w + pad, rows, pool)
-    assert rc == 0, (what, msg)
-    want = expected(buf, h, w, prims, font)
-    assert np.array_equal(got, want), (what, pad, np.argwhere(got != want)[:4].tolist())
-    return got
-
-
 # ---- text --------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("size", D.SIZES, ids=["%dx%d" % s for s in D.SIZES])
 def test_text_against_the_painter(ctx, R, font, size):
@@ -86,7 +46,7 @@ def test_text_against_the_painter(ctx, R, font, size):
     for pad in (0, 7):
         buf = canvas(h, w, pad, seed=h + pad)
         for name, prims in D.text_lists(h, w).items():
-            got = check(ctx, R, font, buf, h, w, pad, prims, name)
+            got = G.check(ctx, R, G.LIST, font, buf, h, w, pad, prims, name)
             if name in D.NOTHING:
                 assert np.array_equal(got, buf), name
             elif size == D.SIZES[-1]:
@@ -96,7 +56,7 @@ def test_text_against_the_painter(ctx, R, font, size):
 def test_every_code_once(ctx, R, font):
     h, w = 16, 600
     buf = canvas(h, w, 5, seed=3)
-    got = check(ctx, R, font, buf, h, w, 5, [("text", 7, 11, D.ALL_CODES, 1) + D.WHITE], "all 95 codes")
+    got = G.check(ctx, R, G.LIST, font, buf, h, w, 5, [("text", 7, 11, D.ALL_CODES, 1) + D.WHITE], "all 95 codes")
     img = got[:, :3 * w].reshape(h, w, 3)
     for k, code in enumerate(D.ALL_CODES):                                                     # glyph by glyph, straight from the table
         cell = (img[4:12, 7 + 6 * k:7 + 6 * k + 6] == 255).all(axis=2)
@@ -113,9 +73,9 @@ def test_a_pool_longer_than_one_batch(ctx, R, font):
     rows = [(D.PRIM_TEXT, x, y, s, 0, a, n, c[0] | c[1] << 8 | c[2] << 16) for a, n, x, y, s, c in runs]
     prims = [("text", x, y, pool[a:a + n], s) + c for a, n, x, y, s, c in runs]
     buf = canvas(h, w, 2, seed=8)
-    rc, msg, got = list_call(ctx, R, buf, h, w, 3 * w + 2, rows, pool)
+    rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, 3 * w + 2, rows, pool)
     assert rc == 0, msg
-    want = expected(buf, h, w, prims, font)
+    want = G.expected(D.paint_list, buf, h, w, prims, font)
     assert np.array_equal(got, want), np.argwhere(got != want)[:4].tolist()
     assert not np.array_equal(got, buf)
 
@@ -126,8 +86,8 @@ def test_the_later_entry_wins(ctx, R, font):
     lists = D.text_lists(h, w)
     buf = canvas(h, w, 0)
     for name in ("text over a filled rectangle", "a filled rectangle over text", "overlapping runs", "outline over text over fill"):
-        forward = check(ctx, R, font, buf, h, w, 0, lists[name], name)
-        backward = check(ctx, R, font, buf, h, w, 0, lists[name][::-1], name + ", reversed")
+        forward = G.check(ctx, R, G.LIST, font, buf, h, w, 0, lists[name], name)
+        backward = G.check(ctx, R, G.LIST, font, buf, h, w, 0, lists[name][::-1], name + ", reversed")
         assert not np.array_equal(forward, backward), name
 
 
@@ -139,7 +99,7 @@ def test_lists_around_the_batch_boundaries(ctx, R, font, count):
     prims = D.batch_list(count, h, w)
     assert len(prims) == count
     buf = canvas(h, w, 3, seed=count)
-    check(ctx, R, font, buf, h, w, 3, prims, "%d entries" % count)
+    G.check(ctx, R, G.LIST, font, buf, h, w, 3, prims, "%d entries" % count)
 
 
 # ---- rectangles ----------------------------------------------------------------------------------------------------------------------------
@@ -151,7 +111,7 @@ def test_rectangles_give_the_bytes_of_draw_rects(ctx, R, font):
         img_dev, table_dev = torch.from_numpy(buf.copy()).cuda(), torch.from_numpy(table.view(np.uint8).copy()).cuda()
         ctx.call("radnet_draw_rects_u8", img_dev, h, w, 3 * w + 7, table.ctypes.data, table_dev, len(table))
         ctx.sync()
-        got = check(ctx, R, font, buf, h, w, 7, [("rect",) + tuple(r) for r in rects], name)
+        got = G.check(ctx, R, G.LIST, font, buf, h, w, 7, [("rect",) + tuple(r) for r in rects], name)
         assert np.array_equal(got, img_dev.cpu().numpy()), name
 
 
@@ -162,11 +122,11 @@ def test_count_zero_and_refusals(ctx, R, font):
     pitch = 3 * w + 4
     good = [("rect", 2, 2, 9, 9, 8, 1, 2, 3), ("text", 3, 12, "ok: 1", 1, 255, 0, 255), ("rect", 1, 1, 5, 5, D.FILLED, 0, 0, 0), ("text", 1, 18, "gy", 1, 9, 9, 9)]
     rows, pool = D.pack(good)
-    rc, msg, got = list_call(ctx, R, buf, h, w, pitch, rows, pool)
-    assert rc == 0 and np.array_equal(got, expected(buf, h, w, good, font)) and not np.array_equal(got, buf)
-    rc, msg, got = list_call(ctx, R, buf, h, w, pitch, [])
+    rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, pitch, rows, pool)
+    assert rc == 0 and np.array_equal(got, G.expected(D.paint_list, buf, h, w, good, font)) and not np.array_equal(got, buf)
+    rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, pitch, [])
     assert rc == 0 and np.array_equal(got, buf)
-    rc, msg, got = list_call(ctx, R, buf, h, w, pitch, rows, pool, count=0, host=False, dev=False, chars_host=False, chars_dev=False)
+    rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, pitch, rows, pool, count=0, host=False, dev=False, chars_host=False, chars_dev=False)
     assert rc == 0 and np.array_equal(got, buf)
 
     names = list(R.PRIM.names)
@@ -193,20 +153,20 @@ def test_count_zero_and_refusals(ctx, R, font):
                                       ("a control code", rows, with_byte(2, 0x1F), 1), ("DEL", rows, with_byte(6, 0x7F), 3),
                                       ("a byte above ASCII", rows, with_byte(0, 0xE5), 1),
                                       ("colour bit 24", with_entry(0, bgr=1 << 24), pool, 0), ("a negative colour", with_entry(3, bgr=-1), pool, 3)):
-        rc, msg, got = list_call(ctx, R, buf, h, w, pitch, table, chars)
+        rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, pitch, table, chars)
         assert rc == ERR_ARG and ("entry %d " % entry) in msg, (what, msg)
         assert np.array_equal(got, buf), what                                                 # not even the entries in front of the bad one
     # a byte outside the font that no run refers to is nobody's business
     rows2, pool2 = D.pack(good, pool=b"\x00\xff")
-    rc, msg, got = list_call(ctx, R, buf, h, w, pitch, rows2, pool2)
-    assert rc == 0 and np.array_equal(got, expected(buf, h, w, good, font)), msg
+    rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, pitch, rows2, pool2)
+    assert rc == 0 and np.array_equal(got, G.expected(D.paint_list, buf, h, w, good, font)), msg
     for what, kw in (("short pitch", dict(pitch=3 * w - 1)), ("negative count", dict(count=-1)), ("null host table", dict(host=False)),
                      ("null device table", dict(dev=False)), ("no context", dict(handle=False)), ("null host pool", dict(chars_host=False)),
                      ("null device pool", dict(chars_dev=False)), ("a negative pool length", dict(n_chars=-1))):
         p = kw.pop("pitch", pitch)
-        rc, msg, got = list_call(ctx, R, buf, h, w, p, rows, pool, **kw)
+        rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, p, rows, pool, **kw)
         assert rc == ERR_ARG and np.array_equal(got, buf), what
-    rc, msg, got = list_call(ctx, R, buf, 0, w, pitch, rows, pool)
+    rc, msg, got = G.prims_call(ctx, R, G.LIST.entry, buf, 0, w, pitch, rows, pool)
     assert rc == ERR_ARG and np.array_equal(got, buf)
 
 

@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-SENTINEL = 0xA5
-ERR_ARG = -1
+import draw_gpu_helpers as G  # noqa: E402  (needs torch)
+from draw_gpu_helpers import ERR_ARG, canvas  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -39,48 +39,6 @@ def font(R):
     return {code: L.glyph_rows(code) for code in range(D.FIRST, D.LAST + 1)}
 
 
-def scene_call(ctx, R, buf, h, w, pitch, rows, pool=b"", count=None, n_chars=None, handle=True, host=True, dev=True, chars_host=True, chars_dev=True,
-               entry="radnet_draw_scene_u8"):
-    """radnet_draw_scene_u8 (or radnet_draw_list_u8) on a copy of the host buffer `buf` (h rows of `pitch` bytes): (rc, message, the
-    buffer afterwards)."""
-    table = np.array([tuple(r) for r in rows], R.PRIM).reshape(-1)
-    chars = np.frombuffer(bytes(pool), np.uint8).copy()
-    img_dev = torch.from_numpy(buf.copy()).cuda()
-    table_dev = torch.from_numpy(table.view(np.uint8).copy()).cuda() if len(table) else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    pool_dev = torch.from_numpy(chars).cuda() if len(chars) else torch.zeros(4, dtype=torch.uint8, device="cuda")
-    rc = getattr(ctx.lib, entry)(ctx.h if handle else None, img_dev.data_ptr(), h, w, pitch, table.ctypes.data if host and len(table) else None,
-                                 table_dev.data_ptr() if dev else None, len(table) if count is None else count,
-                                 chars.ctypes.data if chars_host and len(chars) else None, pool_dev.data_ptr() if chars_dev and len(chars) else None,
-                                 len(chars) if n_chars is None else n_chars)
-    msg = ctx.lib.radnet_last_error(ctx.h)
-    ctx.sync()
-    return rc, (msg.decode() if msg else ""), img_dev.cpu().numpy()
-
-
-def canvas(h, w, pad, seed=0):
-    """A noise image in a buffer of h rows of 3 * w + pad bytes, sentinels in the padding."""
-    buf = np.full((h, 3 * w + pad), SENTINEL, np.uint8)
-    buf[:, :3 * w] = np.random.RandomState(seed).randint(0, 256, (h, 3 * w))
-    return buf
-
-
-def expected(buf, h, w, prims, font):
-    want = buf.copy()
-    img = want[:, :3 * w].reshape(h, w, 3).copy()
-    S.paint_scene(img, prims, font)
-    want[:, :3 * w] = img.reshape(h, 3 * w)
-    return want
-
-
-def check(ctx, R, font, buf, h, w, pad, prims, what):
-    rows, pool = S.pack(prims)
-    rc, msg, got = scene_call(ctx, R, buf, h, w, 3 * w + pad, rows, pool)
-    assert rc == 0, (what, msg)
-    want = expected(buf, h, w, prims, font)
-    assert np.array_equal(got, want), (what, (h, w), pad, np.argwhere(got != want)[:4].tolist())
-    return got
-
-
 # ---- lines, discs, transparency, the lists that paint nothing ------------------------------------------------------------------------------
 @pytest.mark.parametrize("size", S.SIZES, ids=["%dx%d" % s for s in S.SIZES])
 def test_the_case_tables_against_the_painter(ctx, R, font, size):
@@ -89,7 +47,7 @@ def test_the_case_tables_against_the_painter(ctx, R, font, size):
     for pad in (0, 7):
         buf = canvas(h, w, pad, seed=h + pad)
         for name, prims in S.all_lists(h, w).items():
-            got = check(ctx, R, font, buf, h, w, pad, prims, name)
+            got = G.check(ctx, R, G.SCENE, font, buf, h, w, pad, prims, name)
             if name in nothing:
                 assert np.array_equal(got, buf), name
             elif size == S.SIZES[-1] and name != "tau 255":
@@ -101,8 +59,8 @@ def test_the_order_of_translucent_entries_shows(ctx, R, font):
     buf = canvas(h, w, 0)
     lists = S.translucent_lists(h, w)
     for name in ("three kinds overlapping", "opaque under translucent", "translucent under opaque", "tau 102"):
-        forward = check(ctx, R, font, buf, h, w, 0, lists[name], name)
-        backward = check(ctx, R, font, buf, h, w, 0, lists[name][::-1], name + ", reversed")
+        forward = G.check(ctx, R, G.SCENE, font, buf, h, w, 0, lists[name], name)
+        backward = G.check(ctx, R, G.SCENE, font, buf, h, w, 0, lists[name][::-1], name + ", reversed")
         assert not np.array_equal(forward, backward), name
 
 
@@ -114,7 +72,7 @@ def test_lists_around_the_batch_boundaries(ctx, R, font, count):
     prims = S.batch_list(count, h, w)
     assert len(prims) == count and {p[0] for p in prims} == {"rect", "text", "line", "disc"}
     buf = canvas(h, w, 3, seed=count)
-    check(ctx, R, font, buf, h, w, 3, prims, "%d entries" % count)
+    G.check(ctx, R, G.SCENE, font, buf, h, w, 3, prims, "%d entries" % count)
 
 
 # ---- opaque rectangles and text: the bytes of radnet_draw_list_u8 -----------------------------------------------------------------------------
@@ -126,12 +84,34 @@ def test_opaque_lists_give_the_bytes_of_draw_list(ctx, R, font):
     lists["257 entries"] = D.batch_list(257, h, w)
     for name, prims in lists.items():
         rows, pool = D.pack(prims)
-        rc, msg, want = scene_call(ctx, R, buf, h, w, 3 * w + 5, rows, pool, entry="radnet_draw_list_u8")
+        rc, msg, want = G.prims_call(ctx, R, G.LIST.entry, buf, h, w, 3 * w + 5, rows, pool)
         assert rc == 0, (name, msg)
-        rc, msg, got = scene_call(ctx, R, buf, h, w, 3 * w + 5, rows, pool)
+        rc, msg, got = G.prims_call(ctx, R, G.SCENE.entry, buf, h, w, 3 * w + 5, rows, pool)
         assert rc == 0, (name, msg)
         assert np.array_equal(got, want), (name, np.argwhere(got != want)[:4].tolist())
-        assert np.array_equal(got, expected(buf, h, w, prims, font)), name
+        assert np.array_equal(got, G.expected(S.paint_scene, buf, h, w, prims, font)), name
+
+
+def test_the_three_fronts_agree_across_a_batch_boundary(ctx, R, font):
+    """257 rectangles, one more than a batch, through radnet_draw_rects_u8, radnet_draw_list_u8 and radnet_draw_scene_u8: the same
+    bytes, the painter's; then the 257-entry list with its text through the list and the scene.  The pairwise tests above use lists
+    shorter than a batch or compare two fronts only; this pins the second staging of LDS in all three instantiations of the body."""
+    h, w, pad = 20, 45, 3
+    buf = canvas(h, w, pad, seed=257)
+    full = D.batch_list(257, h, w)
+    rects = [p for p in full if p[0] == "rect"]
+    if len(rects) < 257:                                                                       # it has: half of that list is text
+        rects = [p for p in D.batch_list(4 * 257, h, w) if p[0] == "rect"][:257]
+    rects[255], rects[256] = ("rect", 4, 2, 36, 14, D.FILLED) + D.RED, ("rect", 20, 0, 24, 15, 1) + D.BLACK      # the boundary shows
+    assert len(rects) == 257 and len(full) == 257 and any(p[0] == "text" for p in full)
+    want = G.expected(D.paint_list, buf, h, w, rects, font)
+    rc, msg, got = G.rects_call(ctx, R, buf, h, w, 3 * w + pad, [p[1:] for p in rects])
+    assert rc == 0 and np.array_equal(got, want), (msg, np.argwhere(got != want)[:4].tolist())
+    assert tuple(got[0, 3 * 20:3 * 20 + 3]) == D.BLACK and tuple(got[3, 3 * 5:3 * 5 + 3]) == D.RED      # entry 256 on entry 255
+    for prims in (rects, full):
+        want = G.expected(D.paint_list, buf, h, w, prims, font)
+        for front in (G.LIST, G.SCENE):
+            assert np.array_equal(G.check(ctx, R, front, font, buf, h, w, pad, prims, front.entry), want), front.entry
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------------
@@ -140,32 +120,32 @@ def test_count_zero_and_refusals(ctx, R, font):
     buf = canvas(h, w, 4)
     pitch = 3 * w + 4
     rows, pool, cases = S.refusals()
-    rc, msg, got = scene_call(ctx, R, buf, h, w, pitch, rows, pool)
-    assert rc == 0 and np.array_equal(got, expected(buf, h, w, S.GOOD, font)) and not np.array_equal(got, buf), msg
-    rc, msg, got = scene_call(ctx, R, buf, h, w, pitch, [])
+    rc, msg, got = G.prims_call(ctx, R, G.SCENE.entry, buf, h, w, pitch, rows, pool)
+    assert rc == 0 and np.array_equal(got, G.expected(S.paint_scene, buf, h, w, S.GOOD, font)) and not np.array_equal(got, buf), msg
+    rc, msg, got = G.prims_call(ctx, R, G.SCENE.entry, buf, h, w, pitch, [])
     assert rc == 0 and np.array_equal(got, buf)
-    rc, msg, got = scene_call(ctx, R, buf, h, w, pitch, rows, pool, count=0, host=False, dev=False, chars_host=False, chars_dev=False)
+    rc, msg, got = G.prims_call(ctx, R, G.SCENE.entry, buf, h, w, pitch, rows, pool, count=0, host=False, dev=False, chars_host=False, chars_dev=False)
     assert rc == 0 and np.array_equal(got, buf)
     for what, table, chars, entry in cases:
-        rc, msg, got = scene_call(ctx, R, buf, h, w, pitch, table, chars)
+        rc, msg, got = G.prims_call(ctx, R, G.SCENE.entry, buf, h, w, pitch, table, chars)
         assert rc == ERR_ARG and ("entry %d " % entry) in msg, (what, msg)
         assert np.array_equal(got, buf), what                                                 # not even the entries in front of the bad one
     for what, prims in S.accepted():
-        check(ctx, R, font, buf, h, w, 4, prims, what)
+        G.check(ctx, R, G.SCENE, font, buf, h, w, 4, prims, what)
     # what radnet_draw_list_u8 refuses and this entry means: bits 24..31 of the colour
     t = [list(r) for r in rows[:2]]
     t[0][7] |= 1 << 24
-    assert scene_call(ctx, R, buf, h, w, pitch, t, pool, entry="radnet_draw_list_u8")[0] == ERR_ARG and scene_call(ctx, R, buf, h, w, pitch, t, pool)[0] == 0
+    assert G.prims_call(ctx, R, G.LIST.entry, buf, h, w, pitch, t, pool)[0] == ERR_ARG and G.prims_call(ctx, R, G.SCENE.entry, buf, h, w, pitch, t, pool)[0] == 0
     # and kind 2 stays unknown to the list
-    assert scene_call(ctx, R, buf, h, w, pitch, rows[:3], pool, entry="radnet_draw_list_u8")[0] == ERR_ARG
+    assert G.prims_call(ctx, R, G.LIST.entry, buf, h, w, pitch, rows[:3], pool)[0] == ERR_ARG
     for what, kw in (("short pitch", dict(pitch=3 * w - 1)), ("negative count", dict(count=-1)), ("null host table", dict(host=False)),
                      ("null device table", dict(dev=False)), ("no context", dict(handle=False)), ("null host pool", dict(chars_host=False)),
                      ("null device pool", dict(chars_dev=False)), ("a negative pool length", dict(n_chars=-1))):
         p = kw.pop("pitch", pitch)
-        rc, msg, got = scene_call(ctx, R, buf, h, w, p, rows, pool, **kw)
+        rc, msg, got = G.prims_call(ctx, R, G.SCENE.entry, buf, h, w, p, rows, pool, **kw)
         assert rc == ERR_ARG and np.array_equal(got, buf), what
     for hh, ww in ((0, w), (h, 0), (-1, w)):
-        rc, msg, got = scene_call(ctx, R, buf, hh, ww, pitch, rows, pool)
+        rc, msg, got = G.prims_call(ctx, R, G.SCENE.entry, buf, hh, ww, pitch, rows, pool)
         assert rc == ERR_ARG and np.array_equal(got, buf)
 
 

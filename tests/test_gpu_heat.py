@@ -13,7 +13,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ERR_ARG = -1
+import draw_gpu_helpers as G  # noqa: E402  (needs torch)
+from draw_gpu_helpers import ERR_ARG  # noqa: E402
+
 SENTINEL = H.SENTINEL
 
 
@@ -80,18 +82,11 @@ def test_levels_refusals(ctx):
 def paint_call(ctx, R, buf, h, w, pitch, pool, places, lut, tau, min_level, count=None, pool_len=None, handle=True, img=True, pool_ptr=True, host=True, dev=True,
                lut_ptr=True):
     """radnet_heat_paint_u8 on a copy of the host buffer `buf` (h rows of `pitch` bytes): (rc, message, the buffer afterwards)."""
-    table = R.heat_table(places)
-    img_dev = torch.from_numpy(buf.copy()).cuda()
     pool_dev = torch.from_numpy(np.ascontiguousarray(pool, np.uint8)).cuda()
-    table_dev = torch.from_numpy(table.view(np.uint8).copy()).cuda() if len(table) else torch.zeros(32, dtype=torch.uint8, device="cuda")
     lut_dev = torch.from_numpy(np.ascontiguousarray(lut, np.uint8).reshape(-1)).cuda()
-    rc = ctx.lib.radnet_heat_paint_u8(ctx.h if handle else None, img_dev.data_ptr() if img else None, h, w, pitch, pool_dev.data_ptr() if pool_ptr else None,
-                                      len(pool) if pool_len is None else pool_len, table.ctypes.data if host and len(table) else None,
-                                      table_dev.data_ptr() if dev else None, len(table) if count is None else count, lut_dev.data_ptr() if lut_ptr else None,
-                                      tau, min_level)
-    msg = ctx.lib.radnet_last_error(ctx.h)
-    ctx.sync()
-    return rc, (msg.decode() if msg else ""), img_dev.cpu().numpy()
+    return G.raw_call(ctx, "radnet_heat_paint_u8", buf, h, w, pitch, R.heat_table(places),
+                      before=(pool_dev.data_ptr() if pool_ptr else None, len(pool) if pool_len is None else pool_len),
+                      after=(lut_dev.data_ptr() if lut_ptr else None, tau, min_level), count=count, handle=handle, img=img, host=host, dev=dev)
 
 
 @pytest.fixture(scope="module")

@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-SENTINEL = 0xA5
-ERR_ARG = -1
+import draw_gpu_helpers as G  # noqa: E402  (needs torch)
+from draw_gpu_helpers import ERR_ARG, SENTINEL, canvas  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -171,42 +171,15 @@ def test_imwrite_writes_encode_device(png, pictures, tmp_path):
 
 
 # ---- the draw kernel -------------------------------------------------------------------------------------------------------------------
-def draw_call(ctx, R, buf, h, w, pitch, rects, count=None, handle=True, host=True, dev=True):
-    """radnet_draw_rects_u8 on a copy of the host buffer `buf` (h rows of `pitch` bytes): (rc, message, the buffer afterwards)."""
-    table = np.array([tuple(r) for r in rects], R.RECT).reshape(-1)
-    img_dev = torch.from_numpy(buf.copy()).cuda()
-    table_dev = torch.from_numpy(table.view(np.uint8).copy()).cuda() if len(table) else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    rc = ctx.lib.radnet_draw_rects_u8(ctx.h if handle else None, img_dev.data_ptr(), h, w, pitch, table.ctypes.data if host and len(table) else None,
-                                      table_dev.data_ptr() if dev else None, len(table) if count is None else count)
-    msg = ctx.lib.radnet_last_error(ctx.h)
-    ctx.sync()
-    return rc, (msg.decode() if msg else ""), img_dev.cpu().numpy()
-
-
-def canvas(h, w, pad, seed=0):
-    """A noise image in a buffer of h rows of 3 * w + pad bytes, sentinels in the padding: (buffer, the [h][w][3] view of a copy)."""
-    buf = np.full((h, 3 * w + pad), SENTINEL, np.uint8)
-    buf[:, :3 * w] = np.random.RandomState(seed).randint(0, 256, (h, 3 * w))
-    return buf
-
-
-def expected(buf, h, w, rects):
-    want = buf.copy()
-    img = want[:, :3 * w].reshape(h, w, 3).copy()
-    W.paint(img, rects)
-    want[:, :3 * w] = img.reshape(h, 3 * w)
-    return want
-
-
 @pytest.mark.parametrize("size", [(64, 64), (70, 130)], ids=["64x64", "70x130"])
 def test_draw_rects_against_the_painter(ctx, R, size):
     h, w = size
     for pad in (0, 7):
         buf = canvas(h, w, pad, seed=h + pad)
         for name, rects in W.rect_lists(h, w).items():
-            rc, msg, got = draw_call(ctx, R, buf, h, w, 3 * w + pad, rects)
+            rc, msg, got = G.rects_call(ctx, R, buf, h, w, 3 * w + pad, rects)
             assert rc == 0, (name, msg)
-            want = expected(buf, h, w, rects)
+            want = G.expected(W.paint, buf, h, w, rects)
             assert np.array_equal(got, want), (name, pad, np.argwhere(got != want)[:4].tolist())
             if name in ("wholly outside", "outline wider than the image"):
                 assert np.array_equal(got, buf), name
@@ -217,8 +190,8 @@ def test_draw_rects_against_the_painter(ctx, R, size):
 def test_draw_rects_overlap_order_matters(ctx, R):
     lists = W.rect_lists(64, 64)
     buf = canvas(64, 64, 0)
-    a = draw_call(ctx, R, buf, 64, 64, 192, lists["overlap a then b"])[2]
-    b = draw_call(ctx, R, buf, 64, 64, 192, lists["overlap b then a"])[2]
+    a = G.rects_call(ctx, R, buf, 64, 64, 192, lists["overlap a then b"])[2]
+    b = G.rects_call(ctx, R, buf, 64, 64, 192, lists["overlap b then a"])[2]
     assert not np.array_equal(a, b)
 
 
@@ -232,23 +205,23 @@ def test_draw_rects_more_than_one_batch(ctx, R):
     xs[batch], ys[batch] = xs[3], ys[3]
     rects = [(int(x), int(y), int(x), int(y), 1 if k % 2 else W.FILLED, k % 256, (7 * k) % 256, 255 - k % 256) for k, (x, y) in enumerate(zip(xs, ys))]
     buf = canvas(64, 64, 3, seed=5)
-    rc, msg, got = draw_call(ctx, R, buf, 64, 64, 195, rects)
+    rc, msg, got = G.rects_call(ctx, R, buf, 64, 64, 195, rects)
     assert rc == 0, msg
-    want = expected(buf, 64, 64, rects)
+    want = G.expected(W.paint, buf, 64, 64, rects)
     assert np.array_equal(got, want), np.argwhere(got != want)[:4].tolist()
     assert tuple(got[ys[3], 3 * xs[3]:3 * xs[3] + 3]) == rects[batch][5:]
     big = [(k % 60, (k * 7) % 60, k % 60 + 9, (k * 7) % 60 + 5, (1, 8, W.FILLED)[k % 3], k % 256, 3, 200) for k in range(2 * batch + 5)]
-    rc, msg, got = draw_call(ctx, R, buf, 64, 64, 195, big)                                    # three batches of overlapping rectangles
-    assert rc == 0 and np.array_equal(got, expected(buf, 64, 64, big)), msg
+    rc, msg, got = G.rects_call(ctx, R, buf, 64, 64, 195, big)                                    # three batches of overlapping rectangles
+    assert rc == 0 and np.array_equal(got, G.expected(W.paint, buf, 64, 64, big)), msg
 
 
 def test_draw_rects_count_zero_and_refusals(ctx, R):
     h, w = 20, 30
     buf = canvas(h, w, 4)
     good = [(2, 2, 9, 9, 8, 1, 2, 3), (4, 4, 12, 12, W.FILLED, 255, 0, 255), (1, 1, 5, 5, 1, 0, 0, 0)]
-    rc, msg, got = draw_call(ctx, R, buf, h, w, 3 * w + 4, [])
+    rc, msg, got = G.rects_call(ctx, R, buf, h, w, 3 * w + 4, [])
     assert rc == 0 and np.array_equal(got, buf)
-    rc, msg, got = draw_call(ctx, R, buf, h, w, 3 * w + 4, good, count=0, host=False, dev=False)
+    rc, msg, got = G.rects_call(ctx, R, buf, h, w, 3 * w + 4, good, count=0, host=False, dev=False)
     assert rc == 0 and np.array_equal(got, buf)
 
     def with_entry(i, **fields):
@@ -259,15 +232,15 @@ def test_draw_rects_count_zero_and_refusals(ctx, R):
 
     for what, rects, mention in (("thickness 0", with_entry(1, thickness=0), "rectangle 1"), ("blue 256", with_entry(2, b=256), "rectangle 2"),
                                  ("green -1", with_entry(0, g=-1), "rectangle 0"), ("red 1000", with_entry(2, r=1000), "rectangle 2")):
-        rc, msg, got = draw_call(ctx, R, buf, h, w, 3 * w + 4, rects)
+        rc, msg, got = G.rects_call(ctx, R, buf, h, w, 3 * w + 4, rects)
         assert rc == ERR_ARG and mention in msg, (what, msg)
         assert np.array_equal(got, buf), what                                                 # not even the entries in front of the bad one
     for what, kw in (("short pitch", dict(pitch=3 * w - 1)), ("negative count", dict(count=-1)), ("null host table", dict(host=False)),
                      ("null device table", dict(dev=False)), ("no context", dict(handle=False))):
         pitch = kw.pop("pitch", 3 * w + 4)
-        rc, msg, got = draw_call(ctx, R, buf, h, w, pitch, good, **kw)
+        rc, msg, got = G.rects_call(ctx, R, buf, h, w, pitch, good, **kw)
         assert rc == ERR_ARG and np.array_equal(got, buf), what
-    rc, msg, got = draw_call(ctx, R, buf, 0, w, 3 * w + 4, good)
+    rc, msg, got = G.rects_call(ctx, R, buf, 0, w, 3 * w + 4, good)
     assert rc == ERR_ARG and np.array_equal(got, buf)
 
 
