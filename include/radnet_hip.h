@@ -985,6 +985,128 @@ int radnet_rois_from_proposals(radnet_ctx* ctx, const int64_t* R, const int32_t*
  * radnet_predict_tile on the same plan bit for bit (a GEMM row does not depend on the other rows of its launch). */
 int radnet_predict_tile_detect(radnet_ctx* ctx, const radnet_tile_desc* t, const radnet_detect_tail_desc* d);
 
+/* ---- the merge of a scan's tile detections on the device (csrc/scan_tail.hip) ---------------------------------------------
+ * radnet_final_nms: RADNet.final_nms (RADNet.py:156-240) on a batch of groups, bit for bit what the host code returns.  The
+ * groups stand one after the other: group g is the rows offsets[g] .. offsets[g + 1] of boxes / probs (offsets on the DEVICE,
+ * so that a launch can follow the kernel that made them; every offset is clamped to 0 .. capacity before it is used).
+ * Per group, on the STABLE ascending order of the fp32 probs walked from the end (among equal probs the higher row becomes
+ * `top` first; -0 and +0 are equal): the members of top's cluster are the live boxes with
+ *   overlap = double(inter) / (double(area_top + area - inter) + 1e-6) > obj_avg_threshold     (fp64; areas, inter in int64)
+ * in order position, top last.  The members' maximum is top's prob.  Below obj_confidence_threshold (an fp32 comparison, as
+ * NumPy 2 makes it against a Python float) the chosen boxes are the last n_obj_avg members; otherwise the members strictly
+ * above it.  A cluster becomes (round_half_even(double(sum of the int64 coordinates) / count), fp32 sum / float(count)),
+ * the fp32 sum being the one np.mean takes over a contiguous vector: below 8 elements in sequence; up to 128 eight interleaved
+ * accumulators over blocks of 8, combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the remainder in sequence; above 128 the two
+ * halves split at n/2 rounded down to a multiple of 8, recursively.
+ * Outputs of group g: its clusters in the order they were found at rows offsets[g] .. of out_boxes / out_probs (rows past the
+ * cluster count are not written), out_count[g], out_status[g]:
+ *   0                         success
+ *   RADNET_FINAL_NMS_MALFORMED   a box with x1 >= x2 or y1 >= y2 (the host asserts)
+ *   RADNET_FINAL_NMS_EMPTY       a cluster whose maximum equals the threshold, so that nothing is chosen (the host takes
+ *                                the mean of an empty slice)
+ *   RADNET_FINAL_NMS_RANGE       a coordinate beyond +-RADNET_SCAN_MAX_COORD, or a NaN prob
+ * With a negative status the other outputs of that group are unspecified and the caller takes the host path.
+ * One launch, a workgroup of 1024 threads per group: a bitonic sort of the group's keys, then per cluster one parallel pass
+ * over the positions below top, then a second sort that lays every cluster's members side by side and a thread per cluster
+ * for the means.  Bounded by `capacity` alone: all per-box state lives in ws (radnet_final_nms_ws_bytes bytes, no
+ * initialisation needed), LDS holds a sort of up to 2048 keys and nothing that grows with the group.  Integer atomics in LDS
+ * only; no floating-point atomics.  RADNET_ERR_ARG for a null pointer, n_groups < 0, capacity < 0 or n_obj_avg < 1;
+ * n_groups == 0 launches nothing. */
+#define RADNET_FINAL_NMS_MALFORMED -1
+#define RADNET_FINAL_NMS_EMPTY -2
+#define RADNET_FINAL_NMS_RANGE -3
+/* 1 << 29: widths, areas and the coordinate sums of a cluster then stay far inside int64 */
+#define RADNET_SCAN_MAX_COORD 536870912
+typedef struct radnet_final_nms_desc {
+  const int64_t* boxes;    /* device [capacity][4] (x1, y1, x2, y2)                            */
+  const float* probs;      /* device [capacity]                                               */
+  const int32_t* offsets;  /* device [n_groups + 1]                                           */
+  int32_t n_groups, capacity;
+  double obj_avg_threshold;
+  float obj_confidence_threshold;
+  int32_t n_obj_avg;
+  int64_t* out_boxes;      /* device [capacity][4]                                            */
+  float* out_probs;        /* device [capacity]                                               */
+  int32_t* out_count;      /* device [n_groups]                                               */
+  int32_t* out_status;     /* device [n_groups]                                               */
+  void* ws;                /* device, radnet_final_nms_ws_bytes(capacity, n_groups) bytes     */
+} radnet_final_nms_desc;
+uint64_t radnet_final_nms_ws_bytes(int32_t capacity, int32_t n_groups);
+int radnet_final_nms(radnet_ctx* ctx, const radnet_final_nms_desc* d);
+
+/* radnet_scan_merge: the tail of RADNet.predict behind the tile passes (RADNet.py:577-718: the offsets, final_nms per image
+ * and class, NMS across the images per class), with no host read-back inside the call.
+ * pool: device int32 words; tile t's slot starts at word tiles[t].slot and holds what radnet_detect_tail wrote there for a
+ * head of at most slot_rows rows (slot_words = radnet_detect_tail_out_bytes(slot_rows) / 4).  tiles_host / tiles_dev hold the
+ * SAME table on the host and on the device (the caller uploads it; this entry copies nothing); the host copy goes through
+ * radnet_scan_merge_check first.  Tiles stand in predict's order, image indices do not decrease.
+ *   gather     per image and class the records of that class over the image's tiles, in tile order and within a tile in
+ *              record order, (ox, oy) added in int64;
+ *   cluster    radnet_final_nms on every (image, class) group;
+ *   final NMS  per class the clusters of its images in image order, then cluster order: greedy NMS in fp64 with radnet_nms's
+ *              suppression test and tie rule at nms_thresh, at most max_boxes picks;
+ *   write      out: radnet_scan_merge_out_bytes(nc, max_boxes) bytes of int32 words: [0] count, [1] status, [2..7] reserved
+ *              (not written), then `count` records (class, x1, y1, x2, y2, prob as fp32 bits): the classes in the order of
+ *              their first appearance over the tiles (the insertion order of the reference's dicts), the picks of a class in
+ *              pick order.  Words past the last record are not written.
+ * Status: 0, or the smallest of the first four below, or -- when none of them is met -- the fifth:
+ *   RADNET_SCAN_MERGE_BAD_SLOT    a slot whose count is -1 (its tile met a malformed box), exceeds slot_rows, or that holds a
+ *                                 class outside 0 .. nc - 1
+ *   RADNET_SCAN_MERGE_MALFORMED   RADNET_FINAL_NMS_MALFORMED of a group
+ *   RADNET_SCAN_MERGE_EMPTY       RADNET_FINAL_NMS_EMPTY of a group
+ *   RADNET_SCAN_MERGE_RANGE       RADNET_FINAL_NMS_RANGE of a group (a coordinate beyond +-RADNET_SCAN_MAX_COORD, hence
+ *                                 every coordinate beyond int32)
+ *   RADNET_SCAN_MERGE_NMS_BOX     a cluster mean with x1 >= x2 or y1 >= y2 at the final NMS (radnet_nms's count -1)
+ * and then count = 0 and no record is written: the caller takes the host path on a download of the pool.
+ * Six launches on the context's stream (count, plan, fill, radnet_final_nms, a workgroup per class for the final NMS, write);
+ * none waits on another but through stream order.  Bounded by n_tiles * slot_rows boxes and n_images * nc groups; all state in
+ * ws (radnet_scan_merge_ws_bytes bytes, no initialisation needed).  RADNET_ERR_ARG for a null pointer, a table the check refuses,
+ * nc outside 1 .. RADNET_SCAN_MAX_CLASSES, max_boxes < 1 or n_obj_avg < 1.  n_tiles == 0 writes count 0, status 0. */
+#define RADNET_SCAN_MERGE_BAD_SLOT -1
+#define RADNET_SCAN_MERGE_MALFORMED -2
+#define RADNET_SCAN_MERGE_EMPTY -3
+#define RADNET_SCAN_MERGE_RANGE -4
+#define RADNET_SCAN_MERGE_NMS_BOX -5
+#define RADNET_SCAN_MAX_CLASSES 32
+#define RADNET_SCAN_MAX_TILES 65536
+#define RADNET_SCAN_MAX_IMAGES 4096
+/* n_tiles * slot_rows at most (1 << 26) */
+#define RADNET_SCAN_MAX_BOXES 67108864
+typedef struct radnet_scan_tile {
+  int32_t slot;            /* first word of the tile's slot in the pool                       */
+  int32_t ox, oy;          /* the tile's offset in its image                                  */
+  int32_t image;           /* index of its image in the call                                  */
+} radnet_scan_tile;        /* 16 bytes */
+typedef struct radnet_scan_merge_desc {
+  const int32_t* pool;     /* device                                                          */
+  int64_t pool_words;
+  int32_t slot_rows;
+  const radnet_scan_tile* tiles_host;
+  const radnet_scan_tile* tiles_dev;
+  int32_t n_tiles, nc;
+  double obj_avg_threshold;
+  float obj_confidence_threshold;
+  int32_t n_obj_avg;
+  double nms_thresh;
+  int32_t max_boxes;
+  void* out;               /* device, radnet_scan_merge_out_bytes(nc, max_boxes) bytes        */
+  void* ws;                /* device, radnet_scan_merge_ws_bytes(n_tiles, slot_rows, n_images, nc, max_boxes) bytes */
+} radnet_scan_merge_desc;
+uint64_t radnet_scan_merge_out_bytes(int32_t nc, int32_t max_boxes);
+uint64_t radnet_scan_merge_ws_bytes(int32_t n_tiles, int32_t slot_rows, int32_t n_images, int32_t nc, int32_t max_boxes);
+int radnet_scan_merge(radnet_ctx* ctx, const radnet_scan_merge_desc* d);
+/* Host only (csrc/scan_merge_check.cpp; no context, no device, like radnet_heat_check): the checks of a tile table for a pool
+ * of pool_words int32 words whose slots hold slot_rows rows each.  1 <= slot_rows, 0 <= n_tiles <= RADNET_SCAN_MAX_TILES and
+ * n_tiles * slot_rows <= RADNET_SCAN_MAX_BOXES; per entry slot >= 0, even (the slot is 8-byte aligned) and slot + slot_words <=
+ * pool_words; no two slots overlap (they may stand in any order); 0 <= image < RADNET_SCAN_MAX_IMAGES, not below the entry
+ * before; |ox|, |oy| <= RADNET_SCAN_MAX_COORD, so that ox + any int32 coordinate of a record is an int64 sum that the device
+ * forms without overflow and then holds against RADNET_SCAN_MAX_COORD.  RADNET_OK with the number of images (last index + 1; 0
+ * for no tiles) in *n_images, or RADNET_ERR_ARG with the index of the first bad entry in *bad_entry (-1 when the arguments
+ * themselves are at fault) and a sentence naming the entry and the field in msg (at most msg_cap bytes with the terminator).
+ * n_images, bad_entry and msg may be null.  Reads exactly n_tiles entries. */
+int radnet_scan_merge_check(const radnet_scan_tile* tiles, int32_t n_tiles, int64_t pool_words, int32_t slot_rows, int32_t* n_images,
+                            int32_t* bad_entry, char* msg, int32_t msg_cap);
+
 /* One flat optimizer arena (train.py:236-252: one Adam per model). */
 typedef struct radnet_adam_desc {
   float* p; float* g; float* m; float* v; int64_t n; int32_t t; float lr;

@@ -17,6 +17,7 @@
 //                              pick order, float floor division by the resize ratio, one compact record array.
 //                        No floating-point atomics, plain vector stores, no scratch memory outside LDS.
 #include "radnet_internal.h"
+#include "nms_device.h"
 
 namespace {
 
@@ -46,21 +47,8 @@ __device__ __forceinline__ unsigned int sortable_bits(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// rpn.py:429-447 with i = the picked box: proposals.hip's test (the rounded quotient against thr; the division only where its
-// rounding can decide)
-__device__ __forceinline__ bool suppresses(const double4& pk, double pk_area, const double4& c, double c_area, double thr) {
-  const double ww = fmax(0.0, fmin(pk.z, c.z) - fmax(pk.x, c.x));
-  const double hh = fmax(0.0, fmin(pk.w, c.w) - fmax(pk.y, c.y));
-  const double inter = ww * hh;
-  const double uni = pk_area + c_area - inter;
-  const double d = uni + 1e-6;
-  if (d > 0.0 && thr > 0.0) {
-    const double t = thr * d;
-    if (inter > t * (1.0 + 0x1p-40)) return true;
-    if (inter < t * (1.0 - 0x1p-40)) return false;
-  }
-  return inter / d > thr;
-}
+// suppresses(): nms_device.h -- proposals.hip's test (the rounded quotient against thr; the division only where its rounding can
+// decide)
 
 // NumPy's / Python's float floor division (npy_divmod: fmod-based, NOT floor(a / b)); b != 0
 __device__ __forceinline__ double floor_divide(double a, double b) {

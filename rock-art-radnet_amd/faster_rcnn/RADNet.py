@@ -6,6 +6,7 @@
     .draw_detections(img, dets) / .write_predictions(dets, img, dir)   predict.py:90-181 (boxes and files; no text labels)
     .predict_region_proposals(img) / .objectness_maps(img)             RADNet.py:310-480 (the RPN alone; score maps as levels)
     .format_img / .apply_spatial_pyramid_pooling / .final_nms / .get_real_coordinates
+    .predict_device(images) / .final_nms_device / .scan_tail                the merge of a scan on the device (csrc/scan_tail.hip)
     load_radnet(config_path)                                           RADNet.py:721-775
 
 The model objects are duck-typed exactly as in the reference (anything with .predict works, which is how the
@@ -92,6 +93,7 @@ class RADNet():
 
     device_resident = True      # engine-backed models: keep tiles on the device between the stages (see _detect)
     device_tail = True          # ... and decode + per-class NMS + source-pixel coordinates too (see _tail_on_device)
+    scan_tail = False           # ... and the merge of a scan's tiles: final_nms per image, NMS across images (see _scan_tail_on)
 
     def __init__(self, C, model_rpn, model_detector, preprocess_func):
         self.is_object_threshold = 0.5
@@ -231,6 +233,28 @@ class RADNet():
         new_probs = [probs[c].mean() for c in clusters]
         return np.array(new_boxes), np.array(new_probs)
 
+    def final_nms_device(self, boxes, probs, obj_avg_threshold=0.2, obj_confidence_threshold=0.8, n_obj_avg=5):
+        """final_nms computed by radnet_final_nms (csrc/scan_tail.hip): same arguments, same return, bit for bit, for the arrays
+        predict hands it -- integer boxes [n][4] and float32 probs [n] (anything else is a TypeError: there is no device form of
+        it).  One upload, one launch, one download on the calling thread's default context, like rpn.non_max_suppression_fast.
+        AssertionError where final_nms asserts (a box with x1 >= x2 or y1 >= y2).  The inputs the kernel reports and does not
+        take -- a cluster whose best prob EQUALS the threshold, a coordinate beyond +-2^29, a NaN prob -- go to final_nms."""
+        from radnet_hip import runtime as rt
+        from radnet_hip.engine import final_nms_groups
+        if len(boxes) == 0:
+            return []
+        boxes, probs = np.asarray(boxes), np.asarray(probs)
+        if boxes.dtype.kind != "i" or boxes.ndim != 2 or boxes.shape[1] != 4 or probs.dtype != np.float32 or probs.shape != (boxes.shape[0],):
+            raise TypeError("final_nms_device takes integer boxes [n][4] and float32 probs [n], not %s %s and %s %s"
+                            % (boxes.dtype, boxes.shape, probs.dtype, probs.shape))
+        with rt.default_scope() as ctx:
+            (status, nb, npr), = final_nms_groups(ctx, [(boxes, probs)], obj_avg_threshold, obj_confidence_threshold, n_obj_avg)
+        if status == -1:                        # RADNET_FINAL_NMS_MALFORMED
+            raise AssertionError("final_nms: box with x1 >= x2 or y1 >= y2")
+        if status < 0:
+            return self.final_nms(boxes, probs, obj_avg_threshold, obj_confidence_threshold, n_obj_avg)
+        return nb, npr
+
     # ---- inference ---------------------------------------------------------------------------------------------------
     def _detect(self, img):
         """One network pass on an image or tile: {class: (boxes in source px, probs)} after the per-class NMS 0.2.
@@ -290,7 +314,10 @@ class RADNet():
         return self.model_detector.detect_launch(bp, R_dev, Rn_dev, n, ratio, self.C.n_rois, self.bbox_threshold, nms_thresh=0.2)
 
     def _tail_collect(self, handle):
-        cls, boxes, probs = self.model_detector.detect_finish(handle)
+        return self._det_from_records(*self.model_detector.detect_finish(handle))
+
+    def _det_from_records(self, cls, boxes, probs):
+        """A tile's records (engine.read_detections) as _per_class_nms returns them: {class: (boxes in source px, probs)}."""
         out = {}
         for c, b, p in zip(cls.tolist(), boxes.tolist(), probs):
             real, pr = out.setdefault(self.class_mapping[c], ([], []))
@@ -410,21 +437,16 @@ class RADNet():
         merge per image, then NMS 0.4 across images.  An image is a NumPy array or a uint8 [H][W][3] contiguous cuda tensor
         (png.decode_device, utils_io.get_image(..., to_host=False), utils_io.DeviceImageLoader).  With the engine-backed models a
         device image stays on the device: every tile is cut out of it and resized in one launch (ImageWindow) and nothing
-        image-sized crosses PCIe; the detections are those of the host array with the same bytes."""
+        image-sized crosses PCIe; the detections are those of the host array with the same bytes.
+        `scan_tail = True` (engine-backed models, see _scan_tail_on) merges the scan on the device: same list, one download."""
         C = self.C
         for img in images:
             if _is_device_image(img):
                 check_device_image(img)             # every image, before any device work starts
+        if self._scan_tail_on():
+            return self._scan_pass(images).to_host()
         all_boxes, all_probs = {}, {}
         for img in images:
-            boxes_img, probs_img = {}, {}
-
-            def collect(det, ox, oy):
-                for key, (real, pr) in det.items():
-                    for (rx1, ry1, rx2, ry2), p in zip(real, pr):
-                        boxes_img.setdefault(key, []).append([ox + rx1, oy + ry1, ox + rx2, oy + ry2])
-                        probs_img.setdefault(key, []).append(p)
-
             if _is_device_image(img) and not self._takes_device_images():
                 img = img.cpu().numpy()             # one download, then the host path
             if _is_device_image(img):
@@ -438,14 +460,27 @@ class RADNet():
                 work = [np.copy(img[ty0:ty1, tx0:tx1, :]) for (tx0, ty0, tx1, ty1) in spans] + ([img] if C.include_full_img else [])
                 offs = [(tx0, ty0) for (tx0, ty0, tx1, ty1) in spans] + ([(0, 0)] if C.include_full_img else [])
                 dets_img = self._detect_sharded(work)
-            for det, (ox, oy) in zip(dets_img, offs):
-                collect(det, ox, oy)
-            for key in boxes_img:
-                nb, npr = self.final_nms(np.array(boxes_img[key]), np.array(probs_img[key]), obj_avg_threshold=0.2,
-                                         obj_confidence_threshold=0.8, n_obj_avg=5)
-                for j in range(nb.shape[0]):
-                    all_boxes.setdefault(key, []).append(list(nb[j, :]))
-                    all_probs.setdefault(key, []).append(npr[j])
+            self._merge_image(dets_img, offs, all_boxes, all_probs)
+        return self._merge_final(all_boxes, all_probs)
+
+    def _merge_image(self, dets_img, offs, all_boxes, all_probs):
+        """The merge of one image's tiles on the host (RADNet.py:577-600): the tiles' offsets, then final_nms per class, appended
+        to the call's dicts."""
+        boxes_img, probs_img = {}, {}
+        for det, (ox, oy) in zip(dets_img, offs):
+            for key, (real, pr) in det.items():
+                for (rx1, ry1, rx2, ry2), p in zip(real, pr):
+                    boxes_img.setdefault(key, []).append([ox + rx1, oy + ry1, ox + rx2, oy + ry2])
+                    probs_img.setdefault(key, []).append(p)
+        for key in boxes_img:
+            nb, npr = self.final_nms(np.array(boxes_img[key]), np.array(probs_img[key]), obj_avg_threshold=0.2,
+                                     obj_confidence_threshold=0.8, n_obj_avg=5)
+            for j in range(nb.shape[0]):
+                all_boxes.setdefault(key, []).append(list(nb[j, :]))
+                all_probs.setdefault(key, []).append(npr[j])
+
+    def _merge_final(self, all_boxes, all_probs):
+        """NMS 0.4 across the images per class (RADNet.py:700-718) -> predict's list of dicts."""
         dets = []
         for key in all_boxes:
             nb, npr = rpn.non_max_suppression_fast(np.array(all_boxes[key]), np.array(all_probs[key]), overlap_thresh=0.4)
@@ -453,6 +488,101 @@ class RADNet():
                 x1, y1, x2, y2 = nb[j, :]
                 dets.append({'class': key, 'prob': npr[j], 'x1': x1, 'y1': y1, 'x2': x2, 'y2': y2})
         return dets
+
+    # ---- the merge of a scan on the device (csrc/scan_tail.hip) -------------------------------------------------------------
+    def _scan_tail_on(self):
+        """`scan_tail = True` with engine-backed models and the tile tail on the device (_tail_on_device): every tile's records
+        stay in a slot of one device pool, ONE radnet_scan_merge behind the last tile of the last image does what _merge_image
+        and _merge_final do on the host, and one small download brings the detections.  The tile loop still reads 4 bytes per
+        tile (the proposal count) and never a record.  Same detections as the host merge, which stays the path of the default
+        (`scan_tail = False`), of duck-typed models, `device_tail = False`, `device_resident = False` and of predict sharded over
+        ranks (set_distributed): the records of other ranks arrive on the host there."""
+        eng = self._engine()
+        return bool(self.scan_tail and self._tail_on_device() and eng is not None and hasattr(eng, "lane") and hasattr(eng, "scan_merge")
+                    and not self._sharded())
+
+    def _sharded(self):
+        if not getattr(self, "_dist_on", False):
+            return False
+        import torch.distributed as dist
+        return dist.is_available() and dist.is_initialized() and dist.get_world_size(getattr(self, "_dist_group", None)) > 1
+
+    def _scan_pass(self, images, own_pool=False):
+        """The tile passes of `images` with every tile's records written into its slot of a device pool, then radnet_scan_merge:
+        a DeviceDetections, nothing waited for but the proposal counts.  own_pool: a pool of its own, so that the result outlives
+        the next call (predict_device); otherwise the pool of the last call of the same size is used again."""
+        import torch
+        eng, C = self._engine(), self.C
+        for img in images:
+            if _is_device_image(img):
+                check_device_image(img)
+        per_image = []
+        for img in images:
+            if _is_device_image(img):
+                work, offs = tile_windows(img, C, eng.mark())       # the image's bytes are valid behind the caller's stream up to here
+            else:
+                if C.max_n_tiles_train > 0:                 # the reference gates tiling on this training knob (RADNet.py:511)
+                    h, w = img.shape[:2]
+                    spans = [(tx0, ty0, tx1, ty1) for (ty0, ty1) in _spans(h, C.tile_size, C.tile_overlap) for (tx0, tx1) in _spans(w, C.tile_size, C.tile_overlap)]
+                else:
+                    spans = []
+                work = [np.copy(img[ty0:ty1, tx0:tx1, :]) for (tx0, ty0, tx1, ty1) in spans] + ([img] if C.include_full_img else [])
+                offs = [(tx0, ty0) for (tx0, ty0, tx1, ty1) in spans] + ([(0, 0)] if C.include_full_img else [])
+            per_image.append((work, offs))
+        tiles = [t for work, _ in per_image for t in work]
+        k = C.n_rois
+        rows = (300 + k - 1) // k * k                       # the head's rows for propose_launch's 300 proposals at most
+        with torch.cuda.stream(eng.main_stream):
+            key = (len(tiles), rows)
+            cached = getattr(self, "_scan_pool", None)
+            if own_pool or cached is None or cached[0] != key:
+                pool, slot_words = eng.scan_pool(len(tiles), rows)
+                if not own_pool:
+                    self._scan_pool = (key, pool, slot_words)
+            else:
+                _, pool, slot_words = cached
+            table = eng.scan_table([(j * slot_words, ox, oy, im) for im, (_, offs) in enumerate(per_image) for j, (ox, oy) in
+                                    enumerate(offs, sum(len(w) for w, _ in per_image[:im]))])
+            self._scan_tiles(tiles, eng, pool, slot_words)
+            out = eng.scan_merge(pool, rows, table, obj_avg_threshold=0.2, obj_confidence_threshold=0.8, n_obj_avg=5, nms_thresh=0.4, max_boxes=300)
+            done = eng.mark()
+        return DeviceDetections(out, done, self, pool, slot_words, [offs for _, offs in per_image])
+
+    def _scan_tiles(self, tiles, eng, pool, slot_words):
+        """_detect_all_tail's schedule with nothing collected: tile j's records go to slot j of the pool and stay there."""
+        def launch(j, head_done):
+            with eng.lane("side"):
+                eng.after(head_done)                     # the classifier pass that last read this buffer set
+                img_dev, ratio = self.format_img_size(tiles[j], keep_on_device=True, ctx=eng.ctx)
+                h = self.model_rpn.propose_launch(img_dev, overlap_thresh=0.7, slot=j % 2)
+                return h, ratio, self.model_rpn.count_launch(h)
+
+        done = [None, None]
+        nxt = launch(0, None) if tiles else None
+        for j in range(len(tiles)):
+            (h, ratio, counted), nxt = nxt, None
+            n = self.model_rpn.count_finish(counted)     # waits for the side lane up to tile j's proposals, nothing else
+            eng.after(counted[1])
+            R_dev, Rn_dev, bp = h
+            self.model_detector.detect_launch(bp, R_dev, Rn_dev, n, ratio, self.C.n_rois, self.bbox_threshold, nms_thresh=0.2,
+                                              out=pool[j * slot_words:(j + 1) * slot_words])
+            done[j % 2] = eng.mark()
+            if j + 1 < len(tiles):
+                nxt = launch(j + 1, done[(j + 1) % 2])
+
+    def predict_device(self, images):
+        """predict with the scan merged on the device (as `scan_tail = True`, whatever the attribute says), for callers that keep
+        working there: a DeviceDetections -- the merged records as a device tensor, valid behind its `ready` event; to_host()
+        gives predict's list.  Engine-backed models with the tile tail on the device only (TypeError otherwise; not sharded)."""
+        saved = self.scan_tail
+        self.scan_tail = True
+        try:
+            if not self._scan_tail_on():
+                raise TypeError("predict_device needs the engine-backed models of load_radnet / models.build_models with device_resident and "
+                                "device_tail on, and no rank sharding: there is no host form of it (predict is)")
+            return self._scan_pass(images, own_pool=True)
+        finally:
+            self.scan_tail = saved
 
     def predict_from_path(self, img_path):
         """RADNet.py:482-500: one image per type of C.img_types when C.use_img_type, else the first type's, each read by
@@ -632,6 +762,50 @@ class RADNet():
         with open(paths[-1], "w") as outfile:
             json.dump(predictions, outfile, indent=4)
         return paths
+
+
+class DeviceDetections:
+    """What RADNet.predict_device returns.  records: a device int32 tensor, radnet_scan_merge's output (include/radnet_hip.h):
+    [0] count, [1] status, [2..7] reserved, then `count` records (class index, x1, y1, x2, y2, prob as fp32 bits) in predict's
+    order; ready: the event behind which it is valid (the engine's main stream).  len() and to_host() wait for it."""
+
+    def __init__(self, records, ready, net, pool, slot_words, offsets):
+        self.records, self.ready = records, ready
+        self._net, self._pool, self._slot_words, self._offsets, self._words = net, pool, slot_words, offsets, None
+
+    def words(self):
+        """The records' words on the host: waits for `ready`, one download, kept."""
+        if self._words is None:
+            self.ready.synchronize()
+            self._words = self.records.cpu().numpy()
+        return self._words
+
+    @property
+    def status(self):
+        return int(self.words()[1])
+
+    def __len__(self):
+        return int(self.words()[0]) if self.status == 0 else len(self.to_host())
+
+    def to_host(self):
+        """predict's list of dicts.  With a negative status (a tile met a malformed box, a cluster's best prob equals the
+        threshold, ...) the pool comes down once and the host merge runs on it: it raises what the host path raises, or
+        returns what it returns."""
+        from radnet_hip.engine import read_detections, read_scan_records
+        net = self._net
+        status, cls, boxes, probs = read_scan_records(self.words())
+        if status == 0:
+            return [{'class': net.class_mapping[c], 'prob': p, 'x1': b[0], 'y1': b[1], 'x2': b[2], 'y2': b[3]}
+                    for c, b, p in zip(cls.tolist(), boxes.astype(np.int64), probs)]
+        pool = self._pool.cpu().numpy()
+        all_boxes, all_probs, j = {}, {}, 0
+        for offs in self._offsets:
+            dets_img = []
+            for _ in offs:
+                dets_img.append(net._det_from_records(*read_detections(pool[j * self._slot_words:(j + 1) * self._slot_words])))
+                j += 1
+            net._merge_image(dets_img, offs, all_boxes, all_probs)
+        return net._merge_final(all_boxes, all_probs)
 
 
 RECT = np.dtype([(k, np.int32) for k in ("x1", "y1", "x2", "y2", "thickness", "b", "g", "r")])      # radnet_rect, 32 bytes

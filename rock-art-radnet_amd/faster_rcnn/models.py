@@ -292,16 +292,19 @@ class DetectorModel(_ModelBase):
     def predict(self, inputs, **kw):
         return self.predict_finish(self.predict_launch(inputs))
 
-    def detect_launch(self, bp, R_dev, Rn_dev, n, ratio, k, bbox_threshold, nms_thresh=0.2, max_boxes=300):
+    def detect_launch(self, bp, R_dev, Rn_dev, n, ratio, k, bbox_threshold, nms_thresh=0.2, max_boxes=300, out=None):
         """The classifier pass of a tile AND its detection tail, enqueued on the current lane, nothing read back: RoIs from the
         proposals on the device (R_dev int64 xyxy, Rn_dev their device count, n the same count on the host: it fixes the row
         count ceil(n / k) * k, so the head runs the launches predict_launch would), classifier, decode + per-class NMS + source
-        pixels (csrc/detect_tail.hip), records into pinned memory."""
+        pixels (csrc/detect_tail.hip), records into pinned memory -- or, with `out` (a slot of engine.scan_pool), into that device
+        buffer alone (RADNet.scan_tail)."""
         eng = self._s.eng
         rows = (int(n) + k - 1) // k * k
         hp = eng._plan_head(rows, bp["fh"], bp["fw"], bp["F"], training=False)
         eng.head_rois_from_proposals(hp, R_dev, Rn_dev, k)
         eng.head_forward(hp)
+        if out is not None:
+            return eng.detect_tail(hp, Rn_dev, ratio, k, bbox_threshold, nms_thresh, max_boxes, out=out)
         return eng.detect_tail(hp, Rn_dev, ratio, k, bbox_threshold, nms_thresh, max_boxes)
 
     @staticmethod

@@ -69,6 +69,57 @@ def read_detections(words):
     return rec[:, 0], rec[:, 1:5], rec[:, 5].view(np.float32)
 
 
+SCAN_TILE = np.dtype([(k, np.int32) for k in ("slot", "ox", "oy", "image")])      # radnet_scan_tile, 16 bytes
+
+
+def confidence_f32(t):
+    """final_nms compares fp32 probs with obj_confidence_threshold both ways (`max < t`, `p > t`).  For a Python number NumPy 2
+    casts it to fp32 first, and so does this; a NumPy fp64 scalar makes the comparisons fp64, which one fp32 value stands for only
+    when the threshold is one: anything else is refused (the host final_nms takes it)."""
+    u = np.float32(t)
+    if isinstance(t, np.generic) and float(u) != float(t):
+        raise ValueError("final_nms on the device: the threshold %r is an fp64 scalar that is no fp32 value" % (t,))
+    return float(u)
+
+
+def final_nms_groups(ctx, groups, obj_avg_threshold=0.2, obj_confidence_threshold=0.8, n_obj_avg=5):
+    """radnet_final_nms on a batch: groups = [(boxes int64 [n][4], probs float32 [n]), ...] -> [(status, boxes int64 [k][4], probs
+    float32 [k]), ...], one upload, one launch on the stream of `ctx` (made current by the caller), one download.  With a negative
+    status (RADNET_FINAL_NMS_*) the other two are None."""
+    sizes = [int(len(p)) for _, p in groups]
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    cap, ng = int(offsets[-1]), len(groups)
+    if ng == 0:
+        return []
+    boxes = np.concatenate([np.asarray(b, dtype=np.int64).reshape(-1, 4) for b, _ in groups] + [np.zeros((1, 4), np.int64)])
+    probs = np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for _, p in groups] + [np.zeros(1, np.float32)])
+    dev = torch.device("cuda", ctx.device_index)
+    bd, pd, od = (torch.from_numpy(a).to(dev) for a in (boxes, probs, offsets))
+    ob, op = torch.empty_like(bd), torch.empty_like(pd)
+    oc, os_ = torch.empty(ng, dtype=torch.int32, device=dev), torch.empty(ng, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(ctx.lib.radnet_final_nms_ws_bytes(cap, ng)), dtype=torch.uint8, device=dev)
+    d = L.FinalNmsDesc()
+    d.boxes, d.probs, d.offsets, d.n_groups, d.capacity = bd.data_ptr(), pd.data_ptr(), od.data_ptr(), ng, cap
+    d.obj_avg_threshold, d.obj_confidence_threshold, d.n_obj_avg = float(obj_avg_threshold), confidence_f32(obj_confidence_threshold), int(n_obj_avg)
+    d.out_boxes, d.out_probs, d.out_count, d.out_status, d.ws = ob.data_ptr(), op.data_ptr(), oc.data_ptr(), os_.data_ptr(), ws.data_ptr()
+    ctx.check(ctx.lib.radnet_final_nms(ctx.h, C.byref(d)), "radnet_final_nms")
+    ob, op, oc, os_ = ob.cpu().numpy(), op.cpu().numpy(), oc.cpu().numpy(), os_.cpu().numpy()
+    out = []
+    for g in range(ng):
+        lo, k, st = int(offsets[g]), int(oc[g]), int(os_[g])
+        out.append((st, None, None) if st < 0 else (0, ob[lo:lo + k].copy(), op[lo:lo + k].copy()))
+    return out
+
+
+def read_scan_records(words):
+    """The output of radnet_scan_merge (int32 words on the host) -> (status, class index [m] int32, boxes [m][4] int32, probs [m]
+    float32), copies; with a negative status the arrays are empty."""
+    words = words.numpy() if hasattr(words, "numpy") else np.asarray(words)
+    m, status = int(words[0]), int(words[1])
+    rec = words[L.DETECT_HEADER:L.DETECT_HEADER + L.DETECT_RECORD * m].reshape(m, L.DETECT_RECORD).copy()
+    return status, rec[:, 0], rec[:, 1:5], rec[:, 5].view(np.float32)
+
+
 class Arena:
     """One flat fp32 parameter arena (+ grads, Adam moments) with named views: a single Adam launch and a
     single all-reduce cover every tensor of an optimizer (train.py:236-252 has one Adam per model)."""
@@ -1128,14 +1179,66 @@ class FasterRCNNEngine:
         d.out = out.data_ptr()
         return d
 
-    def detect_tail(self, hp, n_dev, ratio, k, bbox_threshold, nms_thresh=0.2, max_boxes=300):
+    def detect_tail(self, hp, n_dev, ratio, k, bbox_threshold, nms_thresh=0.2, max_boxes=300, out=None):
         """Decode + per-class NMS + source-pixel coordinates of a finished classifier pass (RADNet.py:124-154, 562-575, 44-51)
         as one launch on the current lane, then the records into the plan's pinned buffer.  Nothing is waited for: returns
-        (pinned int32 words, event); read_detections() turns the words into records once the event has happened."""
-        d = self.detect_tail_desc(hp, n_dev, ratio, k, bbox_threshold, nms_thresh, max_boxes)
+        (pinned int32 words, event); read_detections() turns the words into records once the event has happened.
+        out: a device int32 tensor of radnet_detect_tail_out_bytes(rows of the plan) bytes or more (a slot of scan_pool): the
+        records go there and nowhere else -- no copy to the host; returns (None, event)."""
+        d = self.detect_tail_desc(hp, n_dev, ratio, k, bbox_threshold, nms_thresh, max_boxes, out=out)
+        if out is not None and out.numel() * out.element_size() < int(self.lib.radnet_detect_tail_out_bytes(hp["R"])):
+            raise L.RadnetError("detect_tail: an output of %d bytes for %d rows" % (out.numel() * out.element_size(), hp["R"]))
         self.ctx.check(self.lib.radnet_detect_tail(self.ctx.h, C.byref(d)), "radnet_detect_tail")
+        if out is not None:
+            return None, self.mark()
         self._copy(hp["det_host"], hp["det_out"])
         return hp["det_host"], self.mark()
+
+    # ------------------------------------------------------------------------------------------ scan merge (csrc/scan_tail.hip)
+    def scan_pool(self, n_tiles, rows):
+        """A device pool of n_tiles slots, each what radnet_detect_tail writes for a head of at most `rows` rows: (pool int32
+        [n_tiles * slot_words], slot_words).  Slot j is pool[j * slot_words:(j + 1) * slot_words] (detect_tail(..., out=))."""
+        words = int(self.lib.radnet_detect_tail_out_bytes(int(rows))) // 4
+        return torch.zeros(max(1, int(n_tiles)) * words, dtype=torch.int32, device=self.dev), words
+
+    def scan_table(self, tiles):
+        """The tile table of scan_merge, rows (slot offset in words, ox, oy, image index), as (host array, device bytes): uploaded
+        on the current lane, so ahead of the tile passes when it is made before them."""
+        table = np.array([tuple(int(v) for v in t) for t in tiles], SCAN_TILE).reshape(-1)
+        return table, (torch.from_numpy(table.view(np.int32).copy()).to(self.dev) if len(table) else None)
+
+    def scan_merge(self, pool, rows, table, nc=None, obj_avg_threshold=0.2, obj_confidence_threshold=0.8, n_obj_avg=5, nms_thresh=0.4, max_boxes=300,
+                   out=None):
+        """radnet_scan_merge on the current lane: the tiles' records in `pool` (slots of `rows` rows, scan_pool), `table` from
+        scan_table (or a sequence of rows, uploaded here) -> the device int32 words of the merged records (read_scan_records).
+        radnet_scan_merge_check runs first on the host table; nothing is waited for.  The workspace is kept per problem size."""
+        if not isinstance(table, tuple):
+            table = self.scan_table(table)
+        host, dev_table = table
+        nc = self.nc if nc is None else int(nc)
+        max_boxes = int(max_boxes)
+        rc, n_images, bad, msg = L.scan_merge_check(host if len(host) else None, pool.numel(), rows)
+        if rc != 0:
+            raise L.RadnetError("radnet_scan_merge_check: %s" % msg)
+        key = ("scan_merge", len(host), int(rows), n_images, nc, max_boxes)
+        cache = self.__dict__.setdefault("_scan_ws", {})      # a handful of scan geometries per engine: kept, not evicted
+        ws = cache.get(key)
+        if ws is None:
+            ws = cache[key] = torch.empty(int(self.lib.radnet_scan_merge_ws_bytes(len(host), int(rows), n_images, nc, max_boxes)), dtype=torch.uint8,
+                                                device=self.dev)
+        if out is None:
+            out = torch.empty(int(self.lib.radnet_scan_merge_out_bytes(nc, max_boxes)) // 4, dtype=torch.int32, device=self.dev)
+        d = L.ScanMergeDesc()
+        d.pool, d.pool_words, d.slot_rows = pool.data_ptr(), pool.numel(), int(rows)
+        d.tiles_host, d.tiles_dev, d.n_tiles, d.nc = (host.ctypes.data if len(host) else None), (dev_table.data_ptr() if len(host) else None), len(host), nc
+        d.obj_avg_threshold, d.obj_confidence_threshold, d.n_obj_avg = float(obj_avg_threshold), confidence_f32(obj_confidence_threshold), int(n_obj_avg)
+        d.nms_thresh, d.max_boxes, d.out, d.ws = float(nms_thresh), max_boxes, out.data_ptr(), ws.data_ptr()
+        self.ctx.check(self.lib.radnet_scan_merge(self.ctx.h, C.byref(d)), "radnet_scan_merge")
+        return out
+
+    def final_nms_device(self, groups, obj_avg_threshold=0.2, obj_confidence_threshold=0.8, n_obj_avg=5):
+        """RADNet.final_nms on a batch of groups in one launch on the current lane (final_nms_groups)."""
+        return final_nms_groups(self.ctx, groups, obj_avg_threshold, obj_confidence_threshold, n_obj_avg)
 
     # ------------------------------------------------------------------------------------------ classifier head
     def _plan_head(self, R, fh, fw, F, training=True, groups=1):

@@ -82,6 +82,30 @@ class DetectTailDesc(C.Structure):
                 ("max_boxes", C.c_int32), ("out", C.c_void_p)]
 
 
+class FinalNmsDesc(C.Structure):
+    """Mirror of `radnet_final_nms_desc`."""
+    _fields_ = [("boxes", C.c_void_p), ("probs", C.c_void_p), ("offsets", C.c_void_p),
+                ("n_groups", C.c_int32), ("capacity", C.c_int32),
+                ("obj_avg_threshold", C.c_double), ("obj_confidence_threshold", C.c_float), ("n_obj_avg", C.c_int32),
+                ("out_boxes", C.c_void_p), ("out_probs", C.c_void_p), ("out_count", C.c_void_p), ("out_status", C.c_void_p),
+                ("ws", C.c_void_p)]
+
+
+class ScanTile(C.Structure):
+    """Mirror of `radnet_scan_tile` (16 bytes; engine.SCAN_TILE is the same row as a NumPy dtype)."""
+    _fields_ = [("slot", C.c_int32), ("ox", C.c_int32), ("oy", C.c_int32), ("image", C.c_int32)]
+
+
+class ScanMergeDesc(C.Structure):
+    """Mirror of `radnet_scan_merge_desc`."""
+    _fields_ = [("pool", C.c_void_p), ("pool_words", C.c_int64), ("slot_rows", C.c_int32),
+                ("tiles_host", C.c_void_p), ("tiles_dev", C.c_void_p),
+                ("n_tiles", C.c_int32), ("nc", C.c_int32),
+                ("obj_avg_threshold", C.c_double), ("obj_confidence_threshold", C.c_float), ("n_obj_avg", C.c_int32),
+                ("nms_thresh", C.c_double), ("max_boxes", C.c_int32),
+                ("out", C.c_void_p), ("ws", C.c_void_p)]
+
+
 AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SALT_PEPPER, AUG_GAUSSIAN, AUG_POISSON = range(5)      # RADNET_AUG_* modes of radnet_aug_pointwise_u8
 DETECT_HEADER, DETECT_RECORD = 8, 6      # int32 words in front of / per record of radnet_detect_tail's output
 
@@ -297,6 +321,12 @@ def load_library():
         "radnet_detect_tail": (C.c_int, [vp, C.POINTER(DetectTailDesc)]),
         "radnet_rois_from_proposals": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
         "radnet_predict_tile_detect": (C.c_int, [vp, C.POINTER(TileDesc), C.POINTER(DetectTailDesc)]),
+        "radnet_final_nms_ws_bytes": (u64, [i32, i32]),
+        "radnet_final_nms": (C.c_int, [vp, C.POINTER(FinalNmsDesc)]),
+        "radnet_scan_merge_out_bytes": (u64, [i32, i32]),
+        "radnet_scan_merge_ws_bytes": (u64, [i32, i32, i32, i32, i32]),
+        "radnet_scan_merge": (C.c_int, [vp, C.POINTER(ScanMergeDesc)]),
+        "radnet_scan_merge_check": (C.c_int, [vp, i32, i64, i32, C.POINTER(i32), C.POINTER(i32), C.c_char_p, i32]),
         "radnet_train_step": (C.c_int, [vp, C.POINTER(TrainDesc), C.POINTER(HostHooks), C.POINTER(C.c_float), C.POINTER(i32)]),
         "radnet_comm_unique_id": (C.c_int, [C.c_char_p]),
         "radnet_comm_init": (C.c_int, [vp, i32, i32, C.c_char_p]),
@@ -354,6 +384,18 @@ def heat_check(table, pool_len, h, w, count=None):
     rc = load_library().radnet_heat_check(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(pool_len), int(h),
                                           int(w), C.byref(bad), msg, len(msg))
     return rc, bad.value, msg.value.decode()
+
+
+def scan_merge_check(table, pool_words, slot_rows, count=None):
+    """radnet_scan_merge_check (host only, no context, no device) on a table of radnet_scan_tile rows -- a NumPy array of 16 bytes
+    per entry, or None for a null table -- for a pool of pool_words int32 words whose slots hold slot_rows rows:
+    (rc, number of images, index of the bad entry or -1, the message).  count defaults to the table's length."""
+    import numpy as np
+    rows = np.zeros((0, 16), np.uint8) if table is None else np.ascontiguousarray(table).view(np.uint8).reshape(-1, 16)
+    n_images, bad, msg = C.c_int32(-2), C.c_int32(-2), C.create_string_buffer(256)
+    rc = load_library().radnet_scan_merge_check(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(pool_words),
+                                                int(slot_rows), C.byref(n_images), C.byref(bad), msg, len(msg))
+    return rc, n_images.value, bad.value, msg.value.decode()
 
 
 def _ptr(t):
