@@ -670,6 +670,116 @@ int radnet_deflate_pack(radnet_ctx* ctx, const uint8_t* pieces, int64_t piece_ca
  * 1 for distance symbol 0, four bits each: 1222 bits.  A match's distance code is therefore one zero bit (dist_nbits = 1).
  * A null pointer or header_cap < 153 is RADNET_ERR_ARG and nothing is written. */
 int radnet_deflate_build_code(const uint32_t* hist, radnet_deflate_code* code, uint8_t* header, int32_t header_cap, int32_t* header_nbits);
+/* ---- inflate of run-length streams on the device (csrc/inflate.hip, csrc/inflate_plan.cpp): speculative block search ----------------
+ * The reader's counterpart of the section above, for the streams this project meets: zlib level 1 with Z_RLE (cv2.imwrite's
+ * defaults), png.assemble and the device deflate.  Every match of such a stream has distance 1, so a block's output depends on the
+ * blocks in front of it through ONE byte, and a dynamic block header can be recognised at any bit offset.  z is the whole zlib
+ * stream of n bytes (device; no alignment asked): 2 header bytes, the deflate blocks, the 4 bytes of the Adler-32; bit b of the
+ * stream is bit b % 8 of byte b / 8 (RFC 1951 3.1.1) and first_bit is 16 for such a stream.  Nothing here waits on another
+ * workgroup or spins; every loop is bounded by the stream's length and by RADNET_INFLATE_UNIT_MAX_SYMBOLS.
+ * A UNIT is a run of consecutive deflate blocks: it begins at a given bit with a block of any type, continues while the next block
+ * is stored or fixed (their headers cannot be recognised speculatively, so they ride with the block in front of them) and ends
+ * before the next dynamic block or behind a block with BFINAL set.
+ * THE READING RULE shared by the three kernels and tests/inflate_cases.py: bits beyond the stream read as zero; after every group of
+ * bits taken the position is compared with 8 * n and a position beyond it ends the unit with RADNET_INFLATE_PAST_END before the
+ * value is looked at; a code word that no symbol has is RADNET_INFLATE_BAD_CODE (PAST_END if fewer than 15 bits were left).
+ * RADNET_INFLATE_UNIT_MAX_SYMBOLS is 8 times the largest block zlib emits (32,767 symbols at memLevel 9); it bounds the time a
+ * false candidate, or a file made of fixed blocks, can hold a wave. */
+#define RADNET_INFLATE_UNIT_MAX_SYMBOLS 262144
+#define RADNET_INFLATE_OK 0
+/* BTYPE 11, or a dynamic header radnet_inflate_find_blocks would not accept */
+#define RADNET_INFLATE_BAD_HEADER 1
+/* a code word without a symbol, literal/length symbol 286 / 287, distance symbol 30 / 31 */
+#define RADNET_INFLATE_BAD_CODE 2
+/* a distance symbol other than 0: not a run-length stream */
+#define RADNET_INFLATE_NOT_RLE 3
+/* LEN != ~NLEN in a stored block */
+#define RADNET_INFLATE_STORED_MISMATCH 4
+/* ran past the stream */
+#define RADNET_INFLATE_PAST_END 5
+/* more than RADNET_INFLATE_UNIT_MAX_SYMBOLS literal/length symbols (end-of-block included) */
+#define RADNET_INFLATE_TOO_LONG 6
+/* the unit ends behind a block with BFINAL set */
+#define RADNET_INFLATE_FLAG_FINAL 1
+/* its first output comes from a match: it needs the byte in front of it */
+#define RADNET_INFLATE_FLAG_LEAD_MATCH 2
+/* it holds a literal or a stored byte, so last_byte does not depend on the predecessor */
+#define RADNET_INFLATE_FLAG_LAST_KNOWN 4
+typedef struct radnet_inflate_unit {
+  uint32_t start_bit;  /* given by the caller */
+  uint32_t end_bit;    /* the bit behind the unit: the next dynamic header, or the bit behind the final block (not byte aligned) */
+  uint32_t out_bytes, symbols, blocks;
+  uint32_t status;     /* RADNET_INFLATE_*; when it is not OK every field but start_bit and status is zero */
+  uint32_t flags;      /* RADNET_INFLATE_FLAG_* */
+  uint32_t last_byte;  /* the unit's last output byte if LAST_KNOWN, else 0 */
+} radnet_inflate_unit; /* 32 bytes */
+typedef struct radnet_inflate_link {
+  int64_t out_offset;  /* exclusive prefix sum of out_bytes along the chain */
+  uint32_t start_bit, out_bytes;
+  uint32_t prev_byte;  /* the output byte in front of the unit (0 for the first) */
+  uint32_t reserved;
+} radnet_inflate_link; /* 24 bytes */
+/* Host only (csrc/inflate_plan.cpp; no context, no device): the CRC-32 of `count` PNG chunks of the file in HOST memory, on up to
+ * `workers` threads (1..16; a run of consecutive chunks each), so that a map written as thousands of 8 KiB IDAT chunks does not pay a
+ * Python call per chunk.  Chunk k's length field stands at file[at[k]], its CRC field at file[end[k]]: the sum covers
+ * file[at[k] + 4 .. end[k]), the type and the payload, and is compared with the big-endian word at end[k].  Returns count when
+ * every sum matches, else the index of the first chunk whose sum does not; RADNET_ERR_ARG for a null pointer, count < 1, or a chunk
+ * that does not lie inside file_len (at[k] + 8 <= end[k], end[k] + 4 <= file_len). */
+int radnet_png_check_crcs(const uint8_t* file, int64_t file_len, const int64_t* at, const int64_t* end, int32_t count, int32_t workers);
+/* One thread per bit offset p in [first_bit, 8 * n): p is appended to cand exactly when a dynamic block header that zlib's inflate
+ * accepts begins there (BFINAL at p, either value).  The rule, in order: BTYPE is 10; 257 + HLIT <= 286 and 1 + HDIST <= 30; the
+ * code-length code is complete (Kraft sum exactly 1); no repeat symbol 16 comes first and no repeat runs past the declared count;
+ * symbol 256 has a non-zero length; the literal/length code is complete or a single 1-bit code; the distance code is complete, a
+ * single 1-bit code, or empty; every bit read lies inside the stream.  The append is unordered: idx = atomicAdd(count, 1) (integer;
+ * the caller zeroes *count, device uint32) and cand[idx] = p if idx < cand_cap, so *count may exceed cand_cap and nothing is written
+ * beyond the cap; the host sorts.  A null pointer, n < 3, first_bit < 0 or >= 8 * n, cand_cap < 0 is RADNET_ERR_ARG; n >= 2^29,
+ * where bit offsets leave 32 bits, RADNET_ERR_UNSUPPORTED; nothing is launched then. */
+int radnet_inflate_find_blocks(radnet_ctx* ctx, const uint8_t* z, int64_t n, int64_t first_bit, uint32_t* cand, int32_t cand_cap, uint32_t* count);
+/* Decodes the unit that begins at units[u].start_bit (device table, count entries; start_bit below 8 * n is the caller's to ensure,
+ * a larger one gives PAST_END) WITHOUT writing output, one wave per unit, and fills the other fields of the record.  The code tables
+ * stand in LDS, the compressed bytes pass through an LDS window, one lane decodes.  A unit AT the symbol cap (262,144 fixed-code literals, one wave alone on the device) took 114 to 134 ms when
+ * measured (tools/png_inflate_timing.py): that is what a false candidate or a file of fixed blocks can cost.
+ * Arguments refused as above; count < 1 is RADNET_ERR_ARG. */
+int radnet_inflate_rle_measure(radnet_ctx* ctx, const uint8_t* z, int64_t n, radnet_inflate_unit* units, int32_t count);
+/* Host only (csrc/inflate_plan.cpp; no context, no device, like radnet_png_plan_segments).  units: the measured records sorted by
+ * start_bit (strictly increasing).  Follows start -> end -> start from first_bit and writes the chained units in order to links
+ * (link_cap >= count always suffices) with their exclusive output offsets and the byte in front of each, inherited through units
+ * that produced no known byte.  *link_count = the links written; *false_count = count - *link_count, the candidates the chain
+ * never visits, when the chain is accepted.  Returns RADNET_INFLATE_CHAIN_OK, RADNET_ERR_ARG (a null pointer, count < 1, n < 1,
+ * first_bit < 0, expected < 0, link_cap < the links needed, unsorted starts) or one of the refusals below with *bad_unit = the
+ * index in `units` of the offending unit (for NO_START: the unit whose end bit is no measured start, or -1 when first_bit itself is
+ * none).  The refusals, checked per unit in this order while walking, LENGTH and TRAILER at the end:
+ *   NO_START   a position of the walk that is no measured start;
+ *   BAD_UNIT   a unit whose status is not RADNET_INFLATE_OK;
+ *   LEAD_MATCH a unit that begins with a match while no output byte stands in front of it (the first unit, or one behind empty ones);
+ *   LENGTH     the chain's total differs from `expected`;
+ *   TRAILER    the final unit's end, rounded up to a byte, plus 4 (the Adler-32) is not n. */
+#define RADNET_INFLATE_CHAIN_OK 0
+#define RADNET_INFLATE_CHAIN_NO_START 1
+#define RADNET_INFLATE_CHAIN_BAD_UNIT 2
+#define RADNET_INFLATE_CHAIN_LEAD_MATCH 3
+#define RADNET_INFLATE_CHAIN_LENGTH 4
+#define RADNET_INFLATE_CHAIN_TRAILER 5
+int radnet_inflate_chain(const radnet_inflate_unit* units, int32_t count, int64_t first_bit, int64_t n, int64_t expected, radnet_inflate_link* links,
+                         int32_t link_cap, int32_t* link_count, int32_t* false_count, int32_t* bad_unit);
+/* Decodes every chained unit again (links: device table, count entries) and writes its bytes to out[out_offset .. out_offset +
+ * out_bytes) (device) and nowhere else: a literal its byte, a stored block its bytes, a match the byte in front of it, which for the
+ * unit's first token is prev_byte.  A unit that would give more than its out_bytes, or pass out_len, is cut there; one that fails
+ * to decode stops (the caller checks the Adler-32 of `out` against the stream's trailer).  One wave per unit: one lane decodes a
+ * batch of tokens into LDS, the wave sums their lengths by prefix and all lanes expand them.  Arguments refused as above;
+ * out_len < 0 is RADNET_ERR_ARG. */
+int radnet_inflate_rle_emit(radnet_ctx* ctx, const uint8_t* z, int64_t n, const radnet_inflate_link* links, int32_t count, uint8_t* out,
+                            int64_t out_len);
+/* The filter-type column of an inflated stream on the device: column[k] = stream[offset[p] + r * (1 + rowbytes[p])] for the rows r
+ * of the passes p = 0 .. passes - 1 in order (k counts them through), one launch; offsets, rows and rowbytes are HOST arrays of
+ * `passes` (1..7) entries that travel with the launch.  The pass must lie inside stream_len.  png.py downloads the column, refuses
+ * a type above 4 and plans segments from it (radnet_png_plan_segments_column). */
+int radnet_png_gather_column_u8(radnet_ctx* ctx, const uint8_t* stream, int64_t stream_len, const int64_t* offsets, const int32_t* rows,
+                                const int32_t* rowbytes, int32_t passes, uint8_t* column);
+/* radnet_png_plan_segments for a pass whose filter-type bytes stand one behind the other: column[r] is the type of row r (HOST).
+ * Same rule, same result, same refusals. */
+int radnet_png_plan_segments_column(const uint8_t* column, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
+                                    radnet_png_segment* out, int32_t cap);
 /* Rectangles painted into a uint8 [h][w][3] device image (rows pitch_bytes apart) IN PLACE.  The contract is this package's own:
  *   the corners (x1, y1), (x2, y2) come in either order, as cv2.rectangle takes them, and are normalised to x1 <= x2, y1 <= y2;
  *   thickness < 0 (cv2.FILLED): pixel (x, y) is painted iff x1 <= x <= x2 and y1 <= y <= y2;

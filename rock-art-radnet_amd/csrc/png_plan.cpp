@@ -21,12 +21,12 @@ struct Column {
   }
 };
 
-}  // namespace
-
-extern "C" int radnet_png_plan_segments(const uint8_t* stream, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
-                                        radnet_png_segment* out, int32_t cap) {
+// the filter-type byte of row r stands at stream[r * pitch]: pitch = 1 + rowbytes inside a scanline stream, 1 in a compact column
+int plan(const uint8_t* stream, int64_t pitch, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows, radnet_png_segment* out,
+         int32_t cap) {
   if (!stream || !out || rows <= 0 || rowbytes <= 0 || cap <= 0 || stream_offset < 0 || target_rows < 0) return RADNET_ERR_ARG;
-  const Column col{stream, 1 + (int64_t)rowbytes, rows, target_rows ? target_rows : RADNET_PNG_SEGMENT_TARGET_ROWS};
+  const Column col{stream, pitch, rows, target_rows ? target_rows : RADNET_PNG_SEGMENT_TARGET_ROWS};
+  const int64_t line = 1 + (int64_t)rowbytes;
   for (int64_t r = 0; r < rows; ++r)
     if (stream[r * col.pitch] > 4) return RADNET_ERR_ARG;
   int64_t n = 0;
@@ -36,10 +36,22 @@ extern "C" int radnet_png_plan_segments(const uint8_t* stream, int64_t stream_of
   int64_t i = 0, last = -1;
   for (int64_t s = 0; s < rows; ++i) {
     const int64_t e = col.end_of(s), slot = merge ? i * cap / n : i;
-    if (slot != last) out[slot] = radnet_png_segment{stream_offset + s * col.pitch, 0, rowbytes};
+    if (slot != last) out[slot] = radnet_png_segment{stream_offset + s * line, 0, rowbytes};
     out[slot].rows += (int32_t)(e - s);
     last = slot;
     s = e;
   }
   return (int)(last + 1);
+}
+
+}  // namespace
+
+extern "C" int radnet_png_plan_segments(const uint8_t* stream, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
+                                        radnet_png_segment* out, int32_t cap) {
+  return plan(stream, 1 + (int64_t)rowbytes, stream_offset, rows, rowbytes, target_rows, out, cap);
+}
+
+extern "C" int radnet_png_plan_segments_column(const uint8_t* column, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
+                                               radnet_png_segment* out, int32_t cap) {
+  return plan(column, 1, stream_offset, rows, rowbytes, target_rows, out, cap);
 }

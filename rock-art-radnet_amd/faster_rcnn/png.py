@@ -13,6 +13,10 @@ stream, every palette and a table of segments -- runs of scanlines that start on
 row above them (radnet_png_plan_segments cuts each pass on the host) -- and one radnet_png_unfilter_segments_u8 per distinct bpp
 reconstructs all passes of all files, one workgroup per segment; the bytes are decode_device's.
 
+decode_device(inflate="device") uploads the COMPRESSED stream instead (parse_compressed) and inflates it on the device
+(csrc/inflate.hip: a speculative search for dynamic block headers at every bit offset, the units measured, chained on the host and
+emitted), for run-length streams; whatever the device cannot take goes to the host path above.  The default is that path, byte for byte.
+
 Formats: colour types 0, 2, 3, 4, 6 with the bit depths 1, 2, 4, 8, 16 the PNG specification allows for each; non-interlaced and
 Adam7.  Output rules: grey is replicated to three channels, depths 1 / 2 / 4 scaled by 255 / 85 / 17; palette entries are looked up
 (an index beyond the PLTE length gives 0); alpha channels and tRNS are dropped, not blended; 16-bit samples keep their high byte
@@ -164,12 +168,279 @@ def parse(data):
     return Image(header, palette, stream, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8))
 
 
-def decode_device(data, ctx=None):
+INFLATE_UNIT = np.dtype([(k, np.uint32) for k in ("start_bit", "end_bit", "out_bytes", "symbols", "blocks", "status", "flags", "last_byte")])      # radnet_inflate_unit
+INFLATE_LINK = np.dtype([("out_offset", np.int64), ("start_bit", np.uint32), ("out_bytes", np.uint32), ("prev_byte", np.uint32), ("reserved", np.uint32)])
+INFLATE_STATUS = ("ok", "bad header", "bad code", "not run-length", "stored length mismatch", "ran past the stream", "unit too long")
+INFLATE_CHAIN = ("ok", "an end bit that is no measured start", "a unit that did not decode", "a match with nothing in front of it",
+                 "the inflated length differs", "the final block does not end 4 bytes before the stream's end")
+# container, geometry and the compressed IDAT stream of a file: staged is a pinned uint8 tensor that holds the n bytes of the zlib
+# stream and, behind them, the 768 bytes of the palette; expected is the length of the inflated stream the geometry asks for
+Compressed = collections.namedtuple("Compressed", "header palette passes bpp expected staged n")
+
+
+def parse_compressed(data):
+    """The container walk of parse() WITHOUT the inflate: Compressed(header, palette, passes, bpp, expected, staged, n).  The IDAT
+    payloads are joined directly into the pinned staging buffer (the palette rides behind them, as in decode_device); the chunk
+    CRCs are summed on up to 8 host threads (fixed, like MANY_DEFAULT_WORKERS: one thread's zlib.crc32 over a 35 MB map would be
+    the new floor).  Checks what parse() checks of the container, and the zlib header: CM 8, a window of at most 32 KiB, FCHECK, no
+    preset dictionary.  Raises ValueError naming the cause; decode_device(inflate="device") then lets the host path speak."""
+    import concurrent.futures
+    import torch
+    view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, np.uint8)).cast("B")
+    header = _header(bytes(view[:33]))
+    pos, idat, plte, ended, jobs = 33, [], None, False, []
+    while pos < len(view):
+        if pos + 12 > len(view):
+            raise ValueError("PNG: truncated file (chunk header at byte %d)" % pos)
+        length, kind = struct.unpack(">I4s", view[pos:pos + 8])
+        end = pos + 8 + length
+        if length > 0x7fffffff or end + 4 > len(view):
+            raise ValueError("PNG: truncated file (%r chunk of %d bytes at byte %d)" % (kind, length, pos))
+        jobs.append((kind, pos, end))
+        if kind == b"IHDR":
+            raise ValueError("PNG: a second IHDR chunk")
+        if kind == b"PLTE":
+            if length % 3 or not 3 <= length <= 768:
+                raise ValueError("PNG: PLTE chunk of %d bytes" % length)
+            plte = bytes(view[pos + 8:end])
+        elif kind == b"IDAT":
+            idat.append((pos + 8, end))
+        pos = end + 4
+        if kind == b"IEND":
+            ended = True
+            break
+    if not ended:
+        raise ValueError("PNG: truncated file (no IEND chunk)")
+    if header.color_type == 3 and plte is None:
+        raise ValueError("PNG: palette (PLTE) missing for colour type 3")
+
+    def crc_ok(job, workers=1):
+        kind, at, end = job                        # the CRC covers the type and the payload, which stand side by side: one call per chunk
+        if workers == 1:
+            return zlib.crc32(view[at + 4:end]) == int.from_bytes(view[end:end + 4], "big")
+        return _crc32_threads(view[at + 8:end], zlib.crc32(kind), workers=workers) == int.from_bytes(view[end:end + 4], "big")
+    n = sum(e - s for s, e in idat)
+    staged = torch.empty(n + 768, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    host = staged.numpy()
+    source = np.frombuffer(view, np.uint8)
+    starts = np.concatenate([[0], np.cumsum([e - s for s, e in idat])]).astype(np.int64).tolist()
+
+    def join(k):
+        s, e = idat[k]
+        host[starts[k]:starts[k] + e - s] = source[s:e]
+    if sum(e - at for _, at, e in jobs) < 1 << 20:
+        oks = {j: crc_ok(j) for j in jobs}
+        for k in range(len(idat)):
+            join(k)
+    else:
+        # a chunk of 4 MiB or more is cut into ranges summed on host threads (one large IDAT: this package's writer); the others
+        # (8 KiB IDAT chunks by the thousand) go to radnet_png_check_crcs in one call, which spreads them over threads of its own
+        from radnet_hip import lib as L
+        large = [j for j in jobs if j[2] - j[1] >= 4 << 20]
+        small = [j for j in jobs if j[2] - j[1] < 4 << 20]
+        oks = {j: crc_ok(j, MANY_DEFAULT_WORKERS) for j in large}
+        if small:
+            at, end = np.array([j[1] for j in small], np.int64), np.array([j[2] for j in small], np.int64)
+            bad = L.load_library().radnet_png_check_crcs(source.ctypes.data, len(source), at.ctypes.data, end.ctypes.data, len(small), MANY_DEFAULT_WORKERS)
+            if bad < 0:
+                raise RuntimeError("PNG: radnet_png_check_crcs failed (%d)" % bad)
+            oks.update((j, k < bad) for k, j in enumerate(small))      # chunks behind the first bad one are not looked at: it is reported
+        with concurrent.futures.ThreadPoolExecutor(max_workers=MANY_DEFAULT_WORKERS) as pool:
+            list(pool.map(lambda g: [join(k) for k in range(g, len(idat), MANY_DEFAULT_WORKERS)], range(min(len(idat), MANY_DEFAULT_WORKERS))))
+    for kind, at, end in jobs:
+        if not oks[(kind, at, end)]:
+            raise ValueError("PNG: CRC mismatch in the %r chunk at byte %d" % (kind, at))
+    palette = np.zeros((256, 3), np.uint8)
+    if plte is not None:
+        rgb = np.frombuffer(plte, np.uint8).reshape(-1, 3)
+        palette[:rgb.shape[0]] = rgb[:, ::-1]
+    host[n:] = palette.reshape(-1)
+    if n < 2 or host[0] & 15 != 8 or host[0] >> 4 > 7 or (int(host[0]) * 256 + int(host[1])) % 31 or host[1] & 32:
+        raise ValueError("PNG: the IDAT stream has no zlib header the device inflate takes (deflate, a window of at most 32 KiB, FCHECK, no dictionary)")
+    passes, expected = pass_geometry(header)
+    return Compressed(header, palette, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8), expected, staged, n)
+
+
+def _lap(report, name):
+    """With report["stages"] a dict (tools/png_inflate_timing.py): the device is drained and the wall time since the last lap is
+    booked under `name`, in milliseconds.  Without it nothing happens and nothing waits."""
+    stages = report.get("stages")
+    if stages is not None:
+        import time
+        import torch
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        stages[name] = stages.get(name, 0.0) + (now - stages.get("_t", now)) * 1e3
+        stages["_t"] = now
+
+
+def _launch(report, ctx, name, *args):
+    """ctx.call(name, *args); with report["stages"] the launch is bracketed by two events and booked under `name`."""
+    stages = report.get("stages")
+    if stages is None:
+        return ctx.call(name, *args)
+    import torch
+    _lap(report, "host_between_ms")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    ctx.call(name, *args)
+    e1.record()
+    e1.synchronize()
+    stages[name + "_ms"] = stages.get(name + "_ms", 0.0) + e0.elapsed_time(e1)
+    _lap(report, "_skip")
+
+
+def _inflate_device(comp, dev, ctx, report):
+    """The inflated scanline stream of `comp` as a cuda tensor of comp.expected bytes (dev: the uploaded staging buffer), or None with
+    report["reason"] saying what the device could not take.  Three syncs: the candidates, the unit records, the Adler parts with the
+    filter-type column; the column comes back as report["column"]."""
+    import ctypes
+    import torch
+    from radnet_hip import lib as L
+    lib, n, expected = L.load_library(), comp.n, comp.expected
+    refuse = lambda why: report.update(reason=why) or None      # noqa: E731
+    if n < 7:
+        return refuse("a zlib stream of %d bytes" % n)
+    if n >= 1 << 29:
+        return refuse("a zlib stream of %d bytes (bit offsets leave 32 bits)" % n)
+    z, first_bit = dev.data_ptr(), 16
+    cap = n // 32 + 1024
+    found = torch.zeros(cap + 1, dtype=torch.int32, device="cuda")      # the count, then the candidates
+    _launch(report, ctx, "radnet_inflate_find_blocks", z, n, first_bit, found.data_ptr() + 4, cap, found)
+    found_host = found.cpu().numpy().view(np.uint32)
+    _lap(report, "download_candidates_ms")
+    count = int(found_host[0])
+    report["candidates"] = count
+    if count > cap:
+        return refuse("%d block candidates, more than the %d the search keeps" % (count, cap))
+    starts = np.union1d(found_host[1:1 + count], np.array([first_bit], np.uint32))
+    units = np.zeros(len(starts), INFLATE_UNIT)
+    units["start_bit"] = starts
+    units_dev = torch.from_numpy(units.view(np.uint8)).cuda()
+    _lap(report, "sort_upload_units_ms")
+    _launch(report, ctx, "radnet_inflate_rle_measure", z, n, units_dev, len(units))
+    units = units_dev.cpu().numpy().view(INFLATE_UNIT)
+    _lap(report, "download_units_ms")
+    links = np.zeros(len(units), INFLATE_LINK)
+    n_links, n_false, bad = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(-1)
+    rc = lib.radnet_inflate_chain(units.ctypes.data, len(units), first_bit, n, expected, links.ctypes.data, len(links), ctypes.byref(n_links),
+                                  ctypes.byref(n_false), ctypes.byref(bad))
+    if rc != 0:
+        if rc < 0:
+            raise RuntimeError("PNG: radnet_inflate_chain failed (%d)" % rc)
+        why = "chain: " + INFLATE_CHAIN[rc]
+        if rc == 2:
+            why += " (%s)" % INFLATE_STATUS[int(units["status"][bad.value])]
+        return refuse(why)
+    links = links[:n_links.value]
+    by_start = dict(zip(units["start_bit"].tolist(), units["blocks"].tolist()))
+    report.update(false_candidates=n_false.value, units=len(links), blocks=sum(by_start[s] for s in links["start_bit"].tolist()))
+    links_dev = torch.from_numpy(links.view(np.uint8)).cuda()
+    stream = torch.empty(max(expected, 1), dtype=torch.uint8, device="cuda")
+    _lap(report, "chain_upload_links_ms")
+    _launch(report, ctx, "radnet_inflate_rle_emit", z, n, links_dev, len(links), stream, expected)
+    chunks = -(-expected // _deflate_constant("RADNET_DEFLATE_CHUNK"))
+    rows = sum(p.pass_h for p in comp.passes)
+    tail = torch.zeros(DEFLATE_SYMBOLS * 4 + chunks * 16 + rows, dtype=torch.uint8, device="cuda")      # counts (not used), Adler parts, column
+    _launch(report, ctx, "radnet_deflate_rle_scan_u8", stream, expected, tail, tail.data_ptr() + DEFLATE_SYMBOLS * 4)
+    offsets = np.array([p.stream_offset for p in comp.passes], np.int64)
+    pass_rows = np.array([p.pass_h for p in comp.passes], np.int32)
+    rowbytes = np.array([p.rowbytes for p in comp.passes], np.int32)
+    _launch(report, ctx, "radnet_png_gather_column_u8", stream, expected, offsets.ctypes.data, pass_rows.ctypes.data, rowbytes.ctypes.data, len(comp.passes),
+             tail.data_ptr() + DEFLATE_SYMBOLS * 4 + chunks * 16)
+    tail_host = tail.cpu().numpy()
+    _lap(report, "download_adler_column_ms")
+    parts = tail_host[DEFLATE_SYMBOLS * 4:DEFLATE_SYMBOLS * 4 + chunks * 16].view(np.uint64)
+    trailer = struct.unpack(">I", comp.staged.numpy()[n - 4:n].tobytes())[0]
+    if adler32_of_parts(parts, expected) != trailer:
+        return refuse("adler")
+    report["column"] = tail_host[DEFLATE_SYMBOLS * 4 + chunks * 16:]
+    return stream
+
+
+def _decode_inflated_on_device(data, ctx, report):
+    """decode_device's device inflate: the image, or None when the host path has to take the file (report["reason"])."""
+    import ctypes
+    import torch
+    from radnet_hip import lib as L
+    from . import augmentation_device as AD
+    _lap(report, "_skip")
+    try:
+        comp = parse_compressed(data)
+    except ValueError as e:
+        report["reason"] = "container: %s" % e
+        return None
+    _lap(report, "container_crc_ms")
+    with AD.feed_stream(ctx) as (ctx, side):
+        dev = comp.staged.cuda(non_blocking=True)
+        _lap(report, "upload_ms")
+        stream = _inflate_device(comp, dev, ctx, report)
+        if stream is None:
+            return None
+        column = report.pop("column")
+        if int(column.max()) > 4:
+            report["reason"] = "a filter type above 4"
+            return None
+        h = comp.header
+        out = torch.empty((h.height, h.width, 3), dtype=torch.uint8, device="cuda")
+        base, palette = stream.data_ptr(), dev.data_ptr() + comp.n
+        # segments when they spread a pass over the device: the longest is at most half its pass
+        lib, tables, row0, spread = L.load_library(), [], 0, True
+        target = L.header_constant("RADNET_PNG_SEGMENT_TARGET_ROWS")
+        for p in comp.passes:
+            cap = min(p.pass_h, 2 * (p.pass_h // target) + 2)
+            table = np.zeros(cap, SEGMENT)
+            col = np.ascontiguousarray(column[row0:row0 + p.pass_h])
+            got = lib.radnet_png_plan_segments_column(col.ctypes.data, p.stream_offset, p.pass_h, p.rowbytes, 0, table.ctypes.data_as(ctypes.c_void_p), cap)
+            if got < 0:
+                raise ValueError("PNG: radnet_png_plan_segments_column failed (%d) on the pass at (%d, %d)" % (got, p.x0, p.y0))
+            tables.append(table[:got])
+            spread = spread and 2 * int(table[:got]["rows"].max()) <= p.pass_h
+            row0 += p.pass_h
+        if spread:
+            table = np.concatenate(tables)
+            table = table[np.argsort(table["rows"] > 64, kind="stable")]
+            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
+            _lap(report, "plan_segments_ms")
+            _launch(report, ctx, "radnet_png_unfilter_segments_u8", base, comp.expected, table.ctypes.data, table_dev, len(table), comp.bpp)
+            report["reconstruction"] = "segments"
+        else:
+            _lap(report, "plan_segments_ms")
+            for p in comp.passes:
+                _launch(report, ctx, "radnet_png_unfilter_u8", base + p.stream_offset, p.pass_h, p.rowbytes, comp.bpp)
+            report["reconstruction"] = "unfilter"
+        for p in comp.passes:
+            _launch(report, ctx, "radnet_png_expand_bgr_u8", base + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, h.color_type, h.bit_depth, palette, out,
+                     h.height, h.width, p.y0, p.x0, p.dy, p.dx)
+    report["path"] = "device"
+    return AD.hand_over(out, side)
+
+
+def decode_device(data, ctx=None, inflate="host", report=None):
     """The decoded image as a uint8 [H][W][3] (B, G, R) cuda tensor: parse, ONE pinned upload of the inflated stream (the palette
     rides behind it), then reconstruction and expansion per pass.  ctx: a radnet context whose stream is torch's current one;
-    None = the calling thread's default context, on a BackgroundFeed worker thread on that thread's own stream."""
+    None = the calling thread's default context, on a BackgroundFeed worker thread on that thread's own stream.
+    inflate="device" (opt-in; "host" is the path above, byte for byte): the COMPRESSED IDAT stream goes up instead
+    (parse_compressed) and is inflated there (csrc/inflate.hip): radnet_inflate_find_blocks tries a dynamic block header at every
+    bit offset, radnet_inflate_rle_measure decodes the unit behind every candidate, radnet_inflate_chain (host) follows them from the
+    first block to the last, radnet_inflate_rle_emit writes the bytes; the Adler-32 and the filter-type column come from the device
+    too.  That takes run-length streams only (zlib level 1 with Z_RLE: cv2.imwrite's defaults, assemble, deflate="device").  Whatever
+    the device cannot take -- matches at other distances, a unit above RADNET_INFLATE_UNIT_MAX_SYMBOLS, a corrupt stream, a broken
+    container -- goes to the host path, with that path's image or exception.  A dict passed as `report` receives path ("device" or
+    "host"), reason (None on the device path), candidates, false_candidates, units, blocks and reconstruction ("segments" through
+    radnet_png_unfilter_segments_u8 when the longest segment is at most half its pass, else "unfilter"; None on the host path)."""
     import torch
     from . import augmentation_device as AD
+    if inflate not in ("host", "device"):
+        raise ValueError("PNG: inflate=%r (\"host\" or \"device\")" % (inflate,))
+    report = {} if report is None else report
+    report.update(path="host", reason=None, candidates=0, false_candidates=0, units=0, blocks=0, reconstruction=None)
+    if inflate == "device":
+        out = _decode_inflated_on_device(data, ctx, report)
+        if out is not None:
+            return out
+        report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None)
+        report.pop("column", None)
     img = parse(data)
     n = len(img.stream)
     with AD.feed_stream(ctx) as (ctx, side):

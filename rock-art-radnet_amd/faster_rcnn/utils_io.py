@@ -19,10 +19,11 @@ def image_path(img_path, img_type):
     return os.path.join(*parts)
 
 
-def get_image(img_path, types, random_type=False, rng=np.random, to_host=True):
+def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, inflate="host"):
     """utils.get_image, draw for draw: types[0], or with random_type one rng.choice(types, 1, p=probs)[0] where the first type has
     probability 0.5 (up to three types) or 0.3 and the others share the rest.  Returns the uint8 BGR HWC image as a NumPy array,
-    or with to_host=False as a cuda tensor (nothing is downloaded)."""
+    or with to_host=False as a cuda tensor (nothing is downloaded).  inflate="device" inflates the file's IDAT stream on the device
+    (png.decode_device: run-length streams; anything else takes the host path as before)."""
     img_type = types[0]
     if random_type:
         first_prob = 0.3
@@ -31,7 +32,10 @@ def get_image(img_path, types, random_type=False, rng=np.random, to_host=True):
         probs = [first_prob] + [(1.0 - first_prob) / (len(types) - 1) for i in range(len(types) - 1)]
         img_type = rng.choice(types, 1, p=probs)[0]
     buf = np.fromfile(image_path(img_path, img_type), np.uint8)
-    return png.imdecode_color(buf) if to_host else png.decode_device(buf)
+    if inflate == "host":
+        return png.imdecode_color(buf) if to_host else png.decode_device(buf)
+    img = png.decode_device(buf, inflate=inflate)
+    return img.cpu().numpy() if to_host else img
 
 
 def image_size(path):
