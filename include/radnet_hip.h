@@ -770,6 +770,63 @@ int radnet_inflate_chain(const radnet_inflate_unit* units, int32_t count, int64_
  * out_len < 0 is RADNET_ERR_ARG. */
 int radnet_inflate_rle_emit(radnet_ctx* ctx, const uint8_t* z, int64_t n, const radnet_inflate_link* links, int32_t count, uint8_t* out,
                             int64_t out_len);
+/* ---- inflate of ANY stream on the device (csrc/inflate_lz.hip, csrc/inflate_plan.cpp): far matches by pointer jumping ---------------
+ * The section above with the distance taken whole.  radnet_inflate_find_blocks recognises a dynamic header whatever the distances
+ * are, and a unit's length in bits and in bytes does not depend on the bytes in front of it, so units are measured and chained in
+ * the same way.  What a match copies need not stand in its own unit: emit therefore writes, beside the literals, for EVERY output
+ * byte the position it is a copy of (src[i] = i for a literal, an earlier position for a byte of a match).  The stream is then a
+ * forest of pointers whose roots are the literals; resolve halves every path per round, gather reads each byte from its root.  No
+ * 32 KiB window travels from unit to unit, no workgroup waits on another, no loop spins, and the final bytes and the final src do
+ * not depend on the order in which anything ran.  The token decoder, the LDS window and THE READING RULE are those above (one
+ * kernel body, csrc/inflate_units_body.h); distance symbols 0..29 take their extra bits (RFC 1951 3.2.5) with the PAST_END check
+ * behind them as behind every group of bits. */
+typedef struct radnet_inflate_lz_unit {
+  uint32_t start_bit;   /* given by the caller */
+  uint32_t end_bit;     /* as in radnet_inflate_unit */
+  uint32_t out_bytes, symbols, blocks;
+  uint32_t status;      /* RADNET_INFLATE_* (never NOT_RLE); when it is not OK every field but start_bit and status is zero */
+  uint32_t flags;       /* RADNET_INFLATE_FLAG_FINAL only */
+  uint32_t reach;       /* max over the unit's matches of distance - bytes the unit produced before that match, floored at 0: how
+                           far the unit reads in front of itself, 0..32768 */
+  uint32_t far_matches; /* the matches whose distance is not 1 */
+  uint32_t reserved;    /* 0 */
+} radnet_inflate_lz_unit; /* 40 bytes */
+/* radnet_inflate_rle_measure for any stream: the same unit rule (stored and fixed blocks ride along), symbol cap, statuses and
+ * refusals; RADNET_INFLATE_NOT_RLE is never returned. */
+int radnet_inflate_lz_measure(radnet_ctx* ctx, const uint8_t* z, int64_t n, radnet_inflate_lz_unit* units, int32_t count);
+/* a unit whose reach exceeds its out_offset: a match that points in front of the stream (zlib: "invalid distance too far back") */
+#define RADNET_INFLATE_CHAIN_REACH 6
+/* Host only (csrc/inflate_plan.cpp; no context, no device): radnet_inflate_chain's walk, arguments, results and refusals for
+ * radnet_inflate_lz_unit records, without LEAD_MATCH and without the byte in front (every link's prev_byte is 0).  Per unit, in
+ * order: NO_START, BAD_UNIT, REACH, then link_cap (RADNET_ERR_ARG); LENGTH and TRAILER at the end.  THE REACH CHECK IS THE GUARD
+ * THAT KEEPS EVERY LATER INDEX NON-NEGATIVE: a unit chained at out_offset copies from out_offset - reach at the lowest, so with
+ * reach <= out_offset every source radnet_inflate_lz_emit writes lies in [0, position). */
+int radnet_inflate_lz_chain(const radnet_inflate_lz_unit* units, int32_t count, int64_t first_bit, int64_t n, int64_t expected,
+                            radnet_inflate_link* links, int32_t link_cap, int32_t* link_count, int32_t* false_count, int32_t* bad_unit);
+/* Decodes every chained unit again, one wave per unit, batches of tokens through LDS as radnet_inflate_rle_emit does.  buf:
+ * uint8[out_len], src: uint32[out_len] (device).  A literal or a stored byte at absolute position i: buf[i] = the byte, src[i] = i.
+ * A match of length L and distance D that begins at p: src[p + j] = p - D + (j % D) for j < L, and buf is NOT written there; the
+ * % D lets an overlapping match (a run) point in front of itself directly, so the depth of a chain is the number of matches on
+ * it, not of bytes.  A source that would be negative (no chain gives one, see REACH) is written as the position itself.  Nothing
+ * outside the unit's [out_offset, out_offset + out_bytes) and [0, out_len) is written, in either array.  Arguments refused as
+ * radnet_inflate_rle_emit refuses them (src null too); out_len >= 2^31 is RADNET_ERR_UNSUPPORTED; nothing is launched then. */
+int radnet_inflate_lz_emit(radnet_ctx* ctx, const uint8_t* z, int64_t n, const radnet_inflate_link* links, int32_t count, uint8_t* buf, uint32_t* src,
+                           int64_t out_len);
+/* Enqueues `rounds` launches (1..RADNET_INFLATE_LZ_MAX_ROUNDS), one thread per position, IN PLACE:
+ *   s = src[i]; if (s < i) { t = src[s]; if (t < s) { src[i] = t; count } }
+ * changed: device uint32[rounds], zeroed by the caller; launch r adds the entries it rewrote to changed[r] (an integer atomic, once
+ * per workgroup that rewrote any).  An entry with src[i] >= i is a root by definition, so the kernel reads nothing outside
+ * src[0 .. out_len) and terminates on ANY content of src.  In place is correct: whatever another thread has stored in src[s]
+ * meanwhile is an ancestor of s.  The roots are unique, so the flat src does not depend on timing; the counts may.  At most
+ * ceil(log2(max(out_len, 2))) rounds flatten any table radnet_inflate_lz_emit writes: a path of k links has at most ceil(k / 2)
+ * after a round, and no path is longer than out_len - 1.  A round that rewrote nothing leaves src flat.  A null pointer,
+ * out_len < 0 or rounds outside 1..RADNET_INFLATE_LZ_MAX_ROUNDS is RADNET_ERR_ARG, out_len >= 2^31 RADNET_ERR_UNSUPPORTED;
+ * nothing is launched then, nor for out_len = 0. */
+#define RADNET_INFLATE_LZ_MAX_ROUNDS 32
+int radnet_inflate_lz_resolve(radnet_ctx* ctx, uint32_t* src, int64_t out_len, int32_t rounds, uint32_t* changed);
+/* s = src[i]; if (s < i) buf[i] = buf[s], one thread per position, IN PLACE: race-free once src is flat, because a root is never
+ * written; memory-safe on any content of src.  Refusals as radnet_inflate_lz_resolve's. */
+int radnet_inflate_lz_gather(radnet_ctx* ctx, const uint32_t* src, uint8_t* buf, int64_t out_len);
 /* The filter-type column of an inflated stream on the device: column[k] = stream[offset[p] + r * (1 + rowbytes[p])] for the rows r
  * of the passes p = 0 .. passes - 1 in order (k counts them through), one launch; offsets, rows and rowbytes are HOST arrays of
  * `passes` (1..7) entries that travel with the launch.  The pass must lie inside stream_len.  png.py downloads the column, refuses

@@ -34,7 +34,8 @@ uint32_t crc32_of(const uint8_t* p, int64_t n) {
 }
 
 // index of the unit that starts at `bit`, or -1: the starts are strictly increasing
-int32_t find_start(const radnet_inflate_unit* units, int32_t count, int64_t bit) {
+template <class Unit>
+int32_t find_start(const Unit* units, int32_t count, int64_t bit) {
   int32_t lo = 0, hi = count;
   while (lo < hi) {
     const int32_t mid = lo + (hi - lo) / 2;
@@ -73,6 +74,45 @@ extern "C" int radnet_inflate_chain(const radnet_inflate_unit* units, int32_t co
     *link_count = written;
     total += unit.out_bytes;
     if (unit.flags & RADNET_INFLATE_FLAG_LAST_KNOWN) prev = unit.last_byte, have_prev = true;      // else its bytes, if any, repeat prev
+    if (unit.flags & RADNET_INFLATE_FLAG_FINAL) {
+      if (total != expected) return RADNET_INFLATE_CHAIN_LENGTH;
+      if (((int64_t)unit.end_bit + 7) / 8 + 4 != n) return RADNET_INFLATE_CHAIN_TRAILER;
+      break;
+    }
+    if ((int64_t)unit.end_bit <= bit) return RADNET_INFLATE_CHAIN_BAD_UNIT;      // a record no measurement gives: the walk must advance
+    from = u;
+    bit = unit.end_bit;
+  }
+  *bad_unit = -1;
+  *false_count = count - written;
+  return RADNET_INFLATE_CHAIN_OK;
+}
+
+extern "C" int radnet_inflate_lz_chain(const radnet_inflate_lz_unit* units, int32_t count, int64_t first_bit, int64_t n, int64_t expected,
+                                       radnet_inflate_link* links, int32_t link_cap, int32_t* link_count, int32_t* false_count, int32_t* bad_unit) {
+  if (!units || !links || !link_count || !false_count || !bad_unit || count < 1 || n < 1 || first_bit < 0 || expected < 0 || link_cap < 0)
+    return RADNET_ERR_ARG;
+  for (int32_t u = 1; u < count; ++u)
+    if (units[u].start_bit <= units[u - 1].start_bit) return RADNET_ERR_ARG;
+  *link_count = 0;
+  *false_count = 0;
+  *bad_unit = -1;
+  int64_t bit = first_bit, total = 0;
+  int32_t from = -1, written = 0;
+  for (;;) {
+    const int32_t u = find_start(units, count, bit);
+    if (u < 0) {
+      *bad_unit = from;
+      return RADNET_INFLATE_CHAIN_NO_START;
+    }
+    const radnet_inflate_lz_unit& unit = units[u];
+    *bad_unit = u;
+    if (unit.status != RADNET_INFLATE_OK) return RADNET_INFLATE_CHAIN_BAD_UNIT;
+    if ((int64_t)unit.reach > total) return RADNET_INFLATE_CHAIN_REACH;      // the guard: every source emit writes is >= total - reach >= 0
+    if (written >= link_cap) return RADNET_ERR_ARG;
+    links[written++] = radnet_inflate_link{total, unit.start_bit, unit.out_bytes, 0u, 0u};
+    *link_count = written;
+    total += unit.out_bytes;
     if (unit.flags & RADNET_INFLATE_FLAG_FINAL) {
       if (total != expected) return RADNET_INFLATE_CHAIN_LENGTH;
       if (((int64_t)unit.end_bit + 7) / 8 + 4 != n) return RADNET_INFLATE_CHAIN_TRAILER;

@@ -93,7 +93,7 @@ class RADNet():
 
     device_resident = True      # engine-backed models: keep tiles on the device between the stages (see _detect)
     device_tail = True          # ... and decode + per-class NMS + source-pixel coordinates too (see _tail_on_device)
-    png_inflate = "host"        # predict_from_path: "device" inflates the maps' IDAT streams on the device (png.decode_device(inflate=))
+    png_inflate = "host"        # predict_from_path: "device" / "device-lz" inflate the maps' IDAT streams on the device (png.decode_device(inflate=))
     scan_tail = False           # ... and the merge of a scan's tiles: final_nms per image, NMS across images (see _scan_tail_on)
 
     def __init__(self, C, model_rpn, model_detector, preprocess_func):
@@ -589,7 +589,8 @@ class RADNet():
         """RADNet.py:482-500: one image per type of C.img_types when C.use_img_type, else the first type's, each read by
         utils_io.get_image (faster_rcnn/png.py decodes; no OpenCV), then predict.  With the engine-backed models and
         `device_resident` the decoded images stay on the device (get_image(..., to_host=False)); otherwise they are host arrays.
-        `png_inflate = "device"` is handed to get_image as inflate=: the same images, inflated on the device where the file allows."""
+        `png_inflate = "device"` or `"device-lz"` is handed to get_image as inflate=: the same images, inflated on the device where
+        the file allows (run-length streams, or any deflate stream)."""
         from . import utils_io
         C = self.C
         to_host = not self._takes_device_images()

@@ -16,6 +16,8 @@ reconstructs all passes of all files, one workgroup per segment; the bytes are d
 decode_device(inflate="device") uploads the COMPRESSED stream instead (parse_compressed) and inflates it on the device
 (csrc/inflate.hip: a speculative search for dynamic block headers at every bit offset, the units measured, chained on the host and
 emitted), for run-length streams; whatever the device cannot take goes to the host path above.  The default is that path, byte for byte.
+decode_device(inflate="device-lz") does so for any deflate stream (csrc/inflate_lz.hip): emit writes the literals and every byte's
+source position, pointer jumping flattens the sources, a gather copies each byte from its root.
 
 Formats: colour types 0, 2, 3, 4, 6 with the bit depths 1, 2, 4, 8, 16 the PNG specification allows for each; non-interlaced and
 Adam7.  Output rules: grey is replicated to three channels, depths 1 / 2 / 4 scaled by 255 / 85 / 17; palette entries are looked up
@@ -173,6 +175,9 @@ INFLATE_LINK = np.dtype([("out_offset", np.int64), ("start_bit", np.uint32), ("o
 INFLATE_STATUS = ("ok", "bad header", "bad code", "not run-length", "stored length mismatch", "ran past the stream", "unit too long")
 INFLATE_CHAIN = ("ok", "an end bit that is no measured start", "a unit that did not decode", "a match with nothing in front of it",
                  "the inflated length differs", "the final block does not end 4 bytes before the stream's end")
+INFLATE_LZ_UNIT = np.dtype([(k, np.uint32) for k in ("start_bit", "end_bit", "out_bytes", "symbols", "blocks", "status", "flags", "reach", "far_matches",
+                                                     "reserved")])      # radnet_inflate_lz_unit
+INFLATE_LZ_CHAIN = INFLATE_CHAIN + ("a match that reaches in front of the stream",)      # RADNET_INFLATE_CHAIN_REACH; LEAD_MATCH is never met
 # container, geometry and the compressed IDAT stream of a file: staged is a pinned uint8 tensor that holds the n bytes of the zlib
 # stream and, behind them, the 768 bytes of the palette; expected is the length of the inflated stream the geometry asks for
 Compressed = collections.namedtuple("Compressed", "header palette passes bpp expected staged n")
@@ -290,14 +295,11 @@ def _launch(report, ctx, name, *args):
     _lap(report, "_skip")
 
 
-def _inflate_device(comp, dev, ctx, report):
-    """The inflated scanline stream of `comp` as a cuda tensor of comp.expected bytes (dev: the uploaded staging buffer), or None with
-    report["reason"] saying what the device could not take.  Three syncs: the candidates, the unit records, the Adler parts with the
-    filter-type column; the column comes back as report["column"]."""
-    import ctypes
+def _measured_units(comp, dev, ctx, report, dtype, measure):
+    """The records (structured array of `dtype`) of the units behind every block candidate of `comp` and behind the stream's first
+    bit, as the entry `measure` fills them, or None with report["reason"].  Two syncs: the candidates, the records."""
     import torch
-    from radnet_hip import lib as L
-    lib, n, expected = L.load_library(), comp.n, comp.expected
+    n = comp.n
     refuse = lambda why: report.update(reason=why) or None      # noqa: E731
     if n < 7:
         return refuse("a zlib stream of %d bytes" % n)
@@ -314,31 +316,101 @@ def _inflate_device(comp, dev, ctx, report):
     if count > cap:
         return refuse("%d block candidates, more than the %d the search keeps" % (count, cap))
     starts = np.union1d(found_host[1:1 + count], np.array([first_bit], np.uint32))
-    units = np.zeros(len(starts), INFLATE_UNIT)
+    units = np.zeros(len(starts), dtype)
     units["start_bit"] = starts
     units_dev = torch.from_numpy(units.view(np.uint8)).cuda()
     _lap(report, "sort_upload_units_ms")
-    _launch(report, ctx, "radnet_inflate_rle_measure", z, n, units_dev, len(units))
-    units = units_dev.cpu().numpy().view(INFLATE_UNIT)
+    _launch(report, ctx, measure, z, n, units_dev, len(units))
+    units = units_dev.cpu().numpy().view(dtype)
     _lap(report, "download_units_ms")
+    return units
+
+
+def _chained_links(comp, report, units, chain, names):
+    """The links (INFLATE_LINK) of the units the host entry `chain` walks from the stream's first bit to its final block, or None
+    with report["reason"]; names: what its refusal codes are called."""
+    import ctypes
+    from radnet_hip import lib as L
     links = np.zeros(len(units), INFLATE_LINK)
     n_links, n_false, bad = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(-1)
-    rc = lib.radnet_inflate_chain(units.ctypes.data, len(units), first_bit, n, expected, links.ctypes.data, len(links), ctypes.byref(n_links),
-                                  ctypes.byref(n_false), ctypes.byref(bad))
+    rc = getattr(L.load_library(), chain)(units.ctypes.data, len(units), 16, comp.n, comp.expected, links.ctypes.data, len(links), ctypes.byref(n_links),
+                                          ctypes.byref(n_false), ctypes.byref(bad))
     if rc != 0:
         if rc < 0:
-            raise RuntimeError("PNG: radnet_inflate_chain failed (%d)" % rc)
-        why = "chain: " + INFLATE_CHAIN[rc]
+            raise RuntimeError("PNG: %s failed (%d)" % (chain, rc))
+        why = "chain: " + names[rc]
         if rc == 2:
             why += " (%s)" % INFLATE_STATUS[int(units["status"][bad.value])]
-        return refuse(why)
+        report["reason"] = why
+        return None
     links = links[:n_links.value]
     by_start = dict(zip(units["start_bit"].tolist(), units["blocks"].tolist()))
     report.update(false_candidates=n_false.value, units=len(links), blocks=sum(by_start[s] for s in links["start_bit"].tolist()))
+    return links
+
+
+def _inflate_device(comp, dev, ctx, report):
+    """The inflated scanline stream of `comp` as a cuda tensor of comp.expected bytes (dev: the uploaded staging buffer), or None with
+    report["reason"] saying what the device could not take.  Three syncs: the candidates, the unit records, the Adler parts with the
+    filter-type column; the column comes back as report["column"]."""
+    import torch
+    units = _measured_units(comp, dev, ctx, report, INFLATE_UNIT, "radnet_inflate_rle_measure")
+    links = None if units is None else _chained_links(comp, report, units, "radnet_inflate_chain", INFLATE_CHAIN)
+    if links is None:
+        return None
+    links_dev = torch.from_numpy(links.view(np.uint8)).cuda()
+    stream = torch.empty(max(comp.expected, 1), dtype=torch.uint8, device="cuda")
+    _lap(report, "chain_upload_links_ms")
+    _launch(report, ctx, "radnet_inflate_rle_emit", dev.data_ptr(), comp.n, links_dev, len(links), stream, comp.expected)
+    return _checked_stream(comp, ctx, report, stream)
+
+
+def _inflate_device_lz(comp, dev, ctx, report):
+    """_inflate_device for any stream (csrc/inflate_lz.hip): the units measured with their distances whole and chained, the literals
+    and every byte's source position emitted, the sources flattened by pointer jumping -- radnet_inflate_lz_resolve in groups of 4
+    rounds, each group's counters downloaded, up to the first round that rewrote nothing and never beyond ceil(log2(bytes)) rounds --
+    and the bytes gathered from their roots.  report["rounds"]: the rounds that rewrote an entry; report["far_units"]: the chained
+    units that hold a match of another distance than 1."""
+    import torch
+    expected = comp.expected
+    if expected >= 1 << 31:
+        report["reason"] = "an inflated stream of %d bytes (positions leave 31 bits)" % expected
+        return None
+    units = _measured_units(comp, dev, ctx, report, INFLATE_LZ_UNIT, "radnet_inflate_lz_measure")
+    links = None if units is None else _chained_links(comp, report, units, "radnet_inflate_lz_chain", INFLATE_LZ_CHAIN)
+    if links is None:
+        return None
+    far = dict(zip(units["start_bit"].tolist(), units["far_matches"].tolist()))
+    report["far_units"] = sum(far[s] > 0 for s in links["start_bit"].tolist())
     links_dev = torch.from_numpy(links.view(np.uint8)).cuda()
     stream = torch.empty(max(expected, 1), dtype=torch.uint8, device="cuda")
+    src = torch.empty(max(expected, 1), dtype=torch.int32, device="cuda")
     _lap(report, "chain_upload_links_ms")
-    _launch(report, ctx, "radnet_inflate_rle_emit", z, n, links_dev, len(links), stream, expected)
+    _launch(report, ctx, "radnet_inflate_lz_emit", dev.data_ptr(), comp.n, links_dev, len(links), stream, src, expected)
+    # ceil(log2(max(expected, 2))) rounds.  A source lies in front of its match, so a path crosses a match once; k links are k matches of
+    # 3 bytes or more, 3 k <= expected, and the ceil(log2(k)) rounds that rewrite leave one of the bound to see that nothing moves any more
+    bound, ran, rounds = max(1, (max(expected, 2) - 1).bit_length()), 0, None
+    while rounds is None:
+        if ran >= bound:
+            raise RuntimeError("PNG: the source table of %d bytes is not flat after %d rounds of radnet_inflate_lz_resolve" % (expected, bound))
+        group = min(4, bound - ran)
+        changed = torch.zeros(group, dtype=torch.int32, device="cuda")
+        _launch(report, ctx, "radnet_inflate_lz_resolve", src, expected, group, changed)
+        still = np.flatnonzero(changed.cpu().numpy() == 0)
+        _lap(report, "download_changed_ms")
+        if len(still):
+            rounds = ran + int(still[0])
+        ran += group
+    report["rounds"] = rounds
+    _launch(report, ctx, "radnet_inflate_lz_gather", src, stream, expected)
+    return _checked_stream(comp, ctx, report, stream)
+
+
+def _checked_stream(comp, ctx, report, stream):
+    """`stream` (the inflated bytes on the device) once its Adler-32, summed there, equals the zlib trailer, else None with the
+    reason "adler"; the filter-type column comes back as report["column"].  One sync."""
+    import torch
+    n, expected = comp.n, comp.expected
     chunks = -(-expected // _deflate_constant("RADNET_DEFLATE_CHUNK"))
     rows = sum(p.pass_h for p in comp.passes)
     tail = torch.zeros(DEFLATE_SYMBOLS * 4 + chunks * 16 + rows, dtype=torch.uint8, device="cuda")      # counts (not used), Adler parts, column
@@ -353,13 +425,15 @@ def _inflate_device(comp, dev, ctx, report):
     parts = tail_host[DEFLATE_SYMBOLS * 4:DEFLATE_SYMBOLS * 4 + chunks * 16].view(np.uint64)
     trailer = struct.unpack(">I", comp.staged.numpy()[n - 4:n].tobytes())[0]
     if adler32_of_parts(parts, expected) != trailer:
-        return refuse("adler")
+        report["reason"] = "adler"
+        return None
     report["column"] = tail_host[DEFLATE_SYMBOLS * 4 + chunks * 16:]
     return stream
 
 
-def _decode_inflated_on_device(data, ctx, report):
-    """decode_device's device inflate: the image, or None when the host path has to take the file (report["reason"])."""
+def _decode_inflated_on_device(data, ctx, report, lz=False):
+    """decode_device's device inflate (lz: the one for any stream): the image, or None when the host path has to take the file
+    (report["reason"])."""
     import ctypes
     import torch
     from radnet_hip import lib as L
@@ -374,7 +448,7 @@ def _decode_inflated_on_device(data, ctx, report):
     with AD.feed_stream(ctx) as (ctx, side):
         dev = comp.staged.cuda(non_blocking=True)
         _lap(report, "upload_ms")
-        stream = _inflate_device(comp, dev, ctx, report)
+        stream = (_inflate_device_lz if lz else _inflate_device)(comp, dev, ctx, report)
         if stream is None:
             return None
         column = report.pop("column")
@@ -428,18 +502,27 @@ def decode_device(data, ctx=None, inflate="host", report=None):
     the device cannot take -- matches at other distances, a unit above RADNET_INFLATE_UNIT_MAX_SYMBOLS, a corrupt stream, a broken
     container -- goes to the host path, with that path's image or exception.  A dict passed as `report` receives path ("device" or
     "host"), reason (None on the device path), candidates, false_candidates, units, blocks and reconstruction ("segments" through
-    radnet_png_unfilter_segments_u8 when the longest segment is at most half its pass, else "unfilter"; None on the host path)."""
+    radnet_png_unfilter_segments_u8 when the longest segment is at most half its pass, else "unfilter"; None on the host path).
+    inflate="device-lz" (opt-in too) takes ANY deflate stream, as other tools write them at level 6 (csrc/inflate_lz.hip): the same
+    search, radnet_inflate_lz_measure with the distances whole, radnet_inflate_lz_chain, radnet_inflate_lz_emit (the literals and
+    every byte's source position), radnet_inflate_lz_resolve (pointer jumping, up to the first round that rewrote nothing and at most
+    ceil(log2(bytes)) rounds; more is a RuntimeError) and radnet_inflate_lz_gather; then the same checks and reconstruction.  What it
+    cannot take -- a unit above the symbol cap, a corrupt stream, a match that reaches in front of the stream, a broken container --
+    goes to the host path as above.  In this mode the report also carries rounds (those that rewrote an entry) and far_units (the
+    chained units with a match of another distance than 1)."""
     import torch
     from . import augmentation_device as AD
-    if inflate not in ("host", "device"):
-        raise ValueError("PNG: inflate=%r (\"host\" or \"device\")" % (inflate,))
+    if inflate not in ("host", "device", "device-lz"):
+        raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
     report = {} if report is None else report
     report.update(path="host", reason=None, candidates=0, false_candidates=0, units=0, blocks=0, reconstruction=None)
-    if inflate == "device":
-        out = _decode_inflated_on_device(data, ctx, report)
+    lz = dict(rounds=0, far_units=0) if inflate == "device-lz" else {}
+    report.update(lz)
+    if inflate != "host":
+        out = _decode_inflated_on_device(data, ctx, report, lz=bool(lz))
         if out is not None:
             return out
-        report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None)
+        report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None, **lz)
         report.pop("column", None)
     img = parse(data)
     n = len(img.stream)

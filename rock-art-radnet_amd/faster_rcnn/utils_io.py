@@ -23,7 +23,8 @@ def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, i
     """utils.get_image, draw for draw: types[0], or with random_type one rng.choice(types, 1, p=probs)[0] where the first type has
     probability 0.5 (up to three types) or 0.3 and the others share the rest.  Returns the uint8 BGR HWC image as a NumPy array,
     or with to_host=False as a cuda tensor (nothing is downloaded).  inflate="device" inflates the file's IDAT stream on the device
-    (png.decode_device: run-length streams; anything else takes the host path as before)."""
+    (png.decode_device: run-length streams; anything else takes the host path as before), inflate="device-lz" does so for a stream
+    with matches at any distance; another value is png.decode_device's ValueError."""
     img_type = types[0]
     if random_type:
         first_prob = 0.3

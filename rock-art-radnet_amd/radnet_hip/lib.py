@@ -308,6 +308,11 @@ def load_library():
         "radnet_inflate_rle_measure": (C.c_int, [vp, vp, i64, vp, i32]),
         "radnet_inflate_chain": (C.c_int, [vp, i32, i64, i64, i64, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "radnet_inflate_rle_emit": (C.c_int, [vp, vp, i64, vp, i32, vp, i64]),
+        "radnet_inflate_lz_measure": (C.c_int, [vp, vp, i64, vp, i32]),
+        "radnet_inflate_lz_chain": (C.c_int, [vp, i32, i64, i64, i64, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "radnet_inflate_lz_emit": (C.c_int, [vp, vp, i64, vp, i32, vp, vp, i64]),
+        "radnet_inflate_lz_resolve": (C.c_int, [vp, vp, i64, i32, vp]),
+        "radnet_inflate_lz_gather": (C.c_int, [vp, vp, vp, i64]),
         "radnet_png_gather_column_u8": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, vp]),
         "radnet_png_plan_segments_column": (C.c_int, [vp, i64, i32, i32, i32, vp, i32]),
         "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
