@@ -1127,6 +1127,9 @@ int radnet_predict_tile(radnet_ctx* ctx, const radnet_tile_desc* t);
  *   records (class, x1, y1, x2, y2, prob as fp32 bits) -- classes in order of their first surviving row (the insertion order of
  *   the reference's dicts), picks of a class in pick order.  Coordinates beyond int32 saturate.
  * One launch of one workgroup; rows <= 1024, nc <= 32; no scratch memory besides `out`. */
+/* int32 words of `out` in front of the records, and of a record */
+#define RADNET_DETECT_HEADER_WORDS 8
+#define RADNET_DETECT_RECORD_WORDS 6
 typedef struct radnet_detect_tail_desc {
   const float* p_cls;      /* [rows][nc] softmax                                              */
   const float* p_regr;     /* [rows][4*(nc-1)]                                                */

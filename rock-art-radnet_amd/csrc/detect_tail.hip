@@ -8,11 +8,11 @@
 //   detect_tail_kernel   ONE workgroup of 1024 threads, the whole problem in LDS (<= 1024 rows, <= 32 classes: latency, not
 //                        bandwidth):
 //                          (1) a thread per row: first maximum, threshold / background test, delta decode in fp64, box in LDS,
-//                              a 64-bit key  (class + 1) << 42 | order-preserving score bits << 10 | row;
-//                          (2) descending bitonic sort of the keys: every class becomes one run, inside it "stable ascending,
-//                              walk from the end" (among equal scores the higher row first) -- nms_kernel's order;
+//                              a 64-bit key  (class + 1) << 42 | raw order-preserving score bits << 10 | row;
+//                          (2) descending bitonic sort of the keys (nms_device.h): every class becomes one run, inside it "stable
+//                              ascending, walk from the end" (among equal scores the higher row first) -- nms_kernel's order;
 //                          (3) a wave per class walks its run: the liveness of candidate j lives in bit j/64 of lane j%64, a pick
-//                              tests the rest of the run 64 candidates at a time with nms_kernel's suppression test;
+//                              tests the rest of the run 64 candidates at a time with nms_device.h's suppression test;
 //                          (4) classes in order of their first surviving row (the insertion order of the Python dicts), picks in
 //                              pick order, float floor division by the resize ratio, one compact record array.
 //                        No floating-point atomics, plain vector stores, no scratch memory outside LDS.
@@ -23,8 +23,8 @@ namespace {
 
 constexpr int kMaxRows = 1024;      // rows of one launch (= threads of the workgroup, bits of the row field in a key)
 constexpr int kMaxClasses = 32;
-constexpr int kHeader = 8;          // int32 words in front of the records: [0] count (-1: malformed box), [1] rows considered
-constexpr int kRecord = 6;          // int32 words per record: class, x1, y1, x2, y2, prob (fp32 bits)
+constexpr int kHeader = RADNET_DETECT_HEADER_WORDS;      // int32 words in front of the records: [0] count (-1: malformed box), [1] rows considered
+constexpr int kRecord = RADNET_DETECT_RECORD_WORDS;      // int32 words per record: class, x1, y1, x2, y2, prob (fp32 bits)
 
 __global__ void __launch_bounds__(256) rois_chunks_kernel(const long long* __restrict__ R, const int* __restrict__ n_dev, int max_n, int k,
                                                           int rows, float* __restrict__ out) {
@@ -41,14 +41,6 @@ __global__ void __launch_bounds__(256) rois_chunks_kernel(const long long* __res
   out[4 * i + 2] = (float)(x2 - x1);
   out[4 * i + 3] = (float)(y2 - y1);
 }
-
-__device__ __forceinline__ unsigned int sortable_bits(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// suppresses(): nms_device.h -- proposals.hip's test (the rounded quotient against thr; the division only where its rounding can
-// decide)
 
 // NumPy's / Python's float floor division (npy_divmod: fmod-based, NOT floor(a / b)); b != 0
 __device__ __forceinline__ double floor_divide(double a, double b) {
@@ -148,19 +140,8 @@ __global__ void __launch_bounds__(1024) detect_tail_kernel(TailArgs g) {
   }
 
   // ---- (2) descending bitonic sort of P keys --------------------------------------------------------------------------------
-  for (int kk = 2; kk <= P; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      if (tid < P) {
-        const int ixj = tid ^ j;
-        if (ixj > tid) {
-          const unsigned long long a = s_key[tid], b = s_key[ixj];
-          const bool desc = (tid & kk) == 0;
-          if (desc ? a < b : a > b) { s_key[tid] = b; s_key[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  __builtin_assume(P <= kMaxRows);                       // one trip of the sort's strided loop: the compiler then emits none
+  bitonic_sort<true>(s_key, P);
   // runs of the classes in the sorted array: the highest class index first
   if (tid == 0) {
     int at = 0;

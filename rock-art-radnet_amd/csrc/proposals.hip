@@ -3,17 +3,14 @@
 // separately, so no FMA contraction is allowed here.
 //
 //   decode   one thread per anchor (a,row,col): delta decode, round-half-even, clamp, clip, validity;
-//            emits a 64-bit sort key (order-preserving score bits << 32 | flat index), 0 for dropped boxes.
+//            emits a 64-bit sort key (score bits with signed zeros tied << 32 | flat index), 0 for dropped boxes.
 //   sort     descending device radix sort of the keys (rocPRIM, header-only) -> "stable ascending,
 //            walk from the end": among equal scores the higher flat index comes first.
+//   nms      ONE workgroup of 1024 threads runs nms_device.h's chunk scan over the sorted candidates (fp64 boxes, picks in
+//            LDS, stops at max_boxes) and writes the picks.
 //   (alternative for rpn_to_roi, RADNET_PROPOSALS_SELECT=1: select_nms_kernel -- one workgroup: radix SELECT of the best
-//    <= 4096 unexamined keys (11-bit digits, histogram in LDS), LDS bitonic sort, integer-arithmetic NMS, band by band;
-//    bit-identical, measured slower than the full sort: see radnet_rpn_to_roi)
-//   nms      ONE workgroup of 1024 threads walks the sorted candidates 64 at a time:
-//            (1) 16 waves test the 64 candidates against all picks so far (picks live in LDS),
-//            (2) each wave builds rows of the 64x64 intra-chunk suppression matrix with __ballot,
-//            (3) one lane resolves the chunk sequentially with bit operations and appends picks.
-//            Work is (#candidates examined) x (#picks), not N^2, and stops at max_boxes.
+//    <= 4096 unexamined keys (11-bit digits, histogram in LDS), nms_device.h's bitonic sort in LDS and its chunk scan on
+//    integer boxes, band by band; bit-identical, measured slower than the full sort: see radnet_rpn_to_roi)
 #include "radnet_internal.h"
 #include "nms_device.h"
 
@@ -21,22 +18,12 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned int sortable_bits(float f) {
-  unsigned int u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;      // -0.0 == +0.0 for NumPy's sort: one key, so the tie rule (higher index first) decides
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 struct DecodeArgs {
   const float* pred;
   int ld, rows, cols, a;
   double std_scaling;
   int use_regr;
   double aw[32], ah[32];
-};
-
-struct __attribute__((aligned(8))) IBox {      // integer-valued box (after np.round and the clip to the feature map), 8 bytes
-  short x1, y1, x2, y2;
 };
 
 __global__ void __launch_bounds__(256) decode_kernel(DecodeArgs g, double4* __restrict__ boxes, IBox* __restrict__ iboxes,
@@ -74,7 +61,7 @@ __global__ void __launch_bounds__(256) decode_kernel(DecodeArgs g, double4* __re
   const bool finite = isfinite(x) && isfinite(y) && isfinite(w) && isfinite(h);
   const bool ok = finite && (x1 < x2) && (y1 < y2);
   unsigned long long key = 0ull;
-  if (ok) key = ((unsigned long long)sortable_bits(p[a]) << 32) | (unsigned int)idx;
+  if (ok) key = ((unsigned long long)sortable_bits_np(p[a]) << 32) | (unsigned int)idx;
   keys[idx] = key;
   if (iboxes != nullptr) {          // integer path (use_regr): every coordinate is an integer in [0, 32767]
     IBox b;
@@ -93,14 +80,11 @@ __global__ void __launch_bounds__(256) nms_keys_kernel(const double* __restrict_
   if (idx >= n) return;
   const double x1 = boxes[4 * idx], y1 = boxes[4 * idx + 1], x2 = boxes[4 * idx + 2], y2 = boxes[4 * idx + 3];
   if (!(x1 < x2) || !(y1 < y2)) atomicAdd(malformed, 1);     // rpn.py:400-401 asserts
-  keys[idx] = ((unsigned long long)sortable_bits(probs[idx]) << 32) | (unsigned int)idx;
+  keys[idx] = ((unsigned long long)sortable_bits_np(probs[idx]) << 32) | (unsigned int)idx;
   if (idx == 0) *n_valid = n;
 }
 
-// suppresses(): nms_device.h
-
-constexpr int kMaxPicks = 1024;
-
+// The greedy scan over the sorted keys, the picks written out: chunk_scan / write_picks of nms_device.h on fp64 boxes
 __global__ void __launch_bounds__(1024) nms_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ n_valid_p,
                                                    const int* __restrict__ malformed, const double4* __restrict__ boxes, double thr,
                                                    int max_boxes, int* __restrict__ out_idx, int* __restrict__ out_count,
@@ -115,8 +99,9 @@ __global__ void __launch_bounds__(1024) nms_kernel(const unsigned long long* __r
   __shared__ unsigned int sup[2];
   __shared__ unsigned long long mat[64];
   __shared__ int s_npicks;
+  const ChunkScanLds<BoxF64> lds = {pick_box, pick_area, pick_idx, cand_box, cand_area, cand_idx, sup, mat, &s_npicks};
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int n_valid = *n_valid_p;
   if (malformed != nullptr && *malformed != 0) {
     if (tid == 0) *out_count = -1;
@@ -124,110 +109,13 @@ __global__ void __launch_bounds__(1024) nms_kernel(const unsigned long long* __r
   }
   if (tid == 0) s_npicks = 0;
   __syncthreads();
-
-  // The chunk's candidates come through two dependent global reads (sorted key -> box): the reads of chunk c+1 are
-  // issued before chunk c is processed and land while its three phases run, instead of ~1.5 us of exposed latency
-  // per chunk on a single workgroup.
-  int pre_id = 0;
-  double4 pre_box = make_double4(0.0, 0.0, 0.0, 0.0);
-  auto fetch = [&](int base) {
-    if (tid < 64 && base + tid < n_valid) {
-      pre_id = (int)(keys[base + tid] & 0xFFFFFFFFull);
-      pre_box = boxes[pre_id];
-    }
-  };
-  fetch(0);
-  for (int base = 0; base < n_valid; base += 64) {
-    const int nc = min(64, n_valid - base);
-    if (tid < 64) {
-      if (tid < nc) {
-        cand_idx[tid] = pre_id;
-        cand_box[tid] = pre_box;
-        cand_area[tid] = (pre_box.z - pre_box.x) * (pre_box.w - pre_box.y);
-      }
-      if (tid < 2) sup[tid] = 0u;
-    }
-    fetch(base + 64);
-    __syncthreads();
-    const int npicks = s_npicks;
-    // (1) candidates vs existing picks: lane = candidate, wave = slice of the pick list
-    {
-      bool dead = false;
-      if (lane < nc) {
-        const double4 c = cand_box[lane];
-        const double ca = cand_area[lane];
-        for (int p = wave; p < npicks && !dead; p += 16) dead = suppresses(pick_box[p], pick_area[p], c, ca, thr);
-      }
-      const unsigned long long m = __ballot(dead);
-      if (lane == 0 && m) {
-        atomicOr(&sup[0], (unsigned int)(m & 0xFFFFFFFFull));
-        atomicOr(&sup[1], (unsigned int)(m >> 32));
-      }
-    }
-    // (2) intra-chunk matrix: wave handles rows j = wave, wave+16, ...; lane = victim i (> j)
-    for (int j = wave; j < 64; j += 16) {
-      bool hit = false;
-      if (j < nc && lane < nc && lane > j) hit = suppresses(cand_box[j], cand_area[j], cand_box[lane], cand_area[lane], thr);
-      const unsigned long long m = __ballot(hit);
-      if (lane == 0) mat[j] = m;
-    }
-    __syncthreads();
-    // (3) sequential resolve of this chunk
-    if (tid == 0) {
-      unsigned long long alive = ~(((unsigned long long)sup[1] << 32) | sup[0]);
-      if (nc < 64) alive &= (1ull << nc) - 1ull;
-      int np = npicks;
-      while (alive != 0ull && np < max_boxes) {          // visits the survivors only, in candidate order
-        const int j = __ffsll((long long)alive) - 1;
-        pick_box[np] = cand_box[j];
-        pick_area[np] = cand_area[j];
-        pick_idx[np] = cand_idx[j];
-        ++np;
-        alive &= ~mat[j];                                 // mat[j] only has bits above j
-        alive &= ~(1ull << j);
-      }
-      s_npicks = np;
-    }
-    __syncthreads();
-    if (s_npicks >= max_boxes) break;
-  }
-  const int np = s_npicks;
-  if (tid == 0) *out_count = np;
-  for (int i = tid; i < np; i += blockDim.x) {
-    const int id = pick_idx[i];
-    if (out_idx) out_idx[i] = id;
-    if (out_boxes) {
-      const double4 b = pick_box[i];
-      out_boxes[4 * i + 0] = (long long)b.x;     // astype('int'): truncation
-      out_boxes[4 * i + 1] = (long long)b.y;
-      out_boxes[4 * i + 2] = (long long)b.z;
-      out_boxes[4 * i + 3] = (long long)b.w;
-    }
-    if (out_probs) {
-      // flat index = a*hw + pix  ->  pred[pix*ld + a]
-      const int a = id / probs_div, pix = id - a * probs_div;
-      out_probs[i] = probs_src[(size_t)pix * probs_stride + a];
-    }
-  }
+  chunk_scan<BoxF64>(keys, n_valid, boxes, thr, max_boxes, lds);
+  write_picks(lds, out_count, out_idx, out_boxes, out_probs, probs_src, probs_stride, probs_div);
 }
 
 // ---- rpn_to_roi: select + sort + NMS in one workgroup ---------------------------------------------------------------
 constexpr int kCap = 4096;          // candidates per band (LDS: 32 KB of keys)
 constexpr int kDigitBits = 11, kDigits = 1 << kDigitBits;
-
-// rpn.py:429-447 on integer boxes: inter and union are exact integers, the comparison is the reference's
-// fl(inter / (union + 1e-6)) > thr (same margin test as `suppresses`, the division only inside the margin)
-__device__ __forceinline__ bool suppresses_int(const IBox& pk, int pk_area, const IBox& c, int c_area, double thr) {
-  const int iw = min((int)pk.x2, (int)c.x2) - max((int)pk.x1, (int)c.x1);
-  const int ih = min((int)pk.y2, (int)c.y2) - max((int)pk.y1, (int)c.y1);
-  if (iw <= 0 || ih <= 0) return false;                   // inter = 0: 0 / d > thr is false for thr > 0 (checked by the launcher)
-  const int inter_i = iw * ih;
-  const double inter = (double)inter_i, d = (double)(pk_area + c_area - inter_i) + 1e-6;
-  const double t = thr * d;
-  if (inter > t * (1.0 + 0x1p-40)) return true;
-  if (inter < t * (1.0 - 0x1p-40)) return false;
-  return inter / d > thr;
-}
 
 __global__ void __launch_bounds__(1024) select_nms_kernel(const unsigned long long* __restrict__ keys, int n, const IBox* __restrict__ iboxes,
                                                           double thr, int max_boxes, int* __restrict__ out_count,
@@ -246,6 +134,7 @@ __global__ void __launch_bounds__(1024) select_nms_kernel(const unsigned long lo
   __shared__ int s_npicks, s_cnt;
   __shared__ unsigned long long s_lo, s_prefix;
   __shared__ int s_remaining, s_refine;
+  const ChunkScanLds<BoxI16> lds = {pick_box, pick_area, pick_idx, cand_box, cand_area, cand_idx, sup, mat, &s_npicks};
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s_npicks = 0;
@@ -365,102 +254,16 @@ __global__ void __launch_bounds__(1024) select_nms_kernel(const unsigned long lo
     while (P < cnt) P <<= 1;
     for (int i = cnt + tid; i < P; i += 1024) skeys[i] = 0ull;
     __syncthreads();
-    // ---------------- bitonic sort, descending
-    for (int k = 2; k <= P; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < P; i += 1024) {
-          const int ixj = i ^ j;
-          if (ixj > i) {
-            const unsigned long long a = skeys[i], b = skeys[ixj];
-            const bool desc = (i & k) == 0;
-            if (desc ? a < b : a > b) { skeys[i] = b; skeys[ixj] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    }
-    // ---------------- greedy NMS over the band, 64 candidates at a time (all data in LDS except the box gather)
-    int pre_id = 0;
-    IBox pre_box = {0, 0, 0, 0};
-    auto fetch = [&](int base) {
-      if (tid < 64 && base + tid < cnt) {
-        pre_id = (int)(skeys[base + tid] & 0xFFFFFFFFull);
-        pre_box = iboxes[pre_id];
-      }
-    };
-    fetch(0);
-    bool full = false;
-    for (int base = 0; base < cnt; base += 64) {
-      const int nc = min(64, cnt - base);
-      if (tid < 64) {
-        if (tid < nc) {
-          cand_idx[tid] = pre_id;
-          cand_box[tid] = pre_box;
-          cand_area[tid] = ((int)pre_box.x2 - (int)pre_box.x1) * ((int)pre_box.y2 - (int)pre_box.y1);
-        }
-        if (tid < 2) sup[tid] = 0u;
-      }
-      fetch(base + 64);
-      __syncthreads();
-      const int npicks = s_npicks;
-      {
-        bool dead = false;
-        if (lane < nc) {
-          const IBox c = cand_box[lane];
-          const int ca = cand_area[lane];
-          for (int p = wave; p < npicks && !dead; p += 16) dead = suppresses_int(pick_box[p], pick_area[p], c, ca, thr);
-        }
-        const unsigned long long m = __ballot(dead);
-        if (lane == 0 && m) {
-          atomicOr(&sup[0], (unsigned int)(m & 0xFFFFFFFFull));
-          atomicOr(&sup[1], (unsigned int)(m >> 32));
-        }
-      }
-      for (int j = wave; j < 64; j += 16) {
-        bool hit = false;
-        if (j < nc && lane < nc && lane > j) hit = suppresses_int(cand_box[j], cand_area[j], cand_box[lane], cand_area[lane], thr);
-        const unsigned long long m = __ballot(hit);
-        if (lane == 0) mat[j] = m;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        unsigned long long alive = ~(((unsigned long long)sup[1] << 32) | sup[0]);
-        if (nc < 64) alive &= (1ull << nc) - 1ull;
-        int np = npicks;
-        while (alive != 0ull && np < max_boxes) {
-          const int j = __ffsll((long long)alive) - 1;
-          pick_box[np] = cand_box[j];
-          pick_area[np] = cand_area[j];
-          pick_idx[np] = cand_idx[j];
-          ++np;
-          alive &= ~mat[j];
-          alive &= ~(1ull << j);
-        }
-        s_npicks = np;
-      }
-      __syncthreads();
-      if (s_npicks >= max_boxes) { full = true; break; }
-    }
+    bitonic_sort<true>(skeys, P);                              // descending
+    // ---------------- greedy NMS over the band (all data in LDS except the box gather)
+    const bool full = chunk_scan<BoxI16>(skeys, cnt, iboxes, thr, max_boxes, lds);
     if (full || lo == 0ull) break;                             // lo == 0: the band reached down to the smallest key
     upper = lo;
     first = false;
     __syncthreads();
   }
   __syncthreads();
-  const int np = s_npicks;
-  if (tid == 0) *out_count = np;
-  for (int i = tid; i < np; i += blockDim.x) {
-    const IBox b = pick_box[i];
-    out_boxes[4 * i + 0] = (long long)b.x1;
-    out_boxes[4 * i + 1] = (long long)b.y1;
-    out_boxes[4 * i + 2] = (long long)b.x2;
-    out_boxes[4 * i + 3] = (long long)b.y2;
-    if (out_probs) {
-      const int id = pick_idx[i];
-      const int a = id / probs_div, pix = id - a * probs_div;
-      out_probs[i] = probs_src[(size_t)pix * probs_stride + a];
-    }
-  }
+  write_picks(lds, out_count, (int*)nullptr, out_boxes, out_probs, probs_src, probs_stride, probs_div);
 }
 
 struct WsLayout {

@@ -3,19 +3,18 @@
 // bit what the host code gives on the same records.  Compiled with -ffp-contract=off: NumPy rounds every product and sum
 // separately.  Contract: include/radnet_hip.h.
 //
-//   final_nms_kernel     a workgroup of 1024 threads per group.  (1) keys  order-preserving prob bits << 32 | row, ascending
+//   final_nms_kernel     a workgroup of 1024 threads per group.  (1) keys  prob bits with signed zeros tied << 32 | row, ascending
 //                        bitonic sort (in LDS up to 2048 keys, in the workspace above): "stable ascending, walked from the end";
-//                        (2) per cluster ONE pass over the positions below `top`: a thread owns the positions tid, tid + 1024, ..,
-//                        marks its members with the cluster's number and proposes the highest position it leaves alive as the
-//                        next `top` (an integer atomicMax in LDS, three rotating slots, one barrier per cluster);  (3) a second
-//                        sort by (cluster, position) lays every cluster's members side by side in order position, which is
-//                        ascending prob: the chosen boxes are a SUFFIX of that run -- the last n_obj_avg, or those above the
-//                        threshold;  (4) a thread per cluster: int64 coordinate sums, NumPy's pairwise fp32 sum, the two means.
+//                        (2) the clusters by nms_device.h's walk from the top: a round per cluster marks its members with the
+//                        cluster's number;  (3) a second sort by (cluster, position) lays every cluster's members side by side
+//                        in order position, which is ascending prob: the chosen boxes are a SUFFIX of that run -- the last
+//                        n_obj_avg, or those above the threshold;  (4) a thread per cluster: int64 coordinate sums, NumPy's
+//                        pairwise fp32 sum, the two means.
 //   scan_count / scan_plan / scan_fill   the gather: per tile the records of every class counted, per (image, class) group the
 //                        tiles' places inside it and the groups' offsets (prefix sums), then every record copied to its place
 //                        with the tile's offset added.
-//   class_nms_kernel     a workgroup per class: the clusters of its images in image order, sorted as above, greedy NMS from the
-//                        end with nms_device.h's suppression test; the next pick found as the next `top` is.
+//   class_nms_kernel     a workgroup per class: the clusters of its images in image order, sorted as above (raw prob bits), greedy
+//                        NMS from the end: the same walk, a pick per round, with nms_device.h's suppression test.
 //   scan_write_kernel    the status, the classes in order of first appearance, the records.
 // All per-box state lives in the workspace; LDS holds one sort of up to 2048 keys and a few words.  No floating-point atomics.
 #include "radnet_internal.h"
@@ -25,37 +24,14 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = kNmsThreads;
 constexpr int kLdsKeys = 2048;      // keys sorted in LDS (16 KB); larger sorts run in the workspace
-constexpr int kHeader = 8;          // radnet_detect_tail's output: int32 words in front of the records ...
-constexpr int kRecord = 6;          // ... and per record
+constexpr int kHeader = RADNET_DETECT_HEADER_WORDS;      // radnet_detect_tail's output: int32 words in front of the records ...
+constexpr int kRecord = RADNET_DETECT_RECORD_WORDS;      // ... and per record
 constexpr int kMaxClasses = RADNET_SCAN_MAX_CLASSES;
 constexpr int kFlagMalformed = 1, kFlagRange = 2, kFlagEmpty = 4;      // final_nms_kernel's findings, by precedence
 
-__device__ __forceinline__ unsigned int sortable_bits(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __host__ __device__ __forceinline__ size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-// ascending bitonic sort of P keys (a power of two), by every thread of the workgroup; the keys are visible to all on entry
-template <typename Keys>
-__device__ __forceinline__ void bitonic_ascending(Keys k, int P) {
-  for (int kk = 2; kk <= P; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < P; i += kThreads) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const u64 a = k[i], b = k[ixj];
-          const bool up = (i & kk) == 0;
-          if (up ? a > b : a < b) { k[i] = b; k[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
 
 // ---- NumPy's fp32 sum of a contiguous vector (pairwise_sum of loops_utils.h.src, as np.add.reduce and np.mean call it) ------
 __device__ float np_block_sum(const float* a, int n) {      // n <= 128
@@ -179,7 +155,9 @@ __device__ void final_group(const FinalArgs& g, int grp, int lo, int n, int P, u
       const long long m = RADNET_SCAN_MAX_COORD;
       if (!(x1 < x2) || !(y1 < y2)) atomicOr(s_flags, kFlagMalformed);      // RADNet.py:171-172 asserts
       if (x1 < -m || y1 < -m || x2 > m || y2 > m || p != p) atomicOr(s_flags, kFlagRange);
-      key = ((u64)sortable_bits(p + 0.0f) << 32) | (unsigned int)i;         // p + 0: -0 sorts as +0 does
+      // signed zeros tie, as in np.argsort: the key of p + 0.0f (-0 + 0 = +0, the sum is the identity on every other non-NaN
+      // value, and a NaN has raised kFlagRange above, which returns before a key is read)
+      key = ((u64)sortable_bits_np(p) << 32) | (unsigned int)i;
     }
     K(i) = key;
   }
@@ -191,7 +169,7 @@ __device__ void final_group(const FinalArgs& g, int grp, int lo, int n, int P, u
     }
     return;
   }
-  if (kLds) bitonic_ascending(s_keys, P); else bitonic_ascending(gkeys, P);
+  if (kLds) bitonic_sort<false>(s_keys, P); else bitonic_sort<false>(gkeys, P);
   for (int i = tid; i < n; i += kThreads) {
     const int r = (int)(K(i) & 0xFFFFFFFFull);
     sbox[i] = make_int4((int)boxes[4 * r], (int)boxes[4 * r + 1], (int)boxes[4 * r + 2], (int)boxes[4 * r + 3]);
@@ -200,34 +178,32 @@ __device__ void final_group(const FinalArgs& g, int grp, int lo, int n, int P, u
   }
   __syncthreads();
 
-  // (2) the clusters: position j belongs to thread j % 1024 alone, so cid needs no ordering between threads
-  int top = n - 1, c = 0;
-  while (top >= 0) {
-    const int4 tb = sbox[top];
-    const long long at = (long long)(tb.z - tb.x) * (long long)(tb.w - tb.y);
-    if (tid == 0) s_next[(c + 1) % 3] = -1;               // last read before the previous barrier
-    int next = -1;
-    for (int j = tid; j < top; j += kThreads) {
-      if (cid[j] >= 0) continue;
-      const int4 b = sbox[j];
-      const long long iw = max(0, min(tb.z, b.z) - max(tb.x, b.x)), ih = max(0, min(tb.w, b.w) - max(tb.y, b.y));
-      const long long inter = iw * ih;
-      const long long ar = (long long)(b.z - b.x) * (long long)(b.w - b.y);
-      const double overlap = (double)inter / ((double)(at + ar - inter) + 1e-6);
-      if (overlap > g.thr) cid[j] = c; else next = j;      // j ascends: the last one left alive is the highest
-    }
-    if ((top & (kThreads - 1)) == tid) cid[top] = c;
-    if (next >= 0) atomicMax(&s_next[c % 3], next);
-    __syncthreads();
-    top = s_next[c % 3];
-    ++c;
-  }
-  const int nclus = c;
+  // (2) the clusters, a round of the walk each: cid[j] is the per-position state.  The overlap is RADNet.final_nms's own (exact
+  // integer areas, the quotient always taken), not suppresses().
+  int4 tb;
+  long long at;
+  const int nclus = walk_from_top(
+      n - 1, INT_MAX, s_next,
+      [&](int top, int c) {
+        tb = sbox[top];
+        at = (long long)(tb.z - tb.x) * (long long)(tb.w - tb.y);
+        if ((top & (kThreads - 1)) == tid) cid[top] = c;
+      },
+      [&](int j, int c) {
+        if (cid[j] >= 0) return true;
+        const int4 b = sbox[j];
+        const long long iw = max(0, min(tb.z, b.z) - max(tb.x, b.x)), ih = max(0, min(tb.w, b.w) - max(tb.y, b.y));
+        const long long inter = iw * ih;
+        const long long ar = (long long)(b.z - b.x) * (long long)(b.w - b.y);
+        const double overlap = (double)inter / ((double)(at + ar - inter) + 1e-6);
+        if (overlap > g.thr) cid[j] = c;
+        return overlap > g.thr;
+      });
 
   // (3) every cluster's members side by side, in order position
   for (int i = tid; i < P; i += kThreads) K(i) = i < n ? (((u64)(unsigned int)cid[i] << 32) | (unsigned int)i) : ~0ull;
   __syncthreads();
-  if (kLds) bitonic_ascending(s_keys, P); else bitonic_ascending(gkeys, P);
+  if (kLds) bitonic_sort<false>(s_keys, P); else bitonic_sort<false>(gkeys, P);
   for (int i = tid; i < n; i += kThreads) {
     const u64 k = K(i);
     const int ci = (int)(k >> 32);
@@ -519,9 +495,9 @@ __device__ void class_nms(const MergeArgs& g, int c, int start, int M, int P, u6
   double4* cbox = g.cbox + start;
   int* srow = g.srow + start;
   int* live = g.live + start;
-  for (int i = tid; i < P; i += kThreads) K(i) = i < M ? (((u64)sortable_bits(g.fprobs[crow[i]]) << 32) | (unsigned int)i) : ~0ull;      // nms_keys_kernel's keys
+  for (int i = tid; i < P; i += kThreads) K(i) = i < M ? (((u64)sortable_bits(g.fprobs[crow[i]]) << 32) | (unsigned int)i) : ~0ull;      // raw bits, as detect_tail_kernel's keys
   __syncthreads();
-  if (kLds) bitonic_ascending(s_keys, P); else bitonic_ascending(gkeys, P);
+  if (kLds) bitonic_sort<false>(s_keys, P); else bitonic_sort<false>(gkeys, P);
   for (int i = tid; i < M; i += kThreads) {
     const int row = crow[(int)(K(i) & 0xFFFFFFFFull)];
     const long long* b = g.fboxes + 4 * (size_t)row;
@@ -536,26 +512,23 @@ __device__ void class_nms(const MergeArgs& g, int c, int start, int M, int P, u6
     if (tid == 0) { g.cls_np[c] = 0; g.cls_bad[c] = 1; }
     return;
   }
-  // greedy from the end of the ascending order (among equal probs the higher index first); position j belongs to thread j % 1024
-  int top = M - 1, np = 0;
-  while (top >= 0 && np < g.max_boxes) {
-    const double4 pk = cbox[top];
-    const double pk_area = (pk.z - pk.x) * (pk.w - pk.y);
-    if (tid == 0) {
-      g.pick_row[(size_t)c * g.max_boxes + np] = srow[top];
-      s_next[(np + 1) % 3] = -1;
-    }
-    int next = -1;
-    for (int j = tid; j < top; j += kThreads) {
-      if (!live[j]) continue;
-      const double4 cb = cbox[j];
-      if (suppresses(pk, pk_area, cb, (cb.z - cb.x) * (cb.w - cb.y), g.nms_thr)) live[j] = 0; else next = j;
-    }
-    if (next >= 0) atomicMax(&s_next[np % 3], next);
-    __syncthreads();
-    top = s_next[np % 3];
-    ++np;
-  }
+  // greedy from the end of the ascending order (among equal probs the higher index first), a pick per round of the walk
+  double4 pk;
+  double pk_area;
+  const int np = walk_from_top(
+      M - 1, g.max_boxes, s_next,
+      [&](int top, int r) {
+        pk = cbox[top];
+        pk_area = (pk.z - pk.x) * (pk.w - pk.y);
+        if (tid == 0) g.pick_row[(size_t)c * g.max_boxes + r] = srow[top];
+      },
+      [&](int j, int) {
+        if (!live[j]) return true;
+        const double4 cb = cbox[j];
+        const bool hit = suppresses(pk, pk_area, cb, (cb.z - cb.x) * (cb.w - cb.y), g.nms_thr);
+        if (hit) live[j] = 0;
+        return hit;
+      });
   if (tid == 0) { g.cls_np[c] = np; g.cls_bad[c] = 0; }
 }
 

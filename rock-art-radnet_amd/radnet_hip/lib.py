@@ -107,7 +107,6 @@ class ScanMergeDesc(C.Structure):
 
 
 AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SALT_PEPPER, AUG_GAUSSIAN, AUG_POISSON = range(5)      # RADNET_AUG_* modes of radnet_aug_pointwise_u8
-DETECT_HEADER, DETECT_RECORD = 8, 6      # int32 words in front of / per record of radnet_detect_tail's output
 
 
 class AdamDesc(C.Structure):
@@ -186,6 +185,10 @@ def header_constant(name):
     if m is None:
         raise RadnetError("include/radnet_hip.h does not define %s" % name)
     return int(m.group(1))
+
+
+# int32 words in front of / per record of radnet_detect_tail's output
+DETECT_HEADER, DETECT_RECORD = header_constant("RADNET_DETECT_HEADER_WORDS"), header_constant("RADNET_DETECT_RECORD_WORDS")
 
 
 def load_library():

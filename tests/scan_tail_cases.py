@@ -335,6 +335,13 @@ def scan_merge_cases():
                           int(rs.randint(30, 45)), rs.uniform(0.7, 1.0)) for i, c in enumerate(cls)])
         tiles.append((int(100 * (t % 3)), int(37 * (t % 2)), t // 3))
     cases["random_three_images"] = dict(records=recs, tiles=tiles, slot_rows=120, nc=6)
+    # 2049 clusters of one class, beyond the NMS's LDS sort and two strides of its walk: disjoint boxes on a grid, 1025 in the first image and
+    # 1024 in the second, shifted by (4, 2): IoU 36*38 / (2*1600 - 36*38) = 0.747 > 0.4 across the images; probs with ties
+    rs = np.random.RandomState(12)
+    p = rs.uniform(0.5, 1.0, 2049).astype(np.float32)
+    p[rs.randint(0, 2049, 200)] = p[0]
+    grid = lambda n, dx, dy, pr: [_rec(1, 60 * (i % 35) + dx, 60 * (i // 35) + dy, 40, 40, pr[i]) for i in range(n)]
+    cases["class_nms_2049"] = dict(records=[grid(1025, 0, 0, p[:1025]), grid(1024, 4, 2, p[1025:])], tiles=[(0, 0, 0), (0, 0, 1)], slot_rows=1025, nc=2)
     return cases
 
 

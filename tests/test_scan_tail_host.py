@@ -83,6 +83,9 @@ def test_case_tables_hold_what_they_are_for():
     assert S.scan_merge_model(pool, tiles, **kw)[0] == 2
     pool, tiles, kw = S.build_scan_case(MERGE_CASES["cross_image_suppression"])
     assert S.scan_merge_model(pool, tiles, **kw)[0] == 3
+    pool, tiles, kw = S.build_scan_case(MERGE_CASES["class_nms_2049"])                      # 2049 candidates of one class, the cap reached
+    out = S.scan_merge_model(pool, tiles, **kw)
+    assert sum(len(r) for r in MERGE_CASES["class_nms_2049"]["records"]) == 2049 and (out[0], out[1]) == (300, 0)
 
 
 def test_model_equals_the_golden_final_nms():
