@@ -535,7 +535,8 @@ int radnet_aug_pointwise_u8(radnet_ctx* ctx, const uint8_t* src, uint8_t* dst, i
  * RADNET_PNG_UNFILTER_BAND_ROWS rows, one lane per row, each row one pixel behind the row above, and moves row data between global
  * memory and LDS in chunks of RADNET_PNG_UNFILTER_CHUNK_BYTES per row: the seams tests/test_gpu_png.py straddles.  Nothing waits
  * on another workgroup; the loop bounds depend on (rows, rowbytes, bpp) alone.  One workgroup is one CU: for whole files, and for
- * many at once, radnet_png_unfilter_segments_u8 below spreads the same walk over the device. */
+ * many at once, radnet_png_unfilter_segments_u8 below spreads the same walk over the device, and radnet_png_unfilter_tiles_u8 (further
+ * down) does so for rows of Up / Average / Paeth type, which allow no segment cut. */
 #define RADNET_PNG_UNFILTER_BAND_ROWS 512
 #define RADNET_PNG_UNFILTER_CHUNK_BYTES 96
 int radnet_png_unfilter_u8(radnet_ctx* ctx, uint8_t* stream, int32_t rows, int32_t rowbytes, int32_t bpp);
@@ -837,6 +838,56 @@ int radnet_png_gather_column_u8(radnet_ctx* ctx, const uint8_t* stream, int64_t 
  * Same rule, same result, same refusals. */
 int radnet_png_plan_segments_column(const uint8_t* column, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
                                     radnet_png_segment* out, int32_t cap);
+/* ---- adaptive-filter rows on all CUs: tiles (csrc/png_tiles.hip, csrc/png_tile_rule.h) ----
+ * Up, Average and Paeth rows allow no segment cut, but byte (r, x) needs only (r, x - bpp), (r - 1, x) and (r - 1, x - bpp).  A
+ * segment of R rows and P = rowbytes / bpp pixels is cut into bands of RADNET_PNG_TILE_ROWS rows (one wave, one lane per row, each
+ * row one pixel behind the row above, as in radnet_png_unfilter_u8) and column blocks of T = RADNET_PNG_TILE_PIXELS pixels.  Tiles
+ * are SKEWED: tile (band b, block c) holds, of the band's row l (lane l), the pixels [c * T - l, (c + 1) * T - l) clipped to
+ * [0, P), so the wave is full through the whole tile.  The tile reads, beside its own bytes, the pixels c * T - l - 1 of its rows
+ * l and l - 1 (tile (b, c - 1)) and of the last row of band b - 1 the pixels [c * T - 1, (c + 1) * T) (tiles (b - 1, c) and
+ * (b - 1, c + 1), because T >= 64).  So tile (b, c) runs on sweep d = c + 2 * b, tiles of one sweep are independent, and
+ *   bands = ceil(R / 64),  blocks = ceil((P + 63) / T),  sweeps = blocks + 2 * (bands - 1).
+ * On sweep d the bands lo .. hi have a tile, lo = max(0, ceil((d - blocks + 1) / 2)), hi = min(bands - 1, floor(d / 2)); the
+ * tile of blockIdx.x = i is (lo + i, d - 2 * (lo + i)); every sweep has a tile, except the odd sweeps of a segment of one block.  The rule stands once, in csrc/png_tile_rule.h, for the planner below and
+ * for the kernel and its launch code.  T = 64, the narrowest block the rule allows, by measurement: of the sweeps, 2 * (bands - 1) do
+ * not depend on T and each lasts as long as one tile, so on the 4000 x 4000 RGB panel the stage takes 6.6 ms at 64, 10.3 at 128 and
+ * 17.9 at 256 (profiles/png_unfilter_tiles_timing.txt). */
+#define RADNET_PNG_TILE_ROWS 64
+#define RADNET_PNG_TILE_PIXELS 64
+typedef struct radnet_png_tile_plan {
+  int32_t bands, blocks, sweeps; /* as above */
+  int32_t tile_rows, tile_pixels; /* RADNET_PNG_TILE_ROWS, RADNET_PNG_TILE_PIXELS */
+} radnet_png_tile_plan;
+/* Host only (csrc/png_plan.cpp; no context, no device): the plan of one segment of `rows` scanlines of `rowbytes` bytes.  RADNET_OK,
+ * or RADNET_ERR_ARG (nothing written) for a null `out`, rows or rowbytes < 1, rowbytes above 2^30, a bpp that is not one of 1, 2, 3,
+ * 4, 6, 8 or does not divide rowbytes. */
+int radnet_png_plan_tiles(int32_t rows, int32_t rowbytes, int32_t bpp, radnet_png_tile_plan* out);
+/* Host only: the tiles of sweep `sweep` (0 .. sweeps - 1) in blockIdx.x order.  Returns their number n and writes the first
+ * min(n, cap) of them as (band, block) pairs, 2 * min(n, cap) int32, to band_block_pairs, which may be null when cap is 0 (the
+ * count alone: what the launch code asks).  RADNET_ERR_ARG (nothing written) for the arguments radnet_png_plan_tiles refuses, a
+ * sweep outside the plan, a negative cap, or a null band_block_pairs with cap > 0. */
+int radnet_png_tiles_on_sweep(int32_t rows, int32_t rowbytes, int32_t bpp, int32_t sweep, int32_t* band_block_pairs, int32_t cap);
+/* radnet_png_unfilter_segments_u8 by tiles, for segments of any length: the same table contract, word for word -- the same table on
+ * the host and on the device, uploaded by the caller (this entry copies nothing); the host table validated before anything is
+ * launched (rows > 0, rowbytes > 0, rowbytes % bpp == 0, offset >= 0, offset + rows * (1 + rowbytes) <= base_len; a violation is
+ * RADNET_ERR_ARG naming the segment's index and nothing is modified); segments must not overlap (not checked); count == 0 is
+ * RADNET_OK without a launch, whatever the pointers; the table may be in any order; a whole pass is a table of one entry.  The bytes
+ * are those radnet_png_unfilter_u8 defines for each segment on its own: the row above the first row counts as zeros, the
+ * filter-type bytes stay, a type above 4 is treated as None.
+ * One plain kernel launch per sweep on the context's stream, max over the segments of `sweeps` launches in all (a sweep on which no
+ * segment has a tile is passed over), stream order being
+ * the only dependency: nothing waits on another workgroup, no flag or counter in memory, every loop bound a function of the
+ * arguments.  The grid of sweep d is (the most tiles any segment has on d, count) -- count in slices of 65535, the limit of
+ * gridDim.y --, one wave per workgroup and per tile; a workgroup whose segment has no such tile returns.  A tile goes through LDS
+ * in chunks of 32 pixels (16 for bpp 6 and 8), the next chunk's loads in flight while the wave works on this one, and every byte
+ * goes out with a byte store to a byte the tile owns: tiles of one sweep own neighbouring bytes of one dword. */
+int radnet_png_unfilter_tiles_u8(radnet_ctx* ctx, uint8_t* base, int64_t base_len, const radnet_png_segment* segs_host,
+                                 const radnet_png_segment* segs_dev, int32_t count, int32_t bpp);
+/* The same with the block width given, for the measurement of T (tools/png_unfilter_timing.py): tile_pixels a multiple of 32 from
+ * 64 to 4096, else RADNET_ERR_ARG.  The plan of such a call is the rule above with that T; the planner entries describe
+ * radnet_png_unfilter_tiles_u8 only. */
+int radnet_png_unfilter_tiles_width_u8(radnet_ctx* ctx, uint8_t* base, int64_t base_len, const radnet_png_segment* segs_host,
+                                       const radnet_png_segment* segs_dev, int32_t count, int32_t bpp, int32_t tile_pixels);
 /* Rectangles painted into a uint8 [h][w][3] device image (rows pitch_bytes apart) IN PLACE.  The contract is this package's own:
  *   the corners (x1, y1), (x2, y2) come in either order, as cv2.rectangle takes them, and are normalised to x1 <= x2, y1 <= y2;
  *   thickness < 0 (cv2.FILLED): pixel (x, y) is painted iff x1 <= x <= x2 and y1 <= y <= y2;

@@ -12,10 +12,12 @@
 // chunks of RADNET_PNG_UNFILTER_CHUNK_BYTES per row, consecutive lanes on consecutive bytes.  Every loop bound is a function of
 // (rows, rowbytes, bpp); workgroups never wait for each other: radnet_png_unfilter_u8 launches one, and
 // radnet_png_unfilter_segments_u8 one per segment, where a segment (csrc/png_plan.cpp) is a run of rows whose first row does not
-// read the row above it (row 0 of a pass, or filter type 0 / 1), so no segment reads a byte another one writes.
+// read the row above it (row 0 of a pass, or filter type 0 / 1), so no segment reads a byte another one writes.  Rows that allow no
+// such cut are spread over the device by png_tiles.hip (radnet_png_unfilter_tiles_u8), which shares png_predict.h with this file.
 // The writer's half is the forward filter (radnet_png_filter_rows_u8, further down): a device image to the scanline stream, one
 // workgroup per row, the adaptive choice of a row's filter type by integer sums.
 #include "radnet_internal.h"
+#include "png_predict.h"
 
 namespace {
 
@@ -26,20 +28,7 @@ static_assert(RADNET_PNG_UNFILTER_BAND_ROWS % 64 == 0 && kWaves >= 1 && kWaves <
 static_assert(kChunk % 24 == 0, "a chunk holds a whole number of pixels for every bpp in {1, 2, 3, 4, 6, 8}");
 static_assert(kWaves * 65 * kLdsStride <= 65536, "static LDS");
 
-// lane l receives lane l - 1's value (DPP wave_shr:1); lane 0 receives 0
-__device__ __forceinline__ int from_lane_above(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
-
-// Recon(x) - x for one byte: the predictor of filter type ft (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth)
-__device__ __forceinline__ int predictor(int ft, int a, int b, int c) {
-  const int pa = abs(b - c), pb = abs(a - c), pc = abs(a + b - 2 * c);
-  const int paeth = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-  int p = 0;
-  p = ft == 1 ? a : p;
-  p = ft == 2 ? b : p;
-  p = ft == 3 ? ((a + b) >> 1) : p;
-  p = ft == 4 ? paeth : p;
-  return p;
-}
+// from_lane_above (the DPP wave shift) and predictor: png_predict.h
 
 // The walk of one independent run of scanlines: `rows` rows of 1 + rowbytes bytes at `stream`, the row above row 0 counting as
 // zeros.  A whole pass is such a run, and so is a segment of one that starts on a row of filter type 0 or 1 (png_plan.cpp).

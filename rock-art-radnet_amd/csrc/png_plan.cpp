@@ -1,6 +1,7 @@
 // ---- host side of the segmented PNG reconstruction (png.hip): one pass -> independent segments ---------------------------
 // No device call and no HIP header: compiled by g++, runs without a GPU (contract: include/radnet_hip.h).
 #include "radnet_hip.h"
+#include "png_tile_rule.h"
 
 namespace {
 
@@ -54,4 +55,34 @@ extern "C" int radnet_png_plan_segments(const uint8_t* stream, int64_t stream_of
 extern "C" int radnet_png_plan_segments_column(const uint8_t* column, int64_t stream_offset, int32_t rows, int32_t rowbytes, int32_t target_rows,
                                                radnet_png_segment* out, int32_t cap) {
   return plan(column, 1, stream_offset, rows, rowbytes, target_rows, out, cap);
+}
+
+// ---- host side of the tiled reconstruction (png_tiles.hip): the plan of one segment, read off png_tile_rule.h --------------
+namespace {
+
+bool tile_args_ok(int32_t rows, int32_t rowbytes, int32_t bpp) {
+  if (rows <= 0 || rowbytes <= 0 || rowbytes > (1 << 30)) return false;
+  return (bpp == 1 || bpp == 2 || bpp == 3 || bpp == 4 || bpp == 6 || bpp == 8) && rowbytes % bpp == 0;
+}
+
+}  // namespace
+
+extern "C" int radnet_png_plan_tiles(int32_t rows, int32_t rowbytes, int32_t bpp, radnet_png_tile_plan* out) {
+  if (!out || !tile_args_ok(rows, rowbytes, bpp)) return RADNET_ERR_ARG;
+  const png_tile_grid g = png_tile_grid_of(rows, rowbytes / bpp, RADNET_PNG_TILE_PIXELS);
+  *out = radnet_png_tile_plan{g.bands, g.blocks, g.sweeps, RADNET_PNG_TILE_ROWS, RADNET_PNG_TILE_PIXELS};
+  return RADNET_OK;
+}
+
+extern "C" int radnet_png_tiles_on_sweep(int32_t rows, int32_t rowbytes, int32_t bpp, int32_t sweep, int32_t* band_block_pairs, int32_t cap) {
+  if (!tile_args_ok(rows, rowbytes, bpp) || cap < 0 || (cap > 0 && !band_block_pairs)) return RADNET_ERR_ARG;
+  const png_tile_grid g = png_tile_grid_of(rows, rowbytes / bpp, RADNET_PNG_TILE_PIXELS);
+  if (sweep < 0 || sweep >= g.sweeps) return RADNET_ERR_ARG;
+  int32_t lo;
+  const int32_t n = png_tiles_on_sweep(g, sweep, &lo);
+  for (int32_t i = 0; i < n && i < cap; ++i) {
+    band_block_pairs[2 * i] = lo + i;
+    band_block_pairs[2 * i + 1] = sweep - 2 * (lo + i);
+  }
+  return n;
 }

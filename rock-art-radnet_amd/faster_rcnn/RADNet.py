@@ -93,6 +93,7 @@ class RADNet():
 
     device_resident = True      # engine-backed models: keep tiles on the device between the stages (see _detect)
     device_tail = True          # ... and decode + per-class NMS + source-pixel coordinates too (see _tail_on_device)
+    png_unfilter = "band"       # predict_from_path: "tiles" reconstructs the maps' adaptive-filter rows on all CUs (png.decode_device(unfilter=))
     png_inflate = "host"        # predict_from_path: "device" / "device-lz" inflate the maps' IDAT streams on the device (png.decode_device(inflate=))
     scan_tail = False           # ... and the merge of a scan's tiles: final_nms per image, NMS across images (see _scan_tail_on)
 
@@ -590,14 +591,18 @@ class RADNet():
         utils_io.get_image (faster_rcnn/png.py decodes; no OpenCV), then predict.  With the engine-backed models and
         `device_resident` the decoded images stay on the device (get_image(..., to_host=False)); otherwise they are host arrays.
         `png_inflate = "device"` or `"device-lz"` is handed to get_image as inflate=: the same images, inflated on the device where
-        the file allows (run-length streams, or any deflate stream)."""
+        the file allows (run-length streams, or any deflate stream).  `png_unfilter = "tiles"` is handed on as unfilter=: the same
+        images, their scanlines reconstructed by tiles."""
         from . import utils_io
         C = self.C
         to_host = not self._takes_device_images()
+        how = dict(inflate=self.png_inflate)
+        if self.png_unfilter != "band":
+            how["unfilter"] = self.png_unfilter
         if C.use_img_type:
-            images = [utils_io.get_image(img_path, [img_type], random_type=False, to_host=to_host, inflate=self.png_inflate) for img_type in C.img_types]
+            images = [utils_io.get_image(img_path, [img_type], random_type=False, to_host=to_host, **how) for img_type in C.img_types]
         else:
-            images = [utils_io.get_image(img_path, C.img_types, random_type=False, to_host=to_host, inflate=self.png_inflate)]
+            images = [utils_io.get_image(img_path, C.img_types, random_type=False, to_host=to_host, **how)]
         return self.predict(images)
 
     # ---- the RPN alone: objectness maps and proposals over a scan (RADNet.py:310-480, train.py:338-347) ------------------------

@@ -18,6 +18,8 @@ decode_device(inflate="device") uploads the COMPRESSED stream instead (parse_com
 emitted), for run-length streams; whatever the device cannot take goes to the host path above.  The default is that path, byte for byte.
 decode_device(inflate="device-lz") does so for any deflate stream (csrc/inflate_lz.hip): emit writes the literals and every byte's
 source position, pointer jumping flattens the sources, a gather copies each byte from its root.
+decode_device(unfilter="tiles"), and decode_device_many likewise, reconstructs rows of Up / Average / Paeth type, which allow no
+segment cut, on all CUs (csrc/png_tiles.hip): tiles of 64 rows by TILE_PIXELS pixels, one launch per sweep of independent tiles.
 
 Formats: colour types 0, 2, 3, 4, 6 with the bit depths 1, 2, 4, 8, 16 the PNG specification allows for each; non-interlaced and
 Adam7.  Output rules: grey is replicated to three channels, depths 1 / 2 / 4 scaled by 255 / 85 / 17; palette entries are looked up
@@ -67,6 +69,41 @@ def _unfilter_constant(name):
 # band and chunk of radnet_png_unfilter_u8 (the seams its tests straddle), read from the header the kernel is compiled with
 UNFILTER_BAND_ROWS = _unfilter_constant("RADNET_PNG_UNFILTER_BAND_ROWS")
 UNFILTER_CHUNK_BYTES = _unfilter_constant("RADNET_PNG_UNFILTER_CHUNK_BYTES")
+# the tile of radnet_png_unfilter_tiles_u8 (unfilter="tiles"): rows of a band, pixels of a column block
+TILE_ROWS = _unfilter_constant("RADNET_PNG_TILE_ROWS")
+TILE_PIXELS = _unfilter_constant("RADNET_PNG_TILE_PIXELS")
+UNFILTER_MODES = ("band", "tiles")
+TilePlan = collections.namedtuple("TilePlan", "bands blocks sweeps tile_rows tile_pixels")      # radnet_png_tile_plan
+
+
+def _check_unfilter(unfilter):
+    if unfilter not in UNFILTER_MODES:
+        raise ValueError("PNG: unfilter=%r (\"band\" or \"tiles\")" % (unfilter,))
+
+
+def plan_tiles(rows, rowbytes, bpp):
+    """radnet_png_plan_tiles (host only, no device): TilePlan(bands, blocks, sweeps, tile_rows, tile_pixels) of one segment of `rows`
+    scanlines of `rowbytes` bytes; sweeps is the number of launches radnet_png_unfilter_tiles_u8 makes for it.  ValueError for
+    arguments the planner refuses."""
+    import ctypes
+    from radnet_hip import lib as L
+    out = (ctypes.c_int32 * 5)()
+    rc = L.load_library().radnet_png_plan_tiles(int(rows), int(rowbytes), int(bpp), out)
+    if rc != 0:
+        raise ValueError("PNG: radnet_png_plan_tiles refuses %d rows of %d bytes at %d bytes per pixel (%d)" % (rows, rowbytes, bpp, rc))
+    return TilePlan(*out)
+
+
+def tiles_on_sweep(rows, rowbytes, bpp, sweep):
+    """radnet_png_tiles_on_sweep: the (band, block) pairs of a sweep in blockIdx.x order, as a list of tuples."""
+    from radnet_hip import lib as L
+    fn = L.load_library().radnet_png_tiles_on_sweep
+    n = fn(int(rows), int(rowbytes), int(bpp), int(sweep), None, 0)
+    if n < 0:
+        raise ValueError("PNG: radnet_png_tiles_on_sweep refuses sweep %d of %d rows of %d bytes at %d bytes per pixel (%d)" % (sweep, rows, rowbytes, bpp, n))
+    pairs = np.zeros((n, 2), np.int32)
+    assert fn(int(rows), int(rowbytes), int(bpp), int(sweep), pairs.ctypes.data, n) == n
+    return [tuple(p) for p in pairs.tolist()]
 
 
 def _chunk(data, pos):
@@ -431,9 +468,10 @@ def _checked_stream(comp, ctx, report, stream):
     return stream
 
 
-def _decode_inflated_on_device(data, ctx, report, lz=False):
+def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False):
     """decode_device's device inflate (lz: the one for any stream): the image, or None when the host path has to take the file
-    (report["reason"])."""
+    (report["reason"]).  tiles: unfilter="tiles" -- segments of at most 64 rows go to radnet_png_unfilter_segments_u8, all longer ones
+    to radnet_png_unfilter_tiles_u8, whether or not the segments spread the passes."""
     import ctypes
     import torch
     from radnet_hip import lib as L
@@ -471,7 +509,20 @@ def _decode_inflated_on_device(data, ctx, report, lz=False):
             tables.append(table[:got])
             spread = spread and 2 * int(table[:got]["rows"].max()) <= p.pass_h
             row0 += p.pass_h
-        if spread:
+        if tiles:
+            table = np.concatenate(tables)
+            table = table[np.argsort(table["rows"] > TILE_ROWS, kind="stable")]
+            short = int((table["rows"] <= TILE_ROWS).sum())
+            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
+            _lap(report, "plan_segments_ms")
+            if short:
+                _launch(report, ctx, "radnet_png_unfilter_segments_u8", base, comp.expected, table.ctypes.data, table_dev, short, comp.bpp)
+            if short < len(table):
+                _launch(report, ctx, "radnet_png_unfilter_tiles_u8", base, comp.expected, table.ctypes.data + SEGMENT.itemsize * short,
+                        table_dev.data_ptr() + SEGMENT.itemsize * short, len(table) - short, comp.bpp)
+            report["reconstruction"] = "segments+tiles" if short else "tiles"
+            report["sweeps"] = max([plan_tiles(int(t["rows"]), int(t["rowbytes"]), comp.bpp).sweeps for t in table[short:]], default=0)
+        elif spread:
             table = np.concatenate(tables)
             table = table[np.argsort(table["rows"] > 64, kind="stable")]
             table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
@@ -490,7 +541,7 @@ def _decode_inflated_on_device(data, ctx, report, lz=False):
     return AD.hand_over(out, side)
 
 
-def decode_device(data, ctx=None, inflate="host", report=None):
+def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band"):
     """The decoded image as a uint8 [H][W][3] (B, G, R) cuda tensor: parse, ONE pinned upload of the inflated stream (the palette
     rides behind it), then reconstruction and expansion per pass.  ctx: a radnet context whose stream is torch's current one;
     None = the calling thread's default context, on a BackgroundFeed worker thread on that thread's own stream.
@@ -509,17 +560,28 @@ def decode_device(data, ctx=None, inflate="host", report=None):
     ceil(log2(bytes)) rounds; more is a RuntimeError) and radnet_inflate_lz_gather; then the same checks and reconstruction.  What it
     cannot take -- a unit above the symbol cap, a corrupt stream, a match that reaches in front of the stream, a broken container --
     goes to the host path as above.  In this mode the report also carries rounds (those that rewrote an entry) and far_units (the
-    chained units with a match of another distance than 1)."""
+    chained units with a match of another distance than 1).
+    unfilter="tiles" (opt-in; "band" is everything above, launch for launch): rows of adaptive filter types are reconstructed on all
+    CUs by radnet_png_unfilter_tiles_u8 (csrc/png_tiles.hip: tiles of 64 rows by TILE_PIXELS pixels, one launch per sweep of
+    independent tiles) instead of one workgroup per pass.  On the host-inflate path ONE such call carries all passes of the file (a
+    table of one entry per pass rides behind the palette in the staging buffer); on the device-inflate paths the segments of at most
+    64 rows keep radnet_png_unfilter_segments_u8 and all longer ones go to the tiles entry.  The bytes are those of "band".  In this
+    mode alone the report's reconstruction is "tiles" or "segments+tiles" (segments of both kinds) and it carries sweeps, the
+    launches of the tiles call: the most sweeps radnet_png_plan_tiles gives for one of its segments."""
     import torch
     from . import augmentation_device as AD
     if inflate not in ("host", "device", "device-lz"):
         raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
+    _check_unfilter(unfilter)
+    tiles = unfilter == "tiles"
     report = {} if report is None else report
     report.update(path="host", reason=None, candidates=0, false_candidates=0, units=0, blocks=0, reconstruction=None)
     lz = dict(rounds=0, far_units=0) if inflate == "device-lz" else {}
     report.update(lz)
+    if tiles:
+        report["sweeps"] = 0
     if inflate != "host":
-        out = _decode_inflated_on_device(data, ctx, report, lz=bool(lz))
+        out = _decode_inflated_on_device(data, ctx, report, lz=bool(lz), tiles=tiles)
         if out is not None:
             return out
         report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None, **lz)
@@ -527,15 +589,25 @@ def decode_device(data, ctx=None, inflate="host", report=None):
     img = parse(data)
     n = len(img.stream)
     with AD.feed_stream(ctx) as (ctx, side):
-        staged = torch.empty(n + 768, dtype=torch.uint8, pin_memory=True)
+        seg_at = (n + 768 + 7) & ~7                        # the tiles table: 8-byte aligned behind the palette
+        table = np.array([(p.stream_offset, p.pass_h, p.rowbytes) for p in img.passes], SEGMENT) if tiles else np.zeros(0, SEGMENT)
+        staged = torch.empty(seg_at + table.nbytes if tiles else n + 768, dtype=torch.uint8, pin_memory=True)
         host = staged.numpy()
         host[:n] = np.frombuffer(img.stream, np.uint8)
-        host[n:] = img.palette.reshape(-1)
+        host[n:n + 768] = img.palette.reshape(-1)
+        if tiles:
+            host[n + 768:seg_at] = 0
+            host[seg_at:] = table.view(np.uint8)
         dev = staged.cuda(non_blocking=True)
         out = torch.empty((img.header.height, img.header.width, 3), dtype=torch.uint8, device="cuda")
         base = dev.data_ptr()
+        if tiles:
+            ctx.call("radnet_png_unfilter_tiles_u8", base, n, host.ctypes.data + seg_at, base + seg_at, len(table), img.bpp)
+            report["reconstruction"] = "tiles"
+            report["sweeps"] = max(plan_tiles(p.pass_h, p.rowbytes, img.bpp).sweeps for p in img.passes)
         for p in img.passes:
-            ctx.call("radnet_png_unfilter_u8", base + p.stream_offset, p.pass_h, p.rowbytes, img.bpp)
+            if not tiles:
+                ctx.call("radnet_png_unfilter_u8", base + p.stream_offset, p.pass_h, p.rowbytes, img.bpp)
             ctx.call("radnet_png_expand_bgr_u8", base + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, img.header.color_type, img.header.bit_depth,
                      base + n, out, img.header.height, img.header.width, p.y0, p.x0, p.dy, p.dx)
     return AD.hand_over(out, side)
@@ -573,16 +645,18 @@ def plan_segments(img, base_offset=0, target_rows=0):
     return np.concatenate(tables)
 
 
-def decode_device_many(datas, ctx=None, workers=None):
+def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
     """decode_device for a list of files in one pass: a list of uint8 [H][W][3] (B, G, R) cuda tensors, byte for byte what
     [decode_device(d) for d in datas] returns.  The files are parsed (CRC, inflate) on `workers` host threads (default
     min(len(datas), 8), at most 16); a file that fails raises its ValueError prefixed with "file <index>: " before any device
     work.  Then ONE pinned staging buffer and ONE upload: the streams, the palettes, the segment table (8-byte aligned, short
     segments first inside each bpp); one radnet_png_unfilter_segments_u8 per distinct bpp; one radnet_png_expand_bgr_u8 per pass.
-    ctx and the stream rules are decode_device's."""
+    ctx and the stream rules are decode_device's.  unfilter="tiles": inside each bpp the segments of at most 64 rows go as above and
+    the longer ones to one radnet_png_unfilter_tiles_u8; the bytes are the same."""
     import concurrent.futures
     import torch
     from . import augmentation_device as AD
+    _check_unfilter(unfilter)
     datas = list(datas)
     if not datas:
         return []
@@ -622,8 +696,11 @@ def decode_device_many(datas, ctx=None, workers=None):
         base = dev.data_ptr()
         first = 0
         for bpp, n in zip(*np.unique(bpps, return_counts=True)):
-            ctx.call("radnet_png_unfilter_segments_u8", base, n_streams, host.ctypes.data + seg_at + 16 * first, base + seg_at + 16 * first,
-                     int(n), int(bpp))
+            # with tiles the long segments, which stand behind the short ones of their bpp, leave the segments call for the tiles call
+            short = int((table["rows"][first:first + int(n)] <= TILE_ROWS).sum()) if unfilter == "tiles" else int(n)
+            for entry, at, count in (("radnet_png_unfilter_segments_u8", first, short), ("radnet_png_unfilter_tiles_u8", first + short, int(n) - short)):
+                if count:
+                    ctx.call(entry, base, n_streams, host.ctypes.data + seg_at + 16 * at, base + seg_at + 16 * at, count, int(bpp))
             first += int(n)
         outs = []
         for k, im in enumerate(imgs):

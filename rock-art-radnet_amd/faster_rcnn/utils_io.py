@@ -19,12 +19,13 @@ def image_path(img_path, img_type):
     return os.path.join(*parts)
 
 
-def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, inflate="host"):
+def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, inflate="host", unfilter="band"):
     """utils.get_image, draw for draw: types[0], or with random_type one rng.choice(types, 1, p=probs)[0] where the first type has
     probability 0.5 (up to three types) or 0.3 and the others share the rest.  Returns the uint8 BGR HWC image as a NumPy array,
     or with to_host=False as a cuda tensor (nothing is downloaded).  inflate="device" inflates the file's IDAT stream on the device
     (png.decode_device: run-length streams; anything else takes the host path as before), inflate="device-lz" does so for a stream
-    with matches at any distance; another value is png.decode_device's ValueError."""
+    with matches at any distance; another value is png.decode_device's ValueError.  unfilter="tiles" reconstructs the scanlines by
+    tiles on all CUs (png.decode_device: the same image); another value than "band" or "tiles" is its ValueError too."""
     img_type = types[0]
     if random_type:
         first_prob = 0.3
@@ -33,9 +34,10 @@ def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, i
         probs = [first_prob] + [(1.0 - first_prob) / (len(types) - 1) for i in range(len(types) - 1)]
         img_type = rng.choice(types, 1, p=probs)[0]
     buf = np.fromfile(image_path(img_path, img_type), np.uint8)
-    if inflate == "host":
+    if inflate == "host" and unfilter == "band":
         return png.imdecode_color(buf) if to_host else png.decode_device(buf)
-    img = png.decode_device(buf, inflate=inflate)
+    tiles = {} if unfilter == "band" else dict(unfilter=unfilter)      # the default call is the one it was
+    img = png.decode_device(buf, inflate=inflate, **tiles)
     return img.cpu().numpy() if to_host else img
 
 
@@ -59,9 +61,12 @@ class DeviceImageLoader:
     RADNet.predict directly: with the engine-backed models it cuts and resizes every tile on the device (RADNet.ImageWindow).
     prefetch() fills the cache ahead of the calls, many files per decode (png.decode_device_many): the types of a scan, the next
     images of a feed.  The cache holds one decoder's images: with decode= set and decode_many= not, prefetch decodes through
-    decode, file by file."""
+    decode, file by file.  unfilter="tiles" is handed to the default decoders of both (png.decode_device and decode_many's
+    unfilter=); a decoder of the caller's is called as it is."""
 
-    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None):
+    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band"):
+        png._check_unfilter(unfilter)
+        self.unfilter = unfilter
         self.cache_bytes = int(cache_bytes)
         self.decode = decode                       # (file bytes as uint8 array) -> image; default: png.decode_device
         # (list of file bytes) -> list of images, for prefetch; default: png.decode_device_many, or `decode` on each file if that is set
@@ -100,7 +105,7 @@ class DeviceImageLoader:
         elif self.decode is not None:
             decode_many = lambda files: [self.decode(f) for f in files]      # noqa: E731  (one decoder fills the cache)
         else:
-            decode_many = png.decode_device_many
+            decode_many = png.decode_device_many if self.unfilter == "band" else lambda files: png.decode_device_many(files, unfilter=self.unfilter)      # noqa: E731
         todo, seen = [], set()
         for img_data, img_type in pairs:
             path, key = self._key(img_data, img_type)
@@ -138,7 +143,10 @@ class DeviceImageLoader:
             return hit[0]
         self.misses += 1
         buf = np.fromfile(path, np.uint8)
-        img = png.decode_device(buf) if self.decode is None else self.decode(buf)
+        if self.decode is not None:
+            img = self.decode(buf)
+        else:
+            img = png.decode_device(buf) if self.unfilter == "band" else png.decode_device(buf, unfilter=self.unfilter)
         self._insert(key, img)
         return img
 

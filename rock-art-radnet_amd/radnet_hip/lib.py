@@ -318,6 +318,10 @@ def load_library():
         "radnet_inflate_lz_gather": (C.c_int, [vp, vp, vp, i64]),
         "radnet_png_gather_column_u8": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, vp]),
         "radnet_png_plan_segments_column": (C.c_int, [vp, i64, i32, i32, i32, vp, i32]),
+        "radnet_png_plan_tiles": (C.c_int, [i32, i32, i32, vp]),
+        "radnet_png_tiles_on_sweep": (C.c_int, [i32, i32, i32, i32, vp, i32]),
+        "radnet_png_unfilter_tiles_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32]),
+        "radnet_png_unfilter_tiles_width_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, i32]),
         "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
         "radnet_draw_list_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
         "radnet_draw_glyph_rows": (C.c_int, [i32, vp]),
