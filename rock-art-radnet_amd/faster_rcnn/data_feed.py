@@ -347,7 +347,8 @@ def _insitu_tables(ts, first_batch, lookahead, next_batch, budget_s, cache_dir, 
             comm = insitu.DistComm(dist, dist_group)
     except Exception:
         pass
-    dev_name = torch.cuda.get_device_name(eng.dev) if torch.cuda.is_available() else "cpu"
+    on_gpu = torch.cuda.is_available() and torch.device(eng.dev).type == "cuda"       # (an engine on the host beside a visible GPU: "cpu")
+    dev_name = torch.cuda.get_device_name(eng.dev) if on_gpu else "cpu"
     path = insitu.cache_path(getattr(eng, "NETWORK", "net"), getattr(eng, "workload", "train"), H, W, len(first_batch), dev_name, cache_dir)
     shipped = any("%dx%d_batch%d" % (H, W, len(first_batch)) in n for n in getattr(eng, "shipped_tuning", []))
     text = None

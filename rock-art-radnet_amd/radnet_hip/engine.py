@@ -436,11 +436,13 @@ class FasterRCNNEngine:
             self.bf16.refresh()
             self._refresh_winograd([n for n in self.INFERENCE_WINOGRAD_LAYERS if getattr(self.convs.get(n), "wino_u", None) is not None])
 
-    def refresh_head_shift(self):
+    def refresh_head_shift(self, force=False):
         """shift = scale * bias + t0 for every stage-5 conv (FixedBatchNormalization.py:59-85 folded).  A no-op right after adam()
-        of the head arena, which refreshes the shifts in the same launch (radnet_adam_step_affine)."""
-        if self._head_shift_fresh:
-            self._head_shift_fresh = False
+        of the head arena, which refreshes the shifts in the same launch (radnet_adam_step_affine) -- the trainers' call behind it costs
+        no launch.  force: whoever writes the biases some other way (set_weights, and so every load path) folds them whatever an
+        earlier adam() left behind."""
+        fresh, self._head_shift_fresh = self._head_shift_fresh, False
+        if fresh and not force:
             return
         bias = self.head_arena.p[self.head_bias_off:self.head_bias_off + self.head_bias_len]
         self.ctx.call("radnet_affine_vec", self.head_shift, self.head_scale, bias, self.head_t0, C.c_int64(self.head_bias_len))
@@ -493,7 +495,7 @@ class FasterRCNNEngine:
         b = np.zeros(self.dense_ld, np.float32)
         b[:self.nc] = dc["bias"]; b[self.nc:self.nc + self.nreg] = dr["bias"]
         self.dense_w.copy_(t(k)); self.dense_b.copy_(t(b))
-        self.refresh_head_shift()
+        self.refresh_head_shift(force=True)
         self._refresh_winograd()
         self.bf16.refresh()
         torch.cuda.synchronize(self.dev)

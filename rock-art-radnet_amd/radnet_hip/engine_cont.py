@@ -77,6 +77,13 @@ class ContEngine(FasterRCNNEngine):
             c.t0 = self.s34_t0[o:o + c.cout]
             c.shift = self.s34_shift[o:o + c.cout]
 
+    def _uses_winograd(self, c, inference=False):
+        # direct stage-3/4 forward (S34_WINOGRAD off): no program reads a transformed filter of these layers, so none is made --
+        # adam_s34() would leave a copy behind that nobody rewrites
+        if not self.S34_WINOGRAD and c.name in self.WINOGRAD_F4_LAYERS:
+            return False
+        return super()._uses_winograd(c, inference)
+
     def refresh_s34_shift(self):
         """shift = scale * bias + t0 for every stage-3/4 conv (frozen BN folded around the trainable bias)."""
         bias = self.s34_arena.p[self.s34_bias_off:self.s34_bias_off + self.s34_bias_len]

@@ -87,7 +87,7 @@ class VGG16Engine(FasterRCNNEngine):
         self.training = True
         self.forced_masks = None
 
-    def refresh_head_shift(self):
+    def refresh_head_shift(self, force=False):
         pass                                                  # no BN in the VGG head: shift IS the bias
 
     # ------------------------------------------------------------------------------------------ weights
@@ -119,6 +119,7 @@ class VGG16Engine(FasterRCNNEngine):
         k[:, :self.nc] = dc["kernel"]; k[:, self.nc:self.nc + self.nreg] = dr["kernel"]
         b[:self.nc] = dc["bias"]; b[self.nc:self.nc + self.nreg] = dr["bias"]
         self.dense_w.copy_(t(k)); self.dense_b.copy_(t(b))
+        self._refresh_winograd()                              # rpn_conv1's transformed filter follows every load, as in FasterRCNNEngine
         torch.cuda.synchronize(self.dev)
 
     def get_weights(self, names=None):

@@ -18,6 +18,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from derived_state import fwd_image_bits  # noqa: E402  (the layout statement of the forward image, shared with the auditor)
+
 # calibrated with tools/bf16_emulate.py ("bf16 inference mode"): measured x >= 3
 BOUND_F_REL = 1.5e-2
 BOUND_RPN = 1.0e-2
@@ -62,7 +64,7 @@ def test_weights_to_bf16_bit_exact_transposed_zero_padded(ctx):
     ctx.call("radnet_weights_to_bf16", wd, K, N, ldw, wt, ldk)
     torch.cuda.synchronize()
     got = wt.cpu().numpy().view(np.uint16)
-    ref = torch.from_numpy(np.ascontiguousarray(w[:, :N].T)).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    ref = fwd_image_bits(w, N)
     assert np.array_equal(got[:, :K], ref)
     assert not got[:, K:].any(), "K padding must be zero"
 

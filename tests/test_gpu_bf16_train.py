@@ -20,18 +20,15 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
+# the rounding and the dgrad layout statements, shared with the auditor of the engines' derived buffers
+from derived_state import bf16_bits as _bf16_bits, dgrad_image_ref as _dgrad_image_ref  # noqa: E402
+
 
 def _cfg(img_size=600):
     from faster_rcnn.config import Config
     C_ = Config()
     C_.img_size = img_size
     return C_
-
-
-def _bf16_bits(a):
-    """NumPy round to nearest, ties to even, fp32 -> bf16 bit patterns (uint16); finite inputs."""
-    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
 
 
 def _bf16_round(a):
@@ -67,16 +64,6 @@ def lanes():
 
 
 # ------------------------------------------------------------------------------------------------------------ 1. cast
-def _dgrad_image_ref(w, taps, c, n, ldkd):
-    """wd[i][t*n8 + j] = bf16(w[t*c + i][j]); zero elsewhere."""
-    n8 = (n + 7) // 8 * 8
-    ref = np.zeros((c, ldkd), np.uint16)
-    b = _bf16_bits(w[:, :n]).reshape(taps, c, n)
-    for t in range(taps):
-        ref[:, t * n8:t * n8 + n] = b[t]
-    return ref
-
-
 @pytest.mark.parametrize("taps,c,n,ldw,extra", [(1, 512, 60, 64, 0), (9, 64, 64, 64, 0), (9, 40, 20, 24, 32), (1, 8, 4, 4, 8)])
 def test_dgrad_image_cast(lanes, taps, c, n, ldw, extra):
     cx, st, _ = lanes[0]
