@@ -180,7 +180,12 @@ int radnet_conv_bwd(radnet_ctx* ctx, const radnet_conv_desc* d);
  * does NOT store the gradient: opt->g is neither written nor read, the same bits as radnet_conv_wgrad into a zeroed arena followed by
  * radnet_adam_step over these ranges.  The caller guarantees that nothing in flight reads the weights (all data gradients of the step
  * have run).  Bias gradients still go to d->db.  Refused: dw_accumulate == 1, and split problems on a context whose reductions are
- * not ordered (radnet_set_deterministic 0).  opt == 0 or opt->p == 0: gradients only. */
+ * not ordered (radnet_set_deterministic 0).  opt == 0 or opt->p == 0: gradients only.
+ * A refused call launches no kernel and changes no byte of opt->p / m / v, but the problems are prepared one by one, each with the host
+ * side of its own radnet_conv_wgrad call, before the later ones are checked: when problem i is refused, the memsets of write mode 0 --
+ * db, and dw where the slices add with atomics -- of problems 0 .. i-1 (and of problem i itself where the refusal comes after its own
+ * preparation: atomic slices under an optimizer block) are already enqueued, so exactly those destinations may hold zeros.  With
+ * dw_accumulate == 2 throughout, a refused call changes nothing. */
 typedef struct radnet_wgrad_adam {
   float* p; float* g; float* m; float* v;   /* the four arenas; dw - g locates a problem's weights and moments */
   int64_t n;                                /* floats per arena */
