@@ -893,6 +893,64 @@ int radnet_png_unfilter_tiles_u8(radnet_ctx* ctx, uint8_t* base, int64_t base_le
  * radnet_png_unfilter_tiles_u8 only. */
 int radnet_png_unfilter_tiles_width_u8(radnet_ctx* ctx, uint8_t* base, int64_t base_len, const radnet_png_segment* segs_host,
                                        const radnet_png_segment* segs_dev, int32_t count, int32_t bpp, int32_t tile_pixels);
+/* ---- CRC-32 of PNG chunks on the device (csrc/crc32.hip, csrc/crc32_plan.cpp, csrc/crc32_rule.h) ------------------------------------
+ * The CRC-32 of zlib and PNG: polynomial 0xEDB88320, reflected (bit 31 of a register is the coefficient of x^0), init and final
+ * xor 0xFFFFFFFF.  With pure(B) the register after the bytes B from init 0 without the final xor, and products taken mod P:
+ *   pure(A || B) = pure(A) * x^(8 |B|) ^ pure(B);   pure(0^k || B) = pure(B);
+ *   zlib.crc32(B, c0) = pure(B) ^ (c0 ^ 0xFFFFFFFF) * x^(8 |B|) ^ 0xFFFFFFFF.
+ * So a range of bytes is summed in pieces of any size, on any number of workgroups in any order, and the result is exact. */
+typedef struct radnet_crc32_segment {
+  int64_t offset;  /* of the segment's first byte in the buffer */
+  int64_t length;  /* in bytes; 0 is legal */
+  uint32_t init;   /* the running value in front of the segment: 0 for a sum of its own, zlib.crc32(b"IDAT") for a chunk's payload */
+  uint32_t expect; /* what the sum is compared with */
+} radnet_crc32_segment; /* 24 bytes */
+/* THE GRAIN RULE: a lane sums RADNET_CRC32_GRAIN bytes, a workgroup a span of RADNET_CRC32_SPAN_GRAINS grains (4096 bytes).  The
+ * last bytes of a segment behind the last 16-byte boundary of device memory inside it (0..15, the tail) are summed one by one; the
+ * body in front of them is cut into grains counted BACKWARDS from that boundary, so that every grain is one aligned 16-byte load
+ * but the segment's first, which is read byte by byte and padded in front with zeros (free, by the second identity); spans are
+ * counted backwards from the same boundary.  A unit that stands i units in front of the end weighs x^(8 * unit * i): constants,
+ * generated at compile time (csrc/crc32_rule.h). */
+#define RADNET_CRC32_GRAIN 16
+#define RADNET_CRC32_SPAN_GRAINS 256
+#define RADNET_CRC32_MAX_SPANS 2147483646
+typedef struct radnet_crc32_plan {
+  int64_t spans;    /* of all segments together: the workgroups of the span launch */
+  int64_t ws_bytes; /* of scratch the call takes from the context: 4 * (count + 1 + spans) */
+} radnet_crc32_plan;
+/* Host only (csrc/crc32_plan.cpp; no context, no device).  x^(8 len) mod P as a register; len <= 0 gives x^0 = 0x80000000. */
+uint32_t radnet_crc32_shift(int64_t len);
+/* Host only.  zlib's crc32_combine: zlib.crc32(a + b) from crc1 = zlib.crc32(a), crc2 = zlib.crc32(b), len2 = len(b); crc1 for
+ * len2 <= 0. */
+uint32_t radnet_crc32_combine(uint32_t crc1, uint32_t crc2, int64_t len2);
+/* Host only: the validation and the grain plan radnet_crc32_segments runs before it launches.  table: `count` segments in HOST
+ * memory for a buffer of n bytes whose first byte stands `misalign` (0..15) bytes behind a 16-byte boundary.  RADNET_ERR_ARG, with
+ * the reason in msg (msg_cap bytes; may be null) and the first bad segment's index in *bad_entry (-1 when the arguments
+ * themselves are refused; may be null): a null plan, count < 0, n < 0, misalign outside 0..15, a null table with count > 0, a
+ * segment with offset < 0, length < 0 or offset + length > n (checked without overflow).  More than RADNET_CRC32_MAX_SPANS spans
+ * is RADNET_ERR_UNSUPPORTED.  *plan is written on RADNET_OK only. */
+int radnet_crc32_plan_segments(const radnet_crc32_segment* table, int32_t count, int64_t n, int32_t misalign, radnet_crc32_plan* plan,
+                               int32_t* bad_entry, char* msg, int32_t msg_cap);
+/* crc[k] = zlib.crc32(buf[offset_k : offset_k + length_k], init_k) for the `count` segments of the device buffer buf[0 .. n);
+ * result[0] = the smallest k with crc[k] != expect_k, or count when there is none; result[1] = how many such k there are.  The
+ * entry initialises result itself (on the stream; nothing is copied or waited for).  count == 0 is legal, gives {0, 0} and may
+ * come with null tables and a null crc; n == 0 may come with a null buf.  Segments may overlap, may be empty and may come in any
+ * order; buf may stand at any byte address.  table_host and table_dev hold the SAME table on the host and on the device (the
+ * caller uploads it, as for radnet_png_unfilter_segments_u8); table_dev is 8-byte aligned, crc (count words) and result (2 words)
+ * 4-byte aligned device memory.
+ * The host table is validated before anything is launched (radnet_crc32_plan_segments: RADNET_ERR_ARG or RADNET_ERR_UNSUPPORTED
+ * with its message; a null ctx, a null result or another null pointer that the counts do not excuse, or a misaligned table_dev,
+ * crc or result is RADNET_ERR_ARG too) and nothing is written then.
+ * Always three launches, whatever count and the data: (1) one workgroup sets result and sums the segments' span counts into their
+ * exclusive prefix, (2) one workgroup per span of the plan -- it finds its segment in the prefix by bisection, a lane sums one
+ * grain bitwise and weighs it, the xor over the lanes is the span's sum --, (3) one workgroup per segment joins its spans (beyond
+ * 256 of them by Horner's rule per lane), adds the tail, folds init in with x^(8 length), writes crc[k] and compares.  The unit
+ * of work is the span, so one segment of tens of MB and thousands of 8 KiB segments both fill the device.  No workgroup waits on
+ * another, every loop is bounded by a length or a count, and the only atomics are an integer min and an integer add on result.
+ * The prefix and the span sums stand in scratch that belongs to the context (plan.ws_bytes; it only grows, and a call that has to
+ * grow it waits for the context's stream first). */
+int radnet_crc32_segments(radnet_ctx* ctx, const uint8_t* buf, int64_t n, const radnet_crc32_segment* table_host,
+                          const radnet_crc32_segment* table_dev, int32_t count, uint32_t* crc, int32_t* result);
 /* Rectangles painted into a uint8 [h][w][3] device image (rows pitch_bytes apart) IN PLACE.  The contract is this package's own:
  *   the corners (x1, y1), (x2, y2) come in either order, as cv2.rectangle takes them, and are normalised to x1 <= x2, y1 <= y2;
  *   thickness < 0 (cv2.FILLED): pixel (x, y) is painted iff x1 <= x <= x2 and y1 <= y <= y2;

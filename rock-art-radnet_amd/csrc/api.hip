@@ -38,6 +38,7 @@ extern "C" void radnet_destroy(radnet_ctx* ctx) {
   if (ctx->tune_ev0) (void)hipEventDestroy(ctx->tune_ev0);
   if (ctx->tune_ev1) (void)hipEventDestroy(ctx->tune_ev1);
   if (ctx->aux) (void)hipFree(ctx->aux);
+  if (ctx->crc_ws) (void)hipFree(ctx->crc_ws);
   delete ctx;
 }
 

@@ -111,6 +111,9 @@ struct radnet_ctx {
   // deterministic = 1 (default; RADNET_DETERMINISTIC=0 turns it off): no floating-point atomics anywhere in a training step.
   int deterministic = 1;
   char* aux = nullptr;
+  // radnet_crc32_segments (crc32.hip): the span prefix and the span sums of a call.  Grows on demand, freed with the context.
+  void* crc_ws = nullptr;
+  uint64_t crc_ws_bytes = 0;
 };
 
 // layout of radnet_ctx::aux (bytes)

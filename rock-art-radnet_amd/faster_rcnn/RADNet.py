@@ -94,6 +94,7 @@ class RADNet():
     device_resident = True      # engine-backed models: keep tiles on the device between the stages (see _detect)
     device_tail = True          # ... and decode + per-class NMS + source-pixel coordinates too (see _tail_on_device)
     png_unfilter = "band"       # predict_from_path: "tiles" reconstructs the maps' adaptive-filter rows on all CUs (png.decode_device(unfilter=))
+    png_crc = "host"            # predict_from_path: "device" sums the maps' IDAT CRC-32s on the device (png.decode_device(crc=); needs a device png_inflate)
     png_inflate = "host"        # predict_from_path: "device" / "device-lz" inflate the maps' IDAT streams on the device (png.decode_device(inflate=))
     scan_tail = False           # ... and the merge of a scan's tiles: final_nms per image, NMS across images (see _scan_tail_on)
 
@@ -592,13 +593,16 @@ class RADNet():
         `device_resident` the decoded images stay on the device (get_image(..., to_host=False)); otherwise they are host arrays.
         `png_inflate = "device"` or `"device-lz"` is handed to get_image as inflate=: the same images, inflated on the device where
         the file allows (run-length streams, or any deflate stream).  `png_unfilter = "tiles"` is handed on as unfilter=: the same
-        images, their scanlines reconstructed by tiles."""
+        images, their scanlines reconstructed by tiles.  `png_crc = "device"` is handed on as crc=: the IDAT chunks' CRC-32 summed on
+        the device (with `png_inflate = "host"` that is png.decode_device's ValueError)."""
         from . import utils_io
         C = self.C
         to_host = not self._takes_device_images()
         how = dict(inflate=self.png_inflate)
         if self.png_unfilter != "band":
             how["unfilter"] = self.png_unfilter
+        if self.png_crc != "host":
+            how["crc"] = self.png_crc
         if C.use_img_type:
             images = [utils_io.get_image(img_path, [img_type], random_type=False, to_host=to_host, **how) for img_type in C.img_types]
         else:
@@ -735,7 +739,7 @@ class RADNet():
 
     LABELLED_MAPS = ("all_predictions.png", "other_predictions.png")      # predict.py:109-115 and 172-178
 
-    def write_predictions(self, dets, img, out_dir, labels=False, label_scale=3, deflate="host", huffman="dynamic"):
+    def write_predictions(self, dets, img, out_dir, labels=False, label_scale=3, deflate="host", huffman="dynamic", crc="host"):
         """What predict.py:96-181 writes for the detections of one scan, into out_dir: all_predictions.png (every detection in
         (255, 255, 255)), boat_predictions.png (boats, (28, 26, 228)), human_predictions.png (humans, (184, 126, 55)),
         other_predictions.png (every other class, (0, 127, 255)) -- each `img` (the map to annotate: a device image or a NumPy
@@ -745,7 +749,8 @@ class RADNet():
         own font at label_scale, not OpenCV's glyphs or metrics; unpinned against cv2); the boat and human maps stay outlines
         only.  The default leaves the labels out and writes the same bytes as before they existed.  deflate / huffman go to
         png.encode_device as they are (deflate="device": the four streams are compressed on the device and only the files' bytes
-        come down); the defaults are the host deflate and the bytes it always wrote.  Returns the five paths."""
+        come down; crc="device" with it: the IDAT chunks' CRC-32 is summed there too, the same bytes); the defaults are the host
+        deflate and the bytes it always wrote.  Returns the five paths."""
         import json
         import os
         from . import png
@@ -756,6 +761,8 @@ class RADNet():
         os.makedirs(out_dir, exist_ok=True)
         paths = []
         encoder = {} if (deflate, huffman) == ("host", "dynamic") else dict(deflate=deflate, huffman=huffman)
+        if crc != "host":
+            encoder["crc"] = crc
         for name, color, classes in self.PREDICTION_MAPS:
             if labels and name in self.LABELLED_MAPS:
                 drawn = self.draw_detections(img, dets, color=color, thickness=8, classes=classes, inplace=False, labels=True, label_scale=label_scale)

@@ -217,15 +217,37 @@ INFLATE_LZ_UNIT = np.dtype([(k, np.uint32) for k in ("start_bit", "end_bit", "ou
 INFLATE_LZ_CHAIN = INFLATE_CHAIN + ("a match that reaches in front of the stream",)      # RADNET_INFLATE_CHAIN_REACH; LEAD_MATCH is never met
 # container, geometry and the compressed IDAT stream of a file: staged is a pinned uint8 tensor that holds the n bytes of the zlib
 # stream and, behind them, the 768 bytes of the palette; expected is the length of the inflated stream the geometry asks for
-Compressed = collections.namedtuple("Compressed", "header palette passes bpp expected staged n")
+# crc_segments (parse_compressed(crc="device") alone, else None): the radnet_crc32_segment table of the IDAT chunks over the joined stream
+Compressed = collections.namedtuple("Compressed", "header palette passes bpp expected staged n crc_segments", defaults=(None,))
+CRC_SEGMENT = np.dtype([("offset", np.int64), ("length", np.int64), ("init", np.uint32), ("expect", np.uint32)])      # radnet_crc32_segment, 24 bytes
+CRC_MODES = ("host", "device")
 
 
-def parse_compressed(data):
+def _check_crc(crc):
+    if crc not in CRC_MODES:
+        raise ValueError("PNG: crc=%r (\"host\" or \"device\")" % (crc,))
+
+
+def crc_layout(n, count):
+    """Where parse_compressed(crc="device") puts what radnet_crc32_segments needs behind the n stream bytes and the 768 palette bytes
+    of the staging buffer: (table_at, sums_at, result_at, total bytes) -- the table of `count` segments 8-byte aligned, then the
+    count sums and the 2 result words the device writes into the uploaded copy."""
+    table_at = (n + 768 + 7) & ~7
+    sums_at = table_at + count * CRC_SEGMENT.itemsize
+    return table_at, sums_at, sums_at + 4 * count, sums_at + 4 * count + 8
+
+
+def parse_compressed(data, crc="host"):
     """The container walk of parse() WITHOUT the inflate: Compressed(header, palette, passes, bpp, expected, staged, n).  The IDAT
     payloads are joined directly into the pinned staging buffer (the palette rides behind them, as in decode_device); the chunk
     CRCs are summed on up to 8 host threads (fixed, like MANY_DEFAULT_WORKERS: one thread's zlib.crc32 over a 35 MB map would be
     the new floor).  Checks what parse() checks of the container, and the zlib header: CM 8, a window of at most 32 KiB, FCHECK, no
-    preset dictionary.  Raises ValueError naming the cause; decode_device(inflate="device") then lets the host path speak."""
+    preset dictionary.  Raises ValueError naming the cause; decode_device(inflate="device") then lets the host path speak.
+    crc="device": the sums of the IDAT chunks are left to radnet_crc32_segments -- every other chunk is still summed here -- and
+    the result carries crc_segments, one CRC_SEGMENT per IDAT chunk (zero-length ones too) over the JOINED stream: offset where the
+    chunk's payload starts in it, its length, init = zlib.crc32(b"IDAT"), expect = the chunk's CRC field.  The staging buffer
+    then holds the table behind the palette and room for the sums and the result (crc_layout)."""
+    _check_crc(crc)
     import concurrent.futures
     import torch
     view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, np.uint8)).cast("B")
@@ -262,7 +284,11 @@ def parse_compressed(data):
             return zlib.crc32(view[at + 4:end]) == int.from_bytes(view[end:end + 4], "big")
         return _crc32_threads(view[at + 8:end], zlib.crc32(kind), workers=workers) == int.from_bytes(view[end:end + 4], "big")
     n = sum(e - s for s, e in idat)
-    staged = torch.empty(n + 768, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    on_device = crc == "device"
+    small_file = sum(e - at for _, at, e in jobs) < 1 << 20
+    if on_device:
+        jobs = [j for j in jobs if j[0] != b"IDAT"]
+    staged = torch.empty(crc_layout(n, len(idat))[3] if on_device else n + 768, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
     host = staged.numpy()
     source = np.frombuffer(view, np.uint8)
     starts = np.concatenate([[0], np.cumsum([e - s for s, e in idat])]).astype(np.int64).tolist()
@@ -270,7 +296,7 @@ def parse_compressed(data):
     def join(k):
         s, e = idat[k]
         host[starts[k]:starts[k] + e - s] = source[s:e]
-    if sum(e - at for _, at, e in jobs) < 1 << 20:
+    if small_file:
         oks = {j: crc_ok(j) for j in jobs}
         for k in range(len(idat)):
             join(k)
@@ -296,11 +322,22 @@ def parse_compressed(data):
     if plte is not None:
         rgb = np.frombuffer(plte, np.uint8).reshape(-1, 3)
         palette[:rgb.shape[0]] = rgb[:, ::-1]
-    host[n:] = palette.reshape(-1)
+    host[n:n + 768] = palette.reshape(-1)
+    segments = None
+    if on_device:
+        segments = np.zeros(len(idat), CRC_SEGMENT)
+        segments["offset"] = starts[:-1]
+        segments["length"] = [e - s for s, e in idat]
+        segments["init"] = zlib.crc32(b"IDAT")
+        segments["expect"] = [int.from_bytes(view[e:e + 4], "big") for _, e in idat]
+        table_at, sums_at, _, total = crc_layout(n, len(idat))
+        host[n + 768:table_at] = 0
+        host[table_at:sums_at] = segments.view(np.uint8)
+        host[sums_at:total] = 0
     if n < 2 or host[0] & 15 != 8 or host[0] >> 4 > 7 or (int(host[0]) * 256 + int(host[1])) % 31 or host[1] & 32:
         raise ValueError("PNG: the IDAT stream has no zlib header the device inflate takes (deflate, a window of at most 32 KiB, FCHECK, no dictionary)")
     passes, expected = pass_geometry(header)
-    return Compressed(header, palette, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8), expected, staged, n)
+    return Compressed(header, palette, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8), expected, staged, n, segments)
 
 
 def _lap(report, name):
@@ -468,17 +505,18 @@ def _checked_stream(comp, ctx, report, stream):
     return stream
 
 
-def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False):
+def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_device=False):
     """decode_device's device inflate (lz: the one for any stream): the image, or None when the host path has to take the file
     (report["reason"]).  tiles: unfilter="tiles" -- segments of at most 64 rows go to radnet_png_unfilter_segments_u8, all longer ones
-    to radnet_png_unfilter_tiles_u8, whether or not the segments spread the passes."""
+    to radnet_png_unfilter_tiles_u8, whether or not the segments spread the passes.  crc_device: crc="device" -- the IDAT chunks' sums
+    come from radnet_crc32_segments, and a mismatch is the reason "crc: IDAT chunk k"."""
     import ctypes
     import torch
     from radnet_hip import lib as L
     from . import augmentation_device as AD
     _lap(report, "_skip")
     try:
-        comp = parse_compressed(data)
+        comp = parse_compressed(data, crc="device") if crc_device else parse_compressed(data)
     except ValueError as e:
         report["reason"] = "container: %s" % e
         return None
@@ -486,7 +524,24 @@ def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False):
     with AD.feed_stream(ctx) as (ctx, side):
         dev = comp.staged.cuda(non_blocking=True)
         _lap(report, "upload_ms")
+        if crc_device:
+            # the IDAT sums right behind the upload: the table stands behind the palette, the sums and the result go into the uploaded
+            # copy, and the 8 bytes of the result are on their way down before the search starts -- its first download delivers them
+            count = len(comp.crc_segments)
+            table_at, sums_at, result_at, _ = crc_layout(comp.n, count)
+            _launch(report, ctx, "radnet_crc32_segments", dev.data_ptr(), comp.n, comp.staged.data_ptr() + table_at, dev.data_ptr() + table_at, count,
+                    dev.data_ptr() + sums_at, dev.data_ptr() + result_at)
+            verdict = torch.empty(2, dtype=torch.int32, pin_memory=True)
+            verdict.copy_(dev[result_at:result_at + 8].view(torch.int32), non_blocking=True)
         stream = (_inflate_device_lz if lz else _inflate_device)(comp, dev, ctx, report)
+        if crc_device:
+            if stream is None:
+                torch.cuda.current_stream().synchronize()      # a refusal may come before the first download; the host path is next anyway
+            first_bad, n_bad = (int(v) for v in verdict)
+            if n_bad:
+                report["reason"] = "crc: IDAT chunk %d" % first_bad
+                return None
+            report["crc"] = "device"
         if stream is None:
             return None
         column = report.pop("column")
@@ -541,7 +596,7 @@ def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False):
     return AD.hand_over(out, side)
 
 
-def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band"):
+def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band", crc="host"):
     """The decoded image as a uint8 [H][W][3] (B, G, R) cuda tensor: parse, ONE pinned upload of the inflated stream (the palette
     rides behind it), then reconstruction and expansion per pass.  ctx: a radnet context whose stream is torch's current one;
     None = the calling thread's default context, on a BackgroundFeed worker thread on that thread's own stream.
@@ -567,12 +622,20 @@ def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band"):
     table of one entry per pass rides behind the palette in the staging buffer); on the device-inflate paths the segments of at most
     64 rows keep radnet_png_unfilter_segments_u8 and all longer ones go to the tiles entry.  The bytes are those of "band".  In this
     mode alone the report's reconstruction is "tiles" or "segments+tiles" (segments of both kinds) and it carries sweeps, the
-    launches of the tiles call: the most sweeps radnet_png_plan_tiles gives for one of its segments."""
+    launches of the tiles call: the most sweeps radnet_png_plan_tiles gives for one of its segments.
+    crc="device" (opt-in; needs a device inflate, with inflate="host" it is a ValueError): the CRC-32 of the IDAT chunks, the bulk
+    of the file, is summed on the uploaded stream by radnet_crc32_segments (csrc/crc32.hip) right behind the upload instead of on
+    host threads in front of it; the other chunks are summed on the host as before.  The verdict comes down with the search's
+    candidates.  A mismatch sends the file to the host path (reason "crc: IDAT chunk k"), which raises the default's ValueError.
+    In this mode alone the report carries crc: "device" when the sums were checked there, "host" when the host path took the file."""
     import torch
     from . import augmentation_device as AD
     if inflate not in ("host", "device", "device-lz"):
         raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
     _check_unfilter(unfilter)
+    _check_crc(crc)
+    if crc == "device" and inflate == "host":
+        raise ValueError("PNG: crc=\"device\" sums the uploaded IDAT stream and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\"")
     tiles = unfilter == "tiles"
     report = {} if report is None else report
     report.update(path="host", reason=None, candidates=0, false_candidates=0, units=0, blocks=0, reconstruction=None)
@@ -580,11 +643,15 @@ def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band"):
     report.update(lz)
     if tiles:
         report["sweeps"] = 0
+    if crc == "device":
+        report["crc"] = "host"
     if inflate != "host":
-        out = _decode_inflated_on_device(data, ctx, report, lz=bool(lz), tiles=tiles)
+        out = _decode_inflated_on_device(data, ctx, report, lz=bool(lz), tiles=tiles, crc_device=crc == "device")
         if out is not None:
             return out
         report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None, **lz)
+        if crc == "device":
+            report["crc"] = "host"
         report.pop("column", None)
     img = parse(data)
     n = len(img.stream)
@@ -898,6 +965,30 @@ def crc32_combine(crc1, crc2, len2):
     return crc1 ^ crc2
 
 
+def crc32_device(t, value=0, ctx=None):
+    """zlib.crc32(bytes of t, value) of a contiguous uint8 cuda tensor, summed where it stands: radnet_crc32_segments with one
+    segment (csrc/crc32.hip), one small upload (the table) and one small download (the sum).  ctx as for decode_device."""
+    import torch
+    from . import augmentation_device as AD
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+        raise TypeError("PNG: crc32_device takes a contiguous uint8 cuda tensor")
+    if not 0 <= int(value) <= 0xffffffff:
+        raise ValueError("PNG: a running CRC-32 of %d" % int(value))
+    n = int(t.numel())
+    table = np.zeros(1, CRC_SEGMENT)
+    table[0] = (0, n, int(value), 0)
+    producer = torch.cuda.current_stream()
+    with AD.feed_stream(ctx) as (ctx, side):
+        if side is not None:
+            side.wait_stream(producer)
+            t.record_stream(side)
+        work = torch.zeros(CRC_SEGMENT.itemsize + 16, dtype=torch.uint8, device="cuda")      # the table, the sum, the result
+        work[:CRC_SEGMENT.itemsize].copy_(torch.from_numpy(table.view(np.uint8)))
+        at = work.data_ptr() + CRC_SEGMENT.itemsize
+        ctx.call("radnet_crc32_segments", t.data_ptr() if n else None, n, table.ctypes.data, work, 1, at, at + 4)
+        return int(work[CRC_SEGMENT.itemsize:CRC_SEGMENT.itemsize + 4].cpu().numpy().view(np.uint32)[0])
+
+
 def _crc32_threads(view, crc, workers=MANY_DEFAULT_WORKERS, least=1 << 20):
     """zlib.crc32(view, crc) with the buffer cut into at most `workers` ranges of at least `least` bytes, each summed on a host thread
     (zlib releases the GIL) and the sums joined by crc32_combine."""
@@ -914,11 +1005,13 @@ def _crc32_threads(view, crc, workers=MANY_DEFAULT_WORKERS, least=1 << 20):
     return crc
 
 
-def assemble_pieces(packed, adler, width, height, color_type):
+def assemble_pieces(packed, adler, width, height, color_type, idat_crc=None):
     """The PNG file round a deflate stream made elsewhere (8 bits per sample, colour type 0 or 2, not interlaced): signature, IHDR,
     one IDAT holding the zlib header 78 01, `packed` (raw deflate blocks, the last one final) and the Adler-32 `adler` of what they
     inflate to, IEND.  Nothing is inflated or checked here but the sizes.  `packed` is read twice and copied once: the chunk's
-    CRC-32 is summed over ranges of it on up to 8 host threads, then the file is joined."""
+    CRC-32 is summed over ranges of it on up to 8 host threads, then the file is joined.  idat_crc: the running value behind
+    `packed`, zlib.crc32(b"IDAT" + the zlib header + packed), summed elsewhere (deflate_device(crc="device")); then only the 4 Adler
+    bytes are added here and `packed` is read once.  The caller answers for it: a wrong value gives a file with a wrong CRC."""
     width, height, adler = int(width), int(height), int(adler)
     if color_type not in (0, 2):
         raise ValueError("PNG: the writer takes colour type 0 or 2, not %r" % (color_type,))
@@ -930,16 +1023,22 @@ def assemble_pieces(packed, adler, width, height, color_type):
     if len(view) + 6 > IDAT_MAX:
         raise ValueError("PNG: an IDAT chunk of %d bytes (at most 2^31 - 1)" % (len(view) + 6))
     head, tail = b"IDAT" + _zlib_header(1), struct.pack(">I", adler)
-    crc = zlib.crc32(tail, _crc32_threads(view, zlib.crc32(head)))
+    if idat_crc is not None and not 0 <= int(idat_crc) <= 0xffffffff:
+        raise ValueError("PNG: a running CRC-32 of %d" % int(idat_crc))
+    crc = zlib.crc32(tail, _crc32_threads(view, zlib.crc32(head)) if idat_crc is None else int(idat_crc))
     ihdr = struct.pack(">IIBBBBB", width, height, 8, color_type, 0, 0, 0)
     return b"".join([SIGNATURE, _chunk_bytes(b"IHDR", ihdr), struct.pack(">I", len(view) + 6), head, view, tail, struct.pack(">I", crc), _chunk_bytes(b"IEND")])
 
 
-def deflate_device(dev, ctx, huffman="dynamic"):
+def deflate_device(dev, ctx, huffman="dynamic", crc="host"):
     """(packed, adler): the raw deflate blocks (bytes-like, in a pinned buffer) and the Adler-32 of the uint8 cuda tensor `dev` of n
     bytes, on the radnet context ctx whose stream is current: scan, ONE small download (286 counts, the Adler parts), the code
-    (huffman_code, or fixed_code for huffman="fixed"), emit, pack, the 8 bytes of the total, ONE download of exactly that many."""
+    (huffman_code, or fixed_code for huffman="fixed"), emit, pack, the 8 bytes of the total, ONE download of exactly that many.
+    crc="device": (packed, adler, idat_crc) -- the packed bytes are summed where they stand (radnet_crc32_segments, one segment)
+    and idat_crc, what assemble_pieces takes, is zlib.crc32(b"IDAT" + the zlib header + packed); its 4 bytes come down in the
+    download of the packed bytes."""
     import torch
+    _check_crc(crc)
     from radnet_hip import lib as L
     n = int(dev.numel())
     chunk = _deflate_constant("RADNET_DEFLATE_CHUNK")
@@ -964,7 +1063,8 @@ def deflate_device(dev, ctx, huffman="dynamic"):
     counts = hist.astype(np.int64)
     token_bits = int((counts * hc.code["length"].astype(np.int64)).sum()) + int(counts[257:].sum()) * (5 + hc.dist_nbits)
     out_cap = (token_bits + 7) // 8 + chunks * ((hc.header_nbits + 7) // 8 + 16)
-    out = torch.empty(out_cap, dtype=torch.uint8, device="cuda")
+    room = 8 + CRC_SEGMENT.itemsize + 12 if crc == "device" else 0      # behind the packed bytes: padding, one segment, its sum, the result
+    out = torch.empty(out_cap + room, dtype=torch.uint8, device="cuda")
     total = torch.empty(1, dtype=torch.int64, device="cuda")
     ctx.call("radnet_deflate_pack", pieces, piece_cap, sizes, chunks, out, out_cap, total)
     total_host = torch.empty(1, dtype=torch.int64, pin_memory=True)
@@ -973,16 +1073,29 @@ def deflate_device(dev, ctx, huffman="dynamic"):
     size = int(total_host[0])
     if size > out_cap:
         raise RuntimeError("PNG: the deflate pieces hold %d bytes, more than the %d their counts allow" % (size, out_cap))
-    packed = torch.empty(size, dtype=torch.uint8, pin_memory=True)
-    packed.copy_(out[:size], non_blocking=True)
+    if crc != "device":
+        packed = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        packed.copy_(out[:size], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return packed.numpy(), adler
+    # the chunk's sum, as far as the packed bytes: one segment over out[:size] that starts from the sum of the type and the zlib header.
+    # The table goes up, and the sum comes down, in the buffer of the packed bytes: no launch and no wait but radnet_crc32_segments's own
+    table_at = (size + 7) & ~7
+    sum_at = table_at + CRC_SEGMENT.itemsize
+    table = torch.zeros(CRC_SEGMENT.itemsize, dtype=torch.uint8, pin_memory=True)
+    table.numpy().view(CRC_SEGMENT)[0] = (0, size, zlib.crc32(b"IDAT" + _zlib_header(1)), 0)
+    out[table_at:sum_at].copy_(table, non_blocking=True)
+    ctx.call("radnet_crc32_segments", out, size, table.data_ptr(), out.data_ptr() + table_at, 1, out.data_ptr() + sum_at, out.data_ptr() + sum_at + 4)
+    packed = torch.empty(sum_at + 4, dtype=torch.uint8, pin_memory=True)
+    packed.copy_(out[:sum_at + 4], non_blocking=True)
     torch.cuda.current_stream().synchronize()
-    return packed.numpy(), adler
+    return packed.numpy()[:size], adler, int(packed.numpy()[sum_at:sum_at + 4].view(np.uint32)[0])
 
 
 HOST_DEFLATE_DEFAULTS = dict(level=1, strategy="rle", workers=None, chunk_bytes=1 << 20)
 
 
-def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None, chunk_bytes=1 << 20, ctx=None, deflate="host", huffman="dynamic"):
+def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None, chunk_bytes=1 << 20, ctx=None, deflate="host", huffman="dynamic", crc="host"):
     """The PNG file (bytes) of a contiguous uint8 cuda tensor [H][W][3] (B, G, R; written as 8-bit RGB) or [H][W] (8-bit grey); a
     NumPy array is uploaded first -- there is no CPU filter path, as there is no CPU reconstruction.  filter: "adaptive" (per row
     the type with the smallest sum of |signed residual|, the lowest on a tie), a fixed type 0..4 or its name.  One
@@ -992,7 +1105,10 @@ def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None,
     deflate="device": the stream stays on the device and is deflated there (deflate_device: run-length tokens, one Huffman code per
     image for huffman="dynamic", RFC 1951's fixed code for huffman="fixed"); only the compressed bytes come down and
     assemble_pieces wraps them.  The file inflates to the same stream as the host path's but its bytes differ.  level, strategy,
-    workers and chunk_bytes belong to the host deflate: any of them off its default together with deflate="device" is a ValueError."""
+    workers and chunk_bytes belong to the host deflate: any of them off its default together with deflate="device" is a ValueError.
+    crc="device" (opt-in; needs deflate="device", with deflate="host" it is a ValueError): the IDAT chunk's CRC-32 is summed over the
+    packed bytes on the device (csrc/crc32.hip) and comes down with them; the host adds the 4 Adler bytes.  The file's bytes are
+    those of crc="host"."""
     import torch
     from . import augmentation_device as AD
     mode = _filter_mode(filter)
@@ -1000,6 +1116,9 @@ def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None,
         raise ValueError("PNG: deflate=%r (\"host\" or \"device\")" % (deflate,))
     if huffman not in ("dynamic", "fixed"):
         raise ValueError("PNG: huffman=%r (\"dynamic\" or \"fixed\")" % (huffman,))
+    _check_crc(crc)
+    if crc == "device" and deflate != "device":
+        raise ValueError("PNG: crc=\"device\" sums the bytes deflate=\"device\" leaves on the device and cannot be set with deflate=\"host\"")
     if deflate == "device":
         given = dict(level=level, strategy=strategy, workers=workers, chunk_bytes=chunk_bytes)
         off = sorted(k for k, v in given.items() if v != HOST_DEFLATE_DEFAULTS[k])
@@ -1019,6 +1138,9 @@ def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None,
         dev = torch.empty(n, dtype=torch.uint8, device="cuda")
         ctx.call("radnet_png_filter_rows_u8", img, h, w, channels, w * channels, mode, dev)
         if deflate == "device":
+            if crc == "device":
+                packed, adler, idat_crc = deflate_device(dev, ctx, huffman, crc="device")
+                return assemble_pieces(packed, adler, w, h, 2 if channels == 3 else 0, idat_crc=idat_crc)
             packed, adler = deflate_device(dev, ctx, huffman)
             return assemble_pieces(packed, adler, w, h, 2 if channels == 3 else 0)
         staged = torch.empty(n, dtype=torch.uint8, pin_memory=True)

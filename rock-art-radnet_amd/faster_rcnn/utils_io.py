@@ -19,13 +19,14 @@ def image_path(img_path, img_type):
     return os.path.join(*parts)
 
 
-def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, inflate="host", unfilter="band"):
+def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, inflate="host", unfilter="band", crc="host"):
     """utils.get_image, draw for draw: types[0], or with random_type one rng.choice(types, 1, p=probs)[0] where the first type has
     probability 0.5 (up to three types) or 0.3 and the others share the rest.  Returns the uint8 BGR HWC image as a NumPy array,
     or with to_host=False as a cuda tensor (nothing is downloaded).  inflate="device" inflates the file's IDAT stream on the device
     (png.decode_device: run-length streams; anything else takes the host path as before), inflate="device-lz" does so for a stream
     with matches at any distance; another value is png.decode_device's ValueError.  unfilter="tiles" reconstructs the scanlines by
-    tiles on all CUs (png.decode_device: the same image); another value than "band" or "tiles" is its ValueError too."""
+    tiles on all CUs (png.decode_device: the same image); another value than "band" or "tiles" is its ValueError too.  crc="device"
+    sums the IDAT chunks' CRC-32 on the device (png.decode_device: needs a device inflate; with inflate="host" its ValueError)."""
     img_type = types[0]
     if random_type:
         first_prob = 0.3
@@ -34,9 +35,11 @@ def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, i
         probs = [first_prob] + [(1.0 - first_prob) / (len(types) - 1) for i in range(len(types) - 1)]
         img_type = rng.choice(types, 1, p=probs)[0]
     buf = np.fromfile(image_path(img_path, img_type), np.uint8)
-    if inflate == "host" and unfilter == "band":
+    if inflate == "host" and unfilter == "band" and crc == "host":
         return png.imdecode_color(buf) if to_host else png.decode_device(buf)
     tiles = {} if unfilter == "band" else dict(unfilter=unfilter)      # the default call is the one it was
+    if crc != "host":
+        tiles["crc"] = crc
     img = png.decode_device(buf, inflate=inflate, **tiles)
     return img.cpu().numpy() if to_host else img
 
@@ -62,11 +65,18 @@ class DeviceImageLoader:
     prefetch() fills the cache ahead of the calls, many files per decode (png.decode_device_many): the types of a scan, the next
     images of a feed.  The cache holds one decoder's images: with decode= set and decode_many= not, prefetch decodes through
     decode, file by file.  unfilter="tiles" is handed to the default decoders of both (png.decode_device and decode_many's
-    unfilter=); a decoder of the caller's is called as it is."""
+    unfilter=); a decoder of the caller's is called as it is.  inflate= and crc= are handed to the default png.decode_device of
+    __call__ in the same way (crc="device" needs inflate="device" or "device-lz": png.decode_device's ValueError, raised here);
+    decode_many keeps the host parse and takes neither."""
 
-    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band"):
+    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band", inflate="host", crc="host"):
         png._check_unfilter(unfilter)
-        self.unfilter = unfilter
+        png._check_crc(crc)
+        if inflate not in ("host", "device", "device-lz"):
+            raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
+        if crc == "device" and inflate == "host":
+            raise ValueError("PNG: crc=\"device\" sums the uploaded IDAT stream and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\"")
+        self.unfilter, self.inflate, self.crc = unfilter, inflate, crc
         self.cache_bytes = int(cache_bytes)
         self.decode = decode                       # (file bytes as uint8 array) -> image; default: png.decode_device
         # (list of file bytes) -> list of images, for prefetch; default: png.decode_device_many, or `decode` on each file if that is set
@@ -146,7 +156,12 @@ class DeviceImageLoader:
         if self.decode is not None:
             img = self.decode(buf)
         else:
-            img = png.decode_device(buf) if self.unfilter == "band" else png.decode_device(buf, unfilter=self.unfilter)
+            how = {} if self.unfilter == "band" else dict(unfilter=self.unfilter)      # the default call is the one it was
+            if self.inflate != "host":
+                how["inflate"] = self.inflate
+            if self.crc != "host":
+                how["crc"] = self.crc
+            img = png.decode_device(buf, **how)
         self._insert(key, img)
         return img
 
@@ -154,7 +169,7 @@ class DeviceImageLoader:
 def imwrite(path, img, **kw):
     """cv2.imwrite(path, img) for a PNG map: png.encode_device(img, **kw) written to `path` (a cuda tensor stays where it is; only
     the filtered stream comes down; with deflate="device" only the compressed bytes do, huffman="dynamic" or "fixed": see
-    png.encode_device).  Only the .png suffix is accepted; returns True like cv2.imwrite."""
+    png.encode_device; crc="device" beside deflate="device" sums the IDAT chunk's CRC-32 there too).  Only the .png suffix is accepted; returns True like cv2.imwrite."""
     path = os.fspath(path)
     if os.path.splitext(path)[1].lower() != ".png":
         raise ValueError("imwrite: only PNG files are written, not %r" % (os.path.splitext(path)[1] or path,))

@@ -322,6 +322,10 @@ def load_library():
         "radnet_png_tiles_on_sweep": (C.c_int, [i32, i32, i32, i32, vp, i32]),
         "radnet_png_unfilter_tiles_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32]),
         "radnet_png_unfilter_tiles_width_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, i32]),
+        "radnet_crc32_shift": (C.c_uint32, [i64]),
+        "radnet_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, i64]),
+        "radnet_crc32_plan_segments": (C.c_int, [vp, i32, i64, i32, vp, C.POINTER(i32), C.c_char_p, i32]),
+        "radnet_crc32_segments": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp]),
         "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
         "radnet_draw_list_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
         "radnet_draw_glyph_rows": (C.c_int, [i32, vp]),
@@ -403,6 +407,28 @@ def heat_check(table, pool_len, h, w, count=None):
     rc = load_library().radnet_heat_check(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(pool_len), int(h),
                                           int(w), C.byref(bad), msg, len(msg))
     return rc, bad.value, msg.value.decode()
+
+
+def crc32_shift(length):
+    """radnet_crc32_shift (host only): x^(8 * length) mod the CRC-32 polynomial, as a reflected register."""
+    return int(load_library().radnet_crc32_shift(int(length)))
+
+
+def crc32_combine(crc1, crc2, len2):
+    """radnet_crc32_combine (host only): zlib's crc32_combine."""
+    return int(load_library().radnet_crc32_combine(int(crc1) & 0xffffffff, int(crc2) & 0xffffffff, int(len2)))
+
+
+def crc32_plan_segments(table, n, misalign=0, count=None):
+    """radnet_crc32_plan_segments (host only, no context, no device) on a table of radnet_crc32_segment rows -- a NumPy array of 24
+    bytes per entry, or None for a null table -- for a buffer of n bytes that stands `misalign` bytes behind a 16-byte boundary:
+    (rc, spans, ws_bytes, index of the bad entry or -1, the message).  count defaults to the table's length."""
+    import numpy as np
+    rows = np.zeros((0, 24), np.uint8) if table is None else np.ascontiguousarray(table).view(np.uint8).reshape(-1, 24)
+    plan, bad, msg = (C.c_int64 * 2)(-1, -1), C.c_int32(-2), C.create_string_buffer(256)
+    rc = load_library().radnet_crc32_plan_segments(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(n),
+                                                   int(misalign), C.cast(plan, C.c_void_p), C.byref(bad), msg, len(msg))
+    return rc, plan[0], plan[1], bad.value, msg.value.decode()
 
 
 def scan_merge_check(table, pool_words, slot_rows, count=None):
