@@ -21,6 +21,13 @@ source position, pointer jumping flattens the sources, a gather copies each byte
 decode_device(unfilter="tiles"), and decode_device_many likewise, reconstructs rows of Up / Average / Paeth type, which allow no
 segment cut, on all CUs (csrc/png_tiles.hip): tiles of 64 rows by TILE_PIXELS pixels, one launch per sweep of independent tiles.
 
+Every leg of the read side goes through the same few statements: the container's structure is _chunks (parse sums each chunk's
+CRC as the walk yields it, parse_compressed takes the whole walk first); where the streams, the palettes, a table and the device's
+sums stand in the ONE uploaded buffer is staging_layout; the segments of a pass are _plan_pass (plan_segments over the scanlines,
+the device-inflate path over the downloaded filter-type column); which table entries go to radnet_png_unfilter_segments_u8 and
+which to radnet_png_unfilter_tiles_u8 is decided by each caller and launched by _reconstruct; the expansion is _expand_passes;
+the legal values of inflate / unfilter / crc are check_modes.
+
 Formats: colour types 0, 2, 3, 4, 6 with the bit depths 1, 2, 4, 8, 16 the PNG specification allows for each; non-interlaced and
 Adam7.  Output rules: grey is replicated to three channels, depths 1 / 2 / 4 scaled by 255 / 85 / 17; palette entries are looked up
 (an index beyond the PLTE length gives 0); alpha channels and tRNS are dropped, not blended; 16-bit samples keep their high byte
@@ -43,6 +50,7 @@ not importable in this build, so no test compares against it (tests/png_cases.py
 of the rules above).  A file this module refuses raises ValueError naming the cause, where cv2.imdecode returns None.
 """
 import collections
+import functools
 import os
 import struct
 import zlib
@@ -61,24 +69,20 @@ Pass = collections.namedtuple("Pass", "x0 y0 dx dy pass_w pass_h rowbytes stream
 Image = collections.namedtuple("Image", "header palette stream passes bpp")
 
 
-def _unfilter_constant(name):
+def _constant(name):
+    """An integer #define of include/radnet_hip.h, the header the kernels are compiled with."""
     from radnet_hip.lib import header_constant
     return header_constant(name)
 
 
 # band and chunk of radnet_png_unfilter_u8 (the seams its tests straddle), read from the header the kernel is compiled with
-UNFILTER_BAND_ROWS = _unfilter_constant("RADNET_PNG_UNFILTER_BAND_ROWS")
-UNFILTER_CHUNK_BYTES = _unfilter_constant("RADNET_PNG_UNFILTER_CHUNK_BYTES")
+UNFILTER_BAND_ROWS = _constant("RADNET_PNG_UNFILTER_BAND_ROWS")
+UNFILTER_CHUNK_BYTES = _constant("RADNET_PNG_UNFILTER_CHUNK_BYTES")
 # the tile of radnet_png_unfilter_tiles_u8 (unfilter="tiles"): rows of a band, pixels of a column block
-TILE_ROWS = _unfilter_constant("RADNET_PNG_TILE_ROWS")
-TILE_PIXELS = _unfilter_constant("RADNET_PNG_TILE_PIXELS")
+TILE_ROWS = _constant("RADNET_PNG_TILE_ROWS")
+TILE_PIXELS = _constant("RADNET_PNG_TILE_PIXELS")
 UNFILTER_MODES = ("band", "tiles")
 TilePlan = collections.namedtuple("TilePlan", "bands blocks sweeps tile_rows tile_pixels")      # radnet_png_tile_plan
-
-
-def _check_unfilter(unfilter):
-    if unfilter not in UNFILTER_MODES:
-        raise ValueError("PNG: unfilter=%r (\"band\" or \"tiles\")" % (unfilter,))
 
 
 def plan_tiles(rows, rowbytes, bpp):
@@ -106,18 +110,50 @@ def tiles_on_sweep(rows, rowbytes, bpp, sweep):
     return [tuple(p) for p in pairs.tolist()]
 
 
-def _chunk(data, pos):
-    """(type, payload, position after the chunk) of the chunk at `pos`; checks its length and CRC."""
-    if pos + 12 > len(data):
-        raise ValueError("PNG: truncated file (chunk header at byte %d)" % pos)
-    length, kind = struct.unpack(">I4s", data[pos:pos + 8])
-    end = pos + 8 + length
-    if length > 0x7fffffff or end + 4 > len(data):
-        raise ValueError("PNG: truncated file (%r chunk of %d bytes at byte %d)" % (kind, length, pos))
-    payload = data[pos + 8:end]
-    if zlib.crc32(payload, zlib.crc32(kind)) != struct.unpack(">I", data[end:end + 4])[0]:
-        raise ValueError("PNG: CRC mismatch in the %r chunk at byte %d" % (kind, pos))
-    return kind, payload, end + 4
+def _chunks(view):
+    """The chunk walk behind IHDR, the one statement of the container's structure: (type, payload start, payload end) of every chunk
+    from byte 33 of the file's bytes up to IEND; the type stands in the 4 bytes in front of the payload, the CRC in the 4 behind it.
+    Raises ValueError for a truncated chunk header or chunk, a second IHDR, a PLTE size and a file that ends without IEND.  A chunk
+    is yielded once it is whole, and what is wrong inside it is raised when the walk moves on: a consumer that sums the CRC in its
+    loop body (parse) reports a mismatch in front of that, and in front of any fault of a later chunk; one that takes the whole walk
+    first (parse_compressed) reports the structure first."""
+    pos = 33
+    while pos < len(view):
+        if pos + 12 > len(view):
+            raise ValueError("PNG: truncated file (chunk header at byte %d)" % pos)
+        length, kind = struct.unpack(">I4s", view[pos:pos + 8])
+        end = pos + 8 + length
+        if length > 0x7fffffff or end + 4 > len(view):
+            raise ValueError("PNG: truncated file (%r chunk of %d bytes at byte %d)" % (kind, length, pos))
+        yield kind, pos + 8, end
+        if kind == b"IHDR":
+            raise ValueError("PNG: a second IHDR chunk")
+        if kind == b"PLTE" and (length % 3 or not 3 <= length <= 768):
+            raise ValueError("PNG: PLTE chunk of %d bytes" % length)
+        if kind == b"IEND":
+            return
+        pos = end + 4
+    raise ValueError("PNG: truncated file (no IEND chunk)")
+
+
+def _crc_ok(view, start, end):
+    """Whether the CRC field behind the payload [start, end) is the sum of the chunk's type and payload, which stand side by side."""
+    return zlib.crc32(view[start - 4:end]) == int.from_bytes(view[end:end + 4], "big")
+
+
+def _crc_mismatch(kind, start):
+    return ValueError("PNG: CRC mismatch in the %r chunk at byte %d" % (kind, start - 8))
+
+
+def _palette(header, plte):
+    """The uint8 [256][3] palette in B, G, R order of a PLTE payload (None: the file has none), zero beyond its entries."""
+    if header.color_type == 3 and plte is None:
+        raise ValueError("PNG: palette (PLTE) missing for colour type 3")
+    palette = np.zeros((256, 3), np.uint8)
+    if plte is not None:
+        rgb = np.frombuffer(plte, np.uint8).reshape(-1, 3)
+        palette[:rgb.shape[0]] = rgb[:, ::-1]
+    return palette
 
 
 def _header(data):
@@ -125,8 +161,9 @@ def _header(data):
         raise ValueError("PNG: bad signature")
     if len(data) < 33 or data[8:16] != b"\x00\x00\x00\rIHDR":
         raise ValueError("PNG: IHDR missing or not the first chunk")
-    _, ihdr, _ = _chunk(data, 8)
-    width, height, depth, color, compression, filt, interlace = struct.unpack(">IIBBBBB", ihdr)
+    if not _crc_ok(data, 16, 29):
+        raise _crc_mismatch(b"IHDR", 16)
+    width, height, depth, color, compression, filt, interlace = struct.unpack(">IIBBBBB", data[16:29])
     if width == 0 or height == 0 or width > 0x7fffffff or height > 0x7fffffff:
         raise ValueError("PNG: illegal size %d x %d" % (width, height))
     if color not in LEGAL_DEPTHS or depth not in LEGAL_DEPTHS[color]:
@@ -167,28 +204,15 @@ def parse(data):
     over-long inflated stream and a filter-type byte above 4.  Data after IEND is ignored."""
     data = bytes(data)
     header = _header(data)
-    pos, idat, plte, ended = 33, [], None, False
-    while pos < len(data):
-        kind, payload, pos = _chunk(data, pos)
-        if kind == b"IHDR":
-            raise ValueError("PNG: a second IHDR chunk")
+    view, idat, plte = memoryview(data), [], None
+    for kind, start, end in _chunks(view):
+        if not _crc_ok(view, start, end):
+            raise _crc_mismatch(kind, start)
         if kind == b"PLTE":
-            if len(payload) % 3 or not 3 <= len(payload) <= 768:
-                raise ValueError("PNG: PLTE chunk of %d bytes" % len(payload))
-            plte = payload
+            plte = view[start:end]
         elif kind == b"IDAT":
-            idat.append(payload)
-        elif kind == b"IEND":
-            ended = True
-            break
-    if not ended:
-        raise ValueError("PNG: truncated file (no IEND chunk)")
-    if header.color_type == 3 and plte is None:
-        raise ValueError("PNG: palette (PLTE) missing for colour type 3")
-    palette = np.zeros((256, 3), np.uint8)
-    if plte is not None:
-        rgb = np.frombuffer(plte, np.uint8).reshape(-1, 3)
-        palette[:rgb.shape[0]] = rgb[:, ::-1]
+            idat.append(view[start:end])
+    palette = _palette(header, plte)
     passes, expected = pass_geometry(header)
     inflater = zlib.decompressobj()
     try:
@@ -220,7 +244,9 @@ INFLATE_LZ_CHAIN = INFLATE_CHAIN + ("a match that reaches in front of the stream
 # crc_segments (parse_compressed(crc="device") alone, else None): the radnet_crc32_segment table of the IDAT chunks over the joined stream
 Compressed = collections.namedtuple("Compressed", "header palette passes bpp expected staged n crc_segments", defaults=(None,))
 CRC_SEGMENT = np.dtype([("offset", np.int64), ("length", np.int64), ("init", np.uint32), ("expect", np.uint32)])      # radnet_crc32_segment, 24 bytes
+INFLATE_MODES = ("host", "device", "device-lz")
 CRC_MODES = ("host", "device")
+Staging = collections.namedtuple("Staging", "palettes pad table sums result total")      # staging_layout
 
 
 def _check_crc(crc):
@@ -228,13 +254,44 @@ def _check_crc(crc):
         raise ValueError("PNG: crc=%r (\"host\" or \"device\")" % (crc,))
 
 
+def check_modes(inflate="host", unfilter="band", crc="host"):
+    """The legal values of the modes of decode_device, and of whoever hands them on to it (decode_device_many,
+    utils_io.DeviceImageLoader), stated once: ValueError for an inflate, unfilter or crc that is none of them, and for crc="device"
+    without a device inflate."""
+    if inflate not in INFLATE_MODES:
+        raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
+    if unfilter not in UNFILTER_MODES:
+        raise ValueError("PNG: unfilter=%r (\"band\" or \"tiles\")" % (unfilter,))
+    _check_crc(crc)
+    if crc == "device" and inflate == "host":
+        raise ValueError("PNG: crc=\"device\" sums the uploaded IDAT stream and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\"")
+
+
+def staging_layout(n, palettes=1, record=0, count=0, sums=False):
+    """Where everything stands in the ONE pinned buffer a decode uploads, as Staging(palettes, pad, table, sums, result, total) byte
+    offsets: the n bytes of the stream(s), `palettes` palettes of 768 bytes, the pad up to the next multiple of 8, a table of
+    `count` records of `record` bytes (SEGMENT or CRC_SEGMENT) and, with sums, the `count` sums and the 2 result words the device
+    writes into the uploaded copy (radnet_crc32_segments).  Without a table (record 0) nothing is padded and nothing follows the
+    palettes."""
+    pad = n + 768 * palettes
+    table = (pad + 7) & ~7 if record else pad
+    result = table + record * count + (4 * count if sums else 0)
+    return Staging(n, pad, table, table + record * count, result, result + (8 if sums else 0))
+
+
+def _stage_table(host, at, table):
+    """`table` into the staging buffer `host` (uint8) at the layout `at`, the pad in front of it and the room behind it zeroed."""
+    host[at.pad:at.table] = 0
+    host[at.table:at.sums] = table.view(np.uint8)
+    host[at.sums:at.total] = 0
+
+
 def crc_layout(n, count):
     """Where parse_compressed(crc="device") puts what radnet_crc32_segments needs behind the n stream bytes and the 768 palette bytes
     of the staging buffer: (table_at, sums_at, result_at, total bytes) -- the table of `count` segments 8-byte aligned, then the
     count sums and the 2 result words the device writes into the uploaded copy."""
-    table_at = (n + 768 + 7) & ~7
-    sums_at = table_at + count * CRC_SEGMENT.itemsize
-    return table_at, sums_at, sums_at + 4 * count, sums_at + 4 * count + 8
+    at = staging_layout(n, 1, CRC_SEGMENT.itemsize, count, sums=True)
+    return at.table, at.sums, at.result, at.total
 
 
 def parse_compressed(data, crc="host"):
@@ -252,43 +309,27 @@ def parse_compressed(data, crc="host"):
     import torch
     view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, np.uint8)).cast("B")
     header = _header(bytes(view[:33]))
-    pos, idat, plte, ended, jobs = 33, [], None, False, []
-    while pos < len(view):
-        if pos + 12 > len(view):
-            raise ValueError("PNG: truncated file (chunk header at byte %d)" % pos)
-        length, kind = struct.unpack(">I4s", view[pos:pos + 8])
-        end = pos + 8 + length
-        if length > 0x7fffffff or end + 4 > len(view):
-            raise ValueError("PNG: truncated file (%r chunk of %d bytes at byte %d)" % (kind, length, pos))
-        jobs.append((kind, pos, end))
-        if kind == b"IHDR":
-            raise ValueError("PNG: a second IHDR chunk")
+    idat, plte, jobs = [], None, []
+    for kind, start, end in _chunks(view):      # the whole walk: the structure is judged before any sum
+        jobs.append((kind, start - 8, end))
         if kind == b"PLTE":
-            if length % 3 or not 3 <= length <= 768:
-                raise ValueError("PNG: PLTE chunk of %d bytes" % length)
-            plte = bytes(view[pos + 8:end])
+            plte = view[start:end]
         elif kind == b"IDAT":
-            idat.append((pos + 8, end))
-        pos = end + 4
-        if kind == b"IEND":
-            ended = True
-            break
-    if not ended:
-        raise ValueError("PNG: truncated file (no IEND chunk)")
-    if header.color_type == 3 and plte is None:
-        raise ValueError("PNG: palette (PLTE) missing for colour type 3")
+            idat.append((start, end))
+    palette = _palette(header, plte)
 
     def crc_ok(job, workers=1):
-        kind, at, end = job                        # the CRC covers the type and the payload, which stand side by side: one call per chunk
+        kind, at, end = job
         if workers == 1:
-            return zlib.crc32(view[at + 4:end]) == int.from_bytes(view[end:end + 4], "big")
+            return _crc_ok(view, at + 8, end)      # one call per chunk
         return _crc32_threads(view[at + 8:end], zlib.crc32(kind), workers=workers) == int.from_bytes(view[end:end + 4], "big")
     n = sum(e - s for s, e in idat)
     on_device = crc == "device"
     small_file = sum(e - at for _, at, e in jobs) < 1 << 20
     if on_device:
         jobs = [j for j in jobs if j[0] != b"IDAT"]
-    staged = torch.empty(crc_layout(n, len(idat))[3] if on_device else n + 768, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    lay = staging_layout(n, 1, CRC_SEGMENT.itemsize, len(idat), sums=True) if on_device else staging_layout(n)
+    staged = torch.empty(lay.total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
     host = staged.numpy()
     source = np.frombuffer(view, np.uint8)
     starts = np.concatenate([[0], np.cumsum([e - s for s, e in idat])]).astype(np.int64).tolist()
@@ -317,12 +358,8 @@ def parse_compressed(data, crc="host"):
             list(pool.map(lambda g: [join(k) for k in range(g, len(idat), MANY_DEFAULT_WORKERS)], range(min(len(idat), MANY_DEFAULT_WORKERS))))
     for kind, at, end in jobs:
         if not oks[(kind, at, end)]:
-            raise ValueError("PNG: CRC mismatch in the %r chunk at byte %d" % (kind, at))
-    palette = np.zeros((256, 3), np.uint8)
-    if plte is not None:
-        rgb = np.frombuffer(plte, np.uint8).reshape(-1, 3)
-        palette[:rgb.shape[0]] = rgb[:, ::-1]
-    host[n:n + 768] = palette.reshape(-1)
+            raise _crc_mismatch(kind, at + 8)
+    host[lay.palettes:lay.pad] = palette.reshape(-1)
     segments = None
     if on_device:
         segments = np.zeros(len(idat), CRC_SEGMENT)
@@ -330,10 +367,7 @@ def parse_compressed(data, crc="host"):
         segments["length"] = [e - s for s, e in idat]
         segments["init"] = zlib.crc32(b"IDAT")
         segments["expect"] = [int.from_bytes(view[e:e + 4], "big") for _, e in idat]
-        table_at, sums_at, _, total = crc_layout(n, len(idat))
-        host[n + 768:table_at] = 0
-        host[table_at:sums_at] = segments.view(np.uint8)
-        host[sums_at:total] = 0
+        _stage_table(host, lay, segments)
     if n < 2 or host[0] & 15 != 8 or host[0] >> 4 > 7 or (int(host[0]) * 256 + int(host[1])) % 31 or host[1] & 32:
         raise ValueError("PNG: the IDAT stream has no zlib header the device inflate takes (deflate, a window of at most 32 KiB, FCHECK, no dictionary)")
     passes, expected = pass_geometry(header)
@@ -485,7 +519,7 @@ def _checked_stream(comp, ctx, report, stream):
     reason "adler"; the filter-type column comes back as report["column"].  One sync."""
     import torch
     n, expected = comp.n, comp.expected
-    chunks = -(-expected // _deflate_constant("RADNET_DEFLATE_CHUNK"))
+    chunks = -(-expected // _constant("RADNET_DEFLATE_CHUNK"))
     rows = sum(p.pass_h for p in comp.passes)
     tail = torch.zeros(DEFLATE_SYMBOLS * 4 + chunks * 16 + rows, dtype=torch.uint8, device="cuda")      # counts (not used), Adler parts, column
     _launch(report, ctx, "radnet_deflate_rle_scan_u8", stream, expected, tail, tail.data_ptr() + DEFLATE_SYMBOLS * 4)
@@ -505,14 +539,72 @@ def _checked_stream(comp, ctx, report, stream):
     return stream
 
 
+SEGMENT = np.dtype([("offset", np.int64), ("rows", np.int32), ("rowbytes", np.int32)])      # radnet_png_segment, 16 bytes
+SEGMENT_TARGET_ROWS = _constant("RADNET_PNG_SEGMENT_TARGET_ROWS")      # the planners' target_rows = 0
+# the `rows <= 64` split in radnet_png_unfilter_segments_u8 (csrc/png.hip): segments of at most this many rows go out in its one-wave
+# launch and the longer ones in its band-sized launch, each over the index range that holds its kind, so a table stands short-first
+# and neither range holds workgroups of the other kind.  Not TILE_ROWS, the height of a tile, though both are 64 today.
+SEGMENT_ONE_WAVE_ROWS = 64
+
+
+def _plan_pass(entry, pointer, p, offset, target_rows=0):
+    """The SEGMENT table of the pass `p` whose first scanline stands at `offset` of the buffer to reconstruct, from the planner
+    `entry`: "radnet_png_plan_segments" reads the pass's scanlines at `pointer`, "radnet_png_plan_segments_column" its column of
+    filter types.  ValueError when the planner refuses."""
+    import ctypes
+    from radnet_hip import lib as L
+    target = target_rows or SEGMENT_TARGET_ROWS
+    cap = min(p.pass_h, 2 * (p.pass_h // target) + 2)      # two neighbours of the greedy rule together exceed target_rows
+    table = np.zeros(cap, SEGMENT)
+    n = getattr(L.load_library(), entry)(pointer, offset, p.pass_h, p.rowbytes, target_rows, table.ctypes.data_as(ctypes.c_void_p), cap)
+    if n < 0:
+        raise ValueError("PNG: %s failed (%d) on the pass at (%d, %d)" % (entry, n, p.x0, p.y0))
+    return table[:n]
+
+
+def _reconstruct(call, table_host, table_dev, base, length, groups):
+    """The reconstruction launches over one short-first-sorted SEGMENT table (table_host, table_dev: its address on the host and in
+    the uploaded copy) whose offsets count from `base`, a device buffer of `length` bytes.  groups: (bpp, first, short, count) --
+    of the `count` table entries from `first` on, which share `bpp`, the first `short` go to radnet_png_unfilter_segments_u8 and
+    the others to radnet_png_unfilter_tiles_u8; an empty range launches nothing.  What `short` is, the caller decides.
+    call(name, *args): ctx.call, or _launch with its report."""
+    for bpp, first, short, count in groups:
+        for entry, at, n in (("radnet_png_unfilter_segments_u8", first, short), ("radnet_png_unfilter_tiles_u8", first + short, count - short)):
+            if n:
+                call(entry, base, length, table_host + SEGMENT.itemsize * at, table_dev + SEGMENT.itemsize * at, n, bpp)
+
+
+def _unfilter_passes(call, passes, base, bpp):
+    """One radnet_png_unfilter_u8 per pass, in place on the stream at `base`: one workgroup walks the pass."""
+    for p in passes:
+        call("radnet_png_unfilter_u8", base + p.stream_offset, p.pass_h, p.rowbytes, bpp)
+
+
+def _expand_passes(call, header, passes, base, palette, out):
+    """One radnet_png_expand_bgr_u8 per pass: the reconstructed scanlines at `base` into their pixels of the image `out`."""
+    for p in passes:
+        call("radnet_png_expand_bgr_u8", base + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, header.color_type, header.bit_depth, palette, out,
+             header.height, header.width, p.y0, p.x0, p.dy, p.dx)
+
+
+def _report_host_path(report, inflate, unfilter, crc):
+    """What the report says of a file the host path decodes, with the keys of the active modes; reason and candidates are not
+    touched: after a refusal they say why, and what the device search had found."""
+    report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None)
+    if inflate == "device-lz":
+        report.update(rounds=0, far_units=0)
+    if unfilter == "tiles":
+        report["sweeps"] = 0
+    if crc == "device":
+        report["crc"] = "host"
+
+
 def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_device=False):
     """decode_device's device inflate (lz: the one for any stream): the image, or None when the host path has to take the file
     (report["reason"]).  tiles: unfilter="tiles" -- segments of at most 64 rows go to radnet_png_unfilter_segments_u8, all longer ones
     to radnet_png_unfilter_tiles_u8, whether or not the segments spread the passes.  crc_device: crc="device" -- the IDAT chunks' sums
     come from radnet_crc32_segments, and a mismatch is the reason "crc: IDAT chunk k"."""
-    import ctypes
     import torch
-    from radnet_hip import lib as L
     from . import augmentation_device as AD
     _lap(report, "_skip")
     try:
@@ -551,47 +643,33 @@ def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_dev
         h = comp.header
         out = torch.empty((h.height, h.width, 3), dtype=torch.uint8, device="cuda")
         base, palette = stream.data_ptr(), dev.data_ptr() + comp.n
+        call = functools.partial(_launch, report, ctx)
         # segments when they spread a pass over the device: the longest is at most half its pass
-        lib, tables, row0, spread = L.load_library(), [], 0, True
-        target = L.header_constant("RADNET_PNG_SEGMENT_TARGET_ROWS")
+        tables, row0, spread = [], 0, True
         for p in comp.passes:
-            cap = min(p.pass_h, 2 * (p.pass_h // target) + 2)
-            table = np.zeros(cap, SEGMENT)
             col = np.ascontiguousarray(column[row0:row0 + p.pass_h])
-            got = lib.radnet_png_plan_segments_column(col.ctypes.data, p.stream_offset, p.pass_h, p.rowbytes, 0, table.ctypes.data_as(ctypes.c_void_p), cap)
-            if got < 0:
-                raise ValueError("PNG: radnet_png_plan_segments_column failed (%d) on the pass at (%d, %d)" % (got, p.x0, p.y0))
-            tables.append(table[:got])
-            spread = spread and 2 * int(table[:got]["rows"].max()) <= p.pass_h
+            tables.append(_plan_pass("radnet_png_plan_segments_column", col.ctypes.data, p, p.stream_offset))
+            spread = spread and 2 * int(tables[-1]["rows"].max()) <= p.pass_h
             row0 += p.pass_h
-        if tiles:
+        if tiles or spread:
             table = np.concatenate(tables)
-            table = table[np.argsort(table["rows"] > TILE_ROWS, kind="stable")]
-            short = int((table["rows"] <= TILE_ROWS).sum())
+            # with tiles the segments above TILE_ROWS rows leave for the tiles call; without, every segment keeps the segments call
+            split = TILE_ROWS if tiles else SEGMENT_ONE_WAVE_ROWS
+            table = table[np.argsort(table["rows"] > split, kind="stable")]
+            short = int((table["rows"] <= split).sum()) if tiles else len(table)
             table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
             _lap(report, "plan_segments_ms")
-            if short:
-                _launch(report, ctx, "radnet_png_unfilter_segments_u8", base, comp.expected, table.ctypes.data, table_dev, short, comp.bpp)
-            if short < len(table):
-                _launch(report, ctx, "radnet_png_unfilter_tiles_u8", base, comp.expected, table.ctypes.data + SEGMENT.itemsize * short,
-                        table_dev.data_ptr() + SEGMENT.itemsize * short, len(table) - short, comp.bpp)
-            report["reconstruction"] = "segments+tiles" if short else "tiles"
-            report["sweeps"] = max([plan_tiles(int(t["rows"]), int(t["rowbytes"]), comp.bpp).sweeps for t in table[short:]], default=0)
-        elif spread:
-            table = np.concatenate(tables)
-            table = table[np.argsort(table["rows"] > 64, kind="stable")]
-            table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
-            _lap(report, "plan_segments_ms")
-            _launch(report, ctx, "radnet_png_unfilter_segments_u8", base, comp.expected, table.ctypes.data, table_dev, len(table), comp.bpp)
-            report["reconstruction"] = "segments"
+            _reconstruct(call, table.ctypes.data, table_dev.data_ptr(), base, comp.expected, [(comp.bpp, 0, short, len(table))])
+            if tiles:
+                report["reconstruction"] = "segments+tiles" if short else "tiles"
+                report["sweeps"] = max([plan_tiles(int(t["rows"]), int(t["rowbytes"]), comp.bpp).sweeps for t in table[short:]], default=0)
+            else:
+                report["reconstruction"] = "segments"
         else:
             _lap(report, "plan_segments_ms")
-            for p in comp.passes:
-                _launch(report, ctx, "radnet_png_unfilter_u8", base + p.stream_offset, p.pass_h, p.rowbytes, comp.bpp)
+            _unfilter_passes(call, comp.passes, base, comp.bpp)
             report["reconstruction"] = "unfilter"
-        for p in comp.passes:
-            _launch(report, ctx, "radnet_png_expand_bgr_u8", base + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, h.color_type, h.bit_depth, palette, out,
-                     h.height, h.width, p.y0, p.x0, p.dy, p.dx)
+        _expand_passes(call, comp.header, comp.passes, base, palette, out)
     report["path"] = "device"
     return AD.hand_over(out, side)
 
@@ -630,57 +708,44 @@ def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band", 
     In this mode alone the report carries crc: "device" when the sums were checked there, "host" when the host path took the file."""
     import torch
     from . import augmentation_device as AD
-    if inflate not in ("host", "device", "device-lz"):
-        raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
-    _check_unfilter(unfilter)
-    _check_crc(crc)
-    if crc == "device" and inflate == "host":
-        raise ValueError("PNG: crc=\"device\" sums the uploaded IDAT stream and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\"")
+    check_modes(inflate, unfilter, crc)
     tiles = unfilter == "tiles"
     report = {} if report is None else report
-    report.update(path="host", reason=None, candidates=0, false_candidates=0, units=0, blocks=0, reconstruction=None)
-    lz = dict(rounds=0, far_units=0) if inflate == "device-lz" else {}
-    report.update(lz)
-    if tiles:
-        report["sweeps"] = 0
-    if crc == "device":
-        report["crc"] = "host"
+    report.update(reason=None, candidates=0)
+    _report_host_path(report, inflate, unfilter, crc)
     if inflate != "host":
-        out = _decode_inflated_on_device(data, ctx, report, lz=bool(lz), tiles=tiles, crc_device=crc == "device")
+        out = _decode_inflated_on_device(data, ctx, report, lz=inflate == "device-lz", tiles=tiles, crc_device=crc == "device")
         if out is not None:
             return out
-        report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None, **lz)
-        if crc == "device":
-            report["crc"] = "host"
+        _report_host_path(report, inflate, unfilter, crc)
         report.pop("column", None)
     img = parse(data)
     n = len(img.stream)
     with AD.feed_stream(ctx) as (ctx, side):
-        seg_at = (n + 768 + 7) & ~7                        # the tiles table: 8-byte aligned behind the palette
-        table = np.array([(p.stream_offset, p.pass_h, p.rowbytes) for p in img.passes], SEGMENT) if tiles else np.zeros(0, SEGMENT)
-        staged = torch.empty(seg_at + table.nbytes if tiles else n + 768, dtype=torch.uint8, pin_memory=True)
+        at = staging_layout(n, 1, SEGMENT.itemsize, len(img.passes)) if tiles else staging_layout(n)
+        staged = torch.empty(at.total, dtype=torch.uint8, pin_memory=True)
         host = staged.numpy()
         host[:n] = np.frombuffer(img.stream, np.uint8)
-        host[n:n + 768] = img.palette.reshape(-1)
-        if tiles:
-            host[n + 768:seg_at] = 0
-            host[seg_at:] = table.view(np.uint8)
+        host[at.palettes:at.pad] = img.palette.reshape(-1)
+        if tiles:      # a table of one entry per pass rides behind the palette
+            table = np.array([(p.stream_offset, p.pass_h, p.rowbytes) for p in img.passes], SEGMENT)
+            _stage_table(host, at, table)
         dev = staged.cuda(non_blocking=True)
         out = torch.empty((img.header.height, img.header.width, 3), dtype=torch.uint8, device="cuda")
         base = dev.data_ptr()
         if tiles:
-            ctx.call("radnet_png_unfilter_tiles_u8", base, n, host.ctypes.data + seg_at, base + seg_at, len(table), img.bpp)
+            # every pass goes to the tiles call, whatever its height
+            _reconstruct(ctx.call, host.ctypes.data + at.table, base + at.table, base, n, [(img.bpp, 0, 0, len(table))])
             report["reconstruction"] = "tiles"
             report["sweeps"] = max(plan_tiles(p.pass_h, p.rowbytes, img.bpp).sweeps for p in img.passes)
-        for p in img.passes:
-            if not tiles:
-                ctx.call("radnet_png_unfilter_u8", base + p.stream_offset, p.pass_h, p.rowbytes, img.bpp)
-            ctx.call("radnet_png_expand_bgr_u8", base + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, img.header.color_type, img.header.bit_depth,
-                     base + n, out, img.header.height, img.header.width, p.y0, p.x0, p.dy, p.dx)
+            _expand_passes(ctx.call, img.header, img.passes, base, base + at.palettes, out)
+        else:
+            for p in img.passes:      # the launches interleave, pass by pass
+                _unfilter_passes(ctx.call, [p], base, img.bpp)
+                _expand_passes(ctx.call, img.header, [p], base, base + at.palettes, out)
     return AD.hand_over(out, side)
 
 
-SEGMENT = np.dtype([("offset", np.int64), ("rows", np.int32), ("rowbytes", np.int32)])      # radnet_png_segment, 16 bytes
 MANY_DEFAULT_WORKERS, MANY_MAX_WORKERS = 8, 16      # host threads of decode_device_many; fixed, not read off the machine
 
 
@@ -695,21 +760,9 @@ def _parse_indexed(item):
 def plan_segments(img, base_offset=0, target_rows=0):
     """The segment table of one parsed image whose stream will stand at base_offset of the uploaded buffer: a structured array
     (offset int64, rows int32, rowbytes int32; radnet_png_segment) from radnet_png_plan_segments, pass after pass."""
-    import ctypes
-    from radnet_hip import lib as L
-    lib = L.load_library()
-    column = np.frombuffer(img.stream, np.uint8)
-    target = target_rows or L.header_constant("RADNET_PNG_SEGMENT_TARGET_ROWS")
-    tables = []
-    for p in img.passes:
-        cap = min(p.pass_h, 2 * (p.pass_h // target) + 2)      # two neighbours of the greedy rule together exceed target_rows
-        table = np.zeros(cap, SEGMENT)
-        n = lib.radnet_png_plan_segments(column.ctypes.data + p.stream_offset, base_offset + p.stream_offset, p.pass_h, p.rowbytes, target_rows,
-                                         table.ctypes.data_as(ctypes.c_void_p), cap)
-        if n < 0:
-            raise ValueError("PNG: radnet_png_plan_segments failed (%d) on the pass at (%d, %d)" % (n, p.x0, p.y0))
-        tables.append(table[:n])
-    return np.concatenate(tables)
+    stream = np.frombuffer(img.stream, np.uint8)
+    return np.concatenate([_plan_pass("radnet_png_plan_segments", stream.ctypes.data + p.stream_offset, p, base_offset + p.stream_offset, target_rows)
+                           for p in img.passes])
 
 
 def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
@@ -723,7 +776,7 @@ def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
     import concurrent.futures
     import torch
     from . import augmentation_device as AD
-    _check_unfilter(unfilter)
+    check_modes(unfilter=unfilter)
     datas = list(datas)
     if not datas:
         return []
@@ -743,38 +796,33 @@ def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
         # one table: grouped by bpp, inside a group the segments of at most 64 rows first (the one-wave launch), then the long ones
         bpps = np.concatenate([np.full(len(t), im.bpp, np.int64) for t, im in zip(tables, imgs)])
         table = np.concatenate(tables)
-        order = np.lexsort((table["rows"] > 64, bpps))
+        order = np.lexsort((table["rows"] > SEGMENT_ONE_WAVE_ROWS, bpps))
         table, bpps = table[order], bpps[order]
-        pal_at = n_streams
-        seg_at = (pal_at + 768 * len(imgs) + 7) & ~7
-        staged = torch.empty(seg_at + table.nbytes, dtype=torch.uint8, pin_memory=True)
+        at = staging_layout(n_streams, len(imgs), SEGMENT.itemsize, len(table))
+        staged = torch.empty(at.total, dtype=torch.uint8, pin_memory=True)
         host = staged.numpy()
 
         def stage(k):
             host[starts[k]:starts[k + 1]] = np.frombuffer(imgs[k].stream, np.uint8)
-            host[pal_at + 768 * k:pal_at + 768 * (k + 1)] = imgs[k].palette.reshape(-1)
+            host[at.palettes + 768 * k:at.palettes + 768 * (k + 1)] = imgs[k].palette.reshape(-1)
         list(pool.map(stage, range(len(imgs))))
     finally:
         pool.shutdown(wait=True)                                          # the host threads are done before any device work
-    host[pal_at + 768 * len(imgs):seg_at] = 0
-    host[seg_at:] = table.view(np.uint8)
+    _stage_table(host, at, table)
+    groups, first = [], 0
+    for bpp, n in zip(*np.unique(bpps, return_counts=True)):
+        # with tiles the long segments, which stand behind the short ones of their bpp, leave the segments call for the tiles call
+        short = int((table["rows"][first:first + int(n)] <= TILE_ROWS).sum()) if unfilter == "tiles" else int(n)
+        groups.append((int(bpp), first, short, int(n)))
+        first += int(n)
     with AD.feed_stream(ctx) as (ctx, side):
         dev = staged.cuda(non_blocking=True)
         base = dev.data_ptr()
-        first = 0
-        for bpp, n in zip(*np.unique(bpps, return_counts=True)):
-            # with tiles the long segments, which stand behind the short ones of their bpp, leave the segments call for the tiles call
-            short = int((table["rows"][first:first + int(n)] <= TILE_ROWS).sum()) if unfilter == "tiles" else int(n)
-            for entry, at, count in (("radnet_png_unfilter_segments_u8", first, short), ("radnet_png_unfilter_tiles_u8", first + short, int(n) - short)):
-                if count:
-                    ctx.call(entry, base, n_streams, host.ctypes.data + seg_at + 16 * at, base + seg_at + 16 * at, count, int(bpp))
-            first += int(n)
+        _reconstruct(ctx.call, host.ctypes.data + at.table, base + at.table, base, n_streams, groups)
         outs = []
         for k, im in enumerate(imgs):
             out = torch.empty((im.header.height, im.header.width, 3), dtype=torch.uint8, device="cuda")
-            for p in im.passes:
-                ctx.call("radnet_png_expand_bgr_u8", base + int(starts[k]) + p.stream_offset, p.pass_h, p.pass_w, p.rowbytes, im.header.color_type,
-                         im.header.bit_depth, base + pal_at + 768 * k, out, im.header.height, im.header.width, p.y0, p.x0, p.dy, p.dx)
+            _expand_passes(ctx.call, im.header, im.passes, base + int(starts[k]), base + at.palettes + 768 * k, out)
             outs.append(out)
     return [AD.hand_over(out, side) for out in outs]
 
@@ -884,11 +932,6 @@ DEFLATE_SYMBOLS = 286
 HuffmanCode = collections.namedtuple("HuffmanCode", "code header header_nbits dist_nbits")      # the arguments of radnet_deflate_rle_emit_u8
 
 
-def _deflate_constant(name):
-    from radnet_hip.lib import header_constant
-    return header_constant(name)
-
-
 def huffman_code(hist):
     """The literal/length code of an image from the 286 counts of radnet_deflate_rle_scan_u8 and the dynamic block header that
     describes it (radnet_deflate_build_code: host only, no device): HuffmanCode(code, header, header_nbits, dist_nbits) with code a
@@ -900,7 +943,7 @@ def huffman_code(hist):
     if hist.size != DEFLATE_SYMBOLS:
         raise ValueError("PNG: a histogram of %d counts (the literal/length alphabet has %d)" % (hist.size, DEFLATE_SYMBOLS))
     code = np.zeros(DEFLATE_SYMBOLS, DEFLATE_CODE)
-    header = np.zeros(_deflate_constant("RADNET_DEFLATE_HEADER_MAX_BITS") // 8, np.uint8)
+    header = np.zeros(_constant("RADNET_DEFLATE_HEADER_MAX_BITS") // 8, np.uint8)
     nbits = ctypes.c_int32(0)
     rc = L.load_library().radnet_deflate_build_code(hist.ctypes.data, code.ctypes.data, header.ctypes.data, header.size, ctypes.byref(nbits))
     if rc != 0:
@@ -921,7 +964,7 @@ def fixed_code():
 def adler32_of_parts(parts, n):
     """The Adler-32 of a stream of n bytes from radnet_deflate_rle_scan_u8's parts, per chunk of len bytes at offset s the sums
     S1 = sum(byte[i]) and S2 = sum((len - i) * byte[i]):  a = 1 + sum(S1),  b = n + sum(S2 + (n - s - len) * S1),  both mod 65521."""
-    chunk = _deflate_constant("RADNET_DEFLATE_CHUNK")
+    chunk = _constant("RADNET_DEFLATE_CHUNK")
     a, b = 1, int(n)
     for c, (s1, s2) in enumerate(np.asarray(parts, np.uint64).reshape(-1, 2).tolist()):
         start = c * chunk
@@ -1041,7 +1084,7 @@ def deflate_device(dev, ctx, huffman="dynamic", crc="host"):
     _check_crc(crc)
     from radnet_hip import lib as L
     n = int(dev.numel())
-    chunk = _deflate_constant("RADNET_DEFLATE_CHUNK")
+    chunk = _constant("RADNET_DEFLATE_CHUNK")
     chunks = -(-n // chunk)
     scan = torch.zeros(DEFLATE_SYMBOLS * 4 + chunks * 16, dtype=torch.uint8, device="cuda")      # 1144 bytes: the parts stand 8-aligned
     ctx.call("radnet_deflate_rle_scan_u8", dev, n, scan, scan.data_ptr() + DEFLATE_SYMBOLS * 4)

@@ -70,12 +70,7 @@ class DeviceImageLoader:
     decode_many keeps the host parse and takes neither."""
 
     def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band", inflate="host", crc="host"):
-        png._check_unfilter(unfilter)
-        png._check_crc(crc)
-        if inflate not in ("host", "device", "device-lz"):
-            raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
-        if crc == "device" and inflate == "host":
-            raise ValueError("PNG: crc=\"device\" sums the uploaded IDAT stream and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\"")
+        png.check_modes(inflate, unfilter, crc)
         self.unfilter, self.inflate, self.crc = unfilter, inflate, crc
         self.cache_bytes = int(cache_bytes)
         self.decode = decode                       # (file bytes as uint8 array) -> image; default: png.decode_device

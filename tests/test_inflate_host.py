@@ -225,3 +225,42 @@ def test_the_native_chunk_crcs_equal_zlib():
     with pytest.raises(ValueError) as b:
         png.parse_compressed(bytes(bad))
     assert str(a.value) == str(b.value) and "CRC" in str(a.value)
+
+
+def test_two_faults_in_one_file_are_reported_in_each_parsers_order():
+    """parse() sums a chunk's CRC before it looks at the next chunk; parse_compressed() judges the whole structure before any sum."""
+    import png_cases as K
+    from faster_rcnn import png
+    enc = K.encode(K.draw(np.random.RandomState(5), 6, 7, 3, 8), 3, 8, palette=np.arange(30).reshape(10, 3))
+    plte, idat = enc.data.index(b"PLTE") - 4, enc.data.index(b"IDAT") - 4
+    head, pal, z, end = enc.data[:33], enc.data[plte:idat], enc.data[idat:-12], enc.data[-12:]
+    assert head + pal + z + end == enc.data and (plte, idat, len(z)) == (33, 75, 71)
+    bad = lambda chunk: chunk[:-1] + bytes([chunk[-1] ^ 1])      # noqa: E731  (the CRC field)
+    for what, data, from_parse, from_parse_compressed in (
+            ("a bad CRC in chunk 2, chunk 3 truncated", head + bad(pal) + z[:-3],
+             "PNG: CRC mismatch in the b'PLTE' chunk at byte 33", "PNG: truncated file (b'IDAT' chunk of 59 bytes at byte 75)"),
+            ("a second IHDR after a bad-CRC PLTE", head + bad(pal) + head[8:] + z + end,
+             "PNG: CRC mismatch in the b'PLTE' chunk at byte 33", "PNG: a second IHDR chunk"),
+            ("no IEND after a bad-CRC IDAT", head + pal + bad(z),
+             "PNG: CRC mismatch in the b'IDAT' chunk at byte 75", "PNG: truncated file (no IEND chunk)")):
+        for parser, want in ((png.parse, from_parse), (png.parse_compressed, from_parse_compressed)):
+            with pytest.raises(ValueError) as e:
+                parser(data)
+            assert str(e.value) == want, (what, parser.__name__)
+
+
+def test_the_modes_are_stated_once():
+    from faster_rcnn import png, utils_io
+    needs_inflate = "PNG: crc=\"device\" sums the uploaded IDAT stream and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\""
+    for kw, want in ((dict(inflate="gpu"), "PNG: inflate='gpu' (\"host\", \"device\" or \"device-lz\")"),
+                     (dict(unfilter="rows"), "PNG: unfilter='rows' (\"band\" or \"tiles\")"),
+                     (dict(crc="gpu"), "PNG: crc='gpu' (\"host\" or \"device\")"),
+                     (dict(inflate="host", crc="device"), needs_inflate)):
+        for taker in (png.check_modes, utils_io.DeviceImageLoader, lambda **k: png.decode_device(b"", **k)):
+            with pytest.raises(ValueError) as e:
+                taker(**kw)
+            assert str(e.value) == want, kw
+    for inflate, unfilter, crc in (("host", "band", "host"), ("device", "tiles", "device"), ("device-lz", "band", "device"), ("device-lz", "tiles", "host")):
+        png.check_modes(inflate, unfilter, crc)
+        utils_io.DeviceImageLoader(inflate=inflate, unfilter=unfilter, crc=crc)
+    png.check_modes()
