@@ -94,7 +94,7 @@ class TrainStep:
         self.defer_head_update = (world_size > 1) if defer_head_update is None else bool(defer_head_update)
         self._init_native_comm()
         self._head_pending = None        # (work handle, images in the global batch) of the exchange in flight
-        self._head_done = {}             # buffer set -> event: end of the head phase that last read its feature map
+        self._head_done = {}             # buffer set -> event: end of the head phase that last read its feature map (or of a dropped prefetch)
         self._head_last = None           # event: end of the last head phase enqueued on the head lane
         self._lane_mode = False          # True between the first pipelined call and flush()
         self._queue = collections.deque()    # states of the announced batches, enqueued ahead (step(next_batch=...))
@@ -310,6 +310,20 @@ class TrainStep:
         self._slots += 1
         return (self._slots - 1) % self.NBUF
 
+    def _drop_prepared(self, q, keep):
+        """Forget the states of q behind the first `keep`: batches that were announced and prepared (phase A + base forward on a prefetch
+        lane) and will not come after all.  They hold the buffer sets handed out last, and nothing reads what was prepared in them: the sets
+        go back, newest first, so that a run whose announcements change never has more than NBUF sets in use -- handing out fresh ones
+        instead would wrap around onto the set of the batch whose classifier phase is still to come.  The next launch into such a set
+        may go to another prefetch lane (a pair and a lone batch deal their sets differently), so the dropped launch becomes the set's
+        last user: it ran behind the classifier phase recorded there before."""
+        while len(q) > keep:
+            st = q.pop()
+            if st["slot"] == (self._slots - 1) % self.NBUF:
+                self._slots -= 1
+            if st.get("done") is not None:
+                self._head_done[st["slot"]] = st["done"]
+
     def _launch_a(self, batch, slot):
         """Device half of phase A (anchor labelling + async copy of the label maps) and the weight-independent part of
         phase B (upload, frozen base forward) of every image of `batch`, into buffer set `slot`."""
@@ -468,7 +482,7 @@ class TrainStep:
                 # the announced batch's RPN phase -- an optimizer step -- has already been applied: dropping it silently would
                 # train the RPN on a batch whose classifier step never happens
                 raise RuntimeError("TrainStep.step: the previous call announced a different next batch (pass the same object)")
-            q.clear()                                  # not the announced batch: forward passes prepared for it are dropped
+            self._drop_prepared(q, 0)                  # not the announced batch: forward passes prepared for it are dropped
             slot = self._next_slot()
             if lanes:
                 k = slot % getattr(eng, "n_side_lanes", 1)
@@ -477,6 +491,7 @@ class TrainStep:
                     st = self._launch_a(batch, slot)
                     st["done"] = eng.mark()
             else:
+                after(self._head_done.get(slot))       # one lane: only a prefetch that was dropped after flush() is still unordered
                 st = self._launch_a(batch, slot)
         if "roi" not in st:                            # first step of a run, or the previous call was not pipelined
             after(st.get("done"))
@@ -484,8 +499,7 @@ class TrainStep:
             self._rpn_phase(st, ntot, mark)
         for j in range(len(q)):                        # announced batches must be the ones prepared, in order
             if j >= len(ahead) or q[j]["batch"] is not ahead[j]:
-                while len(q) > j:
-                    q.pop()
+                self._drop_prepared(q, j)
                 break
         if pipelined:
             j = len(q)

@@ -5,7 +5,6 @@ TrainStep must drop such an image before any optimizer effect, keep going -- in 
 ANNOUNCED batch in the middle of step(i), whose own head phase must still run -- and, data-parallel, still join every
 collective (zeros) so the peers do not hang.  Exercised with the recording stand-in engine of test_dp_deferred (no
 kernels), world 1 in-process and world 2 over gloo."""
-import contextlib
 import os
 import types
 
@@ -14,30 +13,14 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from lane_audit import LaneClocks, audit, describe
 from test_dp_deferred import FakeEngine, _free_port
 
 FAIL_WIDTH = 13
 
 
-class LaneFakeEngine(FakeEngine):
-    """FakeEngine + the lane interface, so TrainStep runs its pipelined schedule; a sample whose source width is FAIL_WIDTH
-    makes anchor_targets_finish raise the reference's KeyError."""
-    n_side_lanes = 1
-
-    def __init__(self, rank, bucketed=False):
-        super().__init__(rank, bucketed)
-        self.ctx = types.SimpleNamespace(timing_on=False)
-
-    def lane(self, name):
-        return contextlib.nullcontext()
-
-    @staticmethod
-    def mark():
-        return None
-
-    @staticmethod
-    def after(ev):
-        pass
+class FailingLabeller:
+    """anchor_targets_launch / _finish of a stand-in whose labeller fails for a sample of source width FAIL_WIDTH."""
 
     def anchor_targets_launch(self, gt, width, height, W, H, slot=0):
         self.k += 1
@@ -47,6 +30,58 @@ class LaneFakeEngine(FakeEngine):
         if tp["fail"]:
             raise KeyError(3)
         return None, None, 0
+
+
+class LaneFakeEngine(LaneClocks, FailingLabeller, FakeEngine):
+    """FakeEngine + the lane interface of the audit's stand-in (lane_audit.LaneClocks: lanes, events and waits are recorded with vector
+    clocks), so TrainStep runs its pipelined schedule and the run can be audited; a sample whose source width is FAIL_WIDTH makes
+    anchor_targets_finish raise the reference's KeyError.  What the stand-in's operations touch is named per buffer set: the feature map,
+    the label maps on the host, and the two sets of weights."""
+
+    def __init__(self, rank, bucketed=False):
+        super().__init__(rank, bucketed)
+        self._init_lanes(1)
+        self.ctx = types.SimpleNamespace(timing_on=False)
+
+    def anchor_targets_launch(self, gt, width, height, W, H, slot=0):
+        self._op("anchor_targets_launch", writes={"h_maps[%d]" % slot}, slot=slot)
+        return dict(super().anchor_targets_launch(gt, width, height, W, H, slot), event=self.mark())
+
+    def anchor_targets_finish(self, tp):
+        self.rec.host_wait(tp["event"], "anchor_targets_finish")
+        self.rec.host_op("host subsamples label maps", reads={"h_maps[%d]" % tp["slot"]}, slot=tp["slot"])
+        return super().anchor_targets_finish(tp)
+
+    def upload_image(self, img, slot=0):
+        return dict(super().upload_image(img, slot), F="F[%d]" % slot)
+
+    def base_forward(self, bp):
+        super().base_forward(bp)
+        self._op("base_forward", writes={bp["F"]}, slot=bp["slot"])
+
+    def rpn_forward(self, bp):
+        self._op("rpn_forward", reads={bp["F"], "W_rpn"})
+        return super().rpn_forward(bp)
+
+    def roi_targets_launch(self, R, Rn, gt, width, height, rw, rh, slot=0):
+        self._op("roi_targets_launch", writes={"h_codes[%d]" % slot}, slot=slot)
+        return dict(super().roi_targets_launch(R, Rn, gt, width, height, rw, rh, slot), slot=slot, event=self.mark())
+
+    def roi_targets_finish(self, P):
+        self.rec.host_wait(P["event"], "roi_targets_finish")
+        self.rec.host_op("host reads RoI class codes", reads={"h_codes[%d]" % P["slot"]}, slot=P["slot"])
+        return super().roi_targets_finish(P)
+
+    def _plan_head(self, R, fh, fw, F):
+        return dict(super()._plan_head(R, fh, fw, F), F=F)
+
+    def head_forward(self, hp, training=False, loss_out=None, group_live=None):
+        super().head_forward(hp, training, loss_out, group_live)
+        self._op("head_forward", reads={hp["F"], "W_head"})
+
+    def adam(self, arena, grad_scale=1.0, zero_grad=True):
+        super().adam(arena, grad_scale, zero_grad)
+        self._op("adam", reads={"W_head" if arena is self.head_arena else "W_rpn"}, writes={"W_head" if arena is self.head_arena else "W_rpn"})
 
 
 def _batches(fail_index, n=4):
@@ -63,8 +98,8 @@ def test_failed_labelling_drops_the_image_and_training_goes_on(pipelined):
     np.random.seed(64)
     eng = LaneFakeEngine(0) if pipelined else FakeEngine(0)
     if not pipelined:
-        eng.anchor_targets_launch = types.MethodType(LaneFakeEngine.anchor_targets_launch, eng)
-        eng.anchor_targets_finish = types.MethodType(LaneFakeEngine.anchor_targets_finish, eng)
+        eng.anchor_targets_launch = types.MethodType(FailingLabeller.anchor_targets_launch, eng)
+        eng.anchor_targets_finish = types.MethodType(FailingLabeller.anchor_targets_finish, eng)
     ts = TrainStep(eng, world_size=1)
     drops = []
     ts.on_drop = lambda sample, exc: drops.append((sample["width"], type(exc).__name__))
@@ -84,6 +119,10 @@ def test_failed_labelling_drops_the_image_and_training_goes_on(pipelined):
     assert sum(1 for e in eng.log if e[0] == "adam_head") == 3
     assert n_head_after == [1, 2, 2, 3]
     assert np.allclose(eng.rpn_arena.p.numpy(), -3.0)
+    if pipelined:          # the lanes of this run, audited: the dropped batch's prefetch and the head phases around it leave no race
+        pairs, examined = audit(eng.rec.trace)
+        assert not pairs, describe(pairs)
+        assert examined > 0 and {o.lane for o in eng.rec.trace} >= {"main", "side", "head", "host"}
 
 
 def _worker(rank, world, port, out):
