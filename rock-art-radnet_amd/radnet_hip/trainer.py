@@ -16,6 +16,8 @@ global RNG is the reference's: subsampling of image 0..B-1, then sample selectio
 import collections
 import contextlib
 import os
+import sys
+import time
 
 import numpy as np
 import torch
@@ -52,6 +54,51 @@ def allreduce_grad_arena_start(flat, world, group=None):
         import torch.distributed as dist
         return dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group, async_op=True)
     return None
+
+
+def gt_on_device(eng, s):
+    """Device copy of a sample's ground truth (cached on the sample: uploaded once)."""
+    if "_gt_dev" not in s:
+        cm = eng.C.class_mapping
+        boxes = np.array([[b["x1"], b["y1"], b["x2"], b["y2"]] for b in s["bboxes"]], dtype=np.float64).reshape(-1, 4)
+        isbg = np.array([1 if b["class"] == "bg" else 0 for b in s["bboxes"]], dtype=np.int32)
+        cls = np.array([cm[b["class"]] for b in s["bboxes"]], dtype=np.int32)
+        s["_gt_dev"] = eng.upload_gt(boxes, isbg, cls)
+    return s["_gt_dev"]
+
+
+def report_drop(sample, exc, on_drop=None):
+    """A sample whose anchor labelling raised: the callback(sample, exception), or one line on stderr, like the reference's print."""
+    if on_drop is not None:
+        on_drop(sample, exc)
+    else:
+        sys.stderr.write("radnet: anchor labelling failed (%s: %s); sample skipped as the reference's generator does\n"
+                         % (type(exc).__name__, exc))
+
+
+def select_rois(eng, cls, n):
+    """get_selected_samples over the RoI class codes of one image (roi_targets / roi_targets_finish: cls, n): None where calc_iou gives
+    None and the reference skips the classifier step -- NO draw from the RNG then -- else (indices into the RoI plan, indices among
+    the kept RoIs, positives among the sampled ones) after one E.select_samples, which draws from NumPy's global RNG."""
+    kept = np.nonzero(cls >= 0)[0]
+    if n <= 0 or len(kept) == 0:
+        return None
+    sel_k, n_pos = E.select_samples(cls[kept], eng.bg, eng.C.n_rois)
+    return kept[np.asarray(sel_k, dtype=np.int64)], sel_k, n_pos
+
+
+# One classifier pass of a step (TrainStep._head_passes): what crop-ahead and the classifier phase both need to know about it.
+#   plan, plan_kw  arguments of engine._plan_head (R, fh, fw, F; groups=nloc for the stacked pass)
+#   groups         per RoI group (image index in the batch, its pick = (RoI plan, selected indices), the detector-loss row it writes);
+#                  pick and row are None for an image of a stacked batch that takes no classifier step
+#   stacked        the per-GPU mini-batch in ONE pass: groups are packed by number, losses go out as a list, idle groups are masked
+#   accumulate     the backward adds to the gradients of an earlier pass of this step (never the stacked pass; from the second live image on)
+#   last           the step's gradient is complete after this backward (the stacked pass; the last live image's): a bucketed exchange rides on it
+HeadPass = collections.namedtuple("HeadPass", "plan plan_kw groups stacked accumulate last")
+
+
+def _no_lanes(ev):
+    pass
 
 
 class _EventWork:
@@ -195,8 +242,21 @@ class TrainStep:
         for work in works if isinstance(works, (list, tuple)) else [works]:
             if work is not None:
                 work.wait()
+        self._apply_head_update(ntot)
+
+    def _apply_head_update(self, ntot):
+        """Adam #2 on the (exchanged) head gradients: the mean over the global batch."""
         self.eng.adam(self.eng.head_arena, grad_scale=1.0 / ntot)
         self.eng.refresh_head_shift()
+
+    def _mark(self, label):
+        if self.host_marks is not None:
+            self.host_marks.append((label, time.perf_counter()))
+
+    @property
+    def _after(self):
+        """eng.after, called from the phase that needs the edge (a stand-in engine without lanes has none: nothing to order)."""
+        return getattr(self.eng, "after", _no_lanes)
 
     def start_loss_log(self, capacity):
         """Keep the five losses of every classifier step from here on in a device buffer (one row per image that took a head step,
@@ -253,16 +313,13 @@ class TrainStep:
         dl = torch.zeros(n_max, 3, dtype=torch.float32, device=eng.dev)
         used, n_pos_all, skipped, dropped = [], [], 0, 0
         for k, s in enumerate(samples):
-            H, W = s["img"].shape[:2]
-            tp = eng.anchor_targets_launch(self._gt(s), s["width"], s["height"], W, H, slot=self.VAL_SLOT)
-            bp = eng.upload_image(s["img"], slot=self.VAL_SLOT)
-            eng.base_forward(bp)
-            rp = eng.rpn_forward(bp)
+            st = self._launch_ab([s], self.VAL_SLOT)       # labelling kernels, upload, base and RPN forward, as for a batch of one
+            tp, bp, rp = st["tp"][0], st["plans"][0], st["rps"][0]
             try:
                 ycls, yregr, _ = eng.anchor_targets_finish(tp)
             except KeyError as e:
                 dropped += 1
-                self._report_drop(s, e)
+                report_drop(s, e, self.on_drop)
                 continue
             eng.rpn_losses_only(rp, ycls, yregr, rl[k])
             R, Rn = eng.proposals(rp, overlap_thresh=0.7, max_boxes=300)
@@ -270,12 +327,11 @@ class TrainStep:
             P, cls, n = eng.roi_targets(R, Rn, self._gt(s), s["width"], s["height"], rw, rh)
             if self.capture is not None:
                 self.capture.append(dict(pred=rp["pred"].cpu().numpy().copy(), R=R[:max(n, 0)].cpu().numpy().copy()))
-            kept = np.nonzero(cls >= 0)[0]
-            if n <= 0 or len(kept) == 0:
+            picked = select_rois(eng, cls, n)
+            if picked is None:
                 skipped += 1
                 continue
-            sel_k, n_pos = E.select_samples(cls[kept], eng.bg, C.n_rois)
-            sel = kept[np.asarray(sel_k, dtype=np.int64)]
+            sel, _, n_pos = picked
             hp = eng._plan_head(C.n_rois, bp["fh"], bp["fw"], bp["F"])
             eng.pack_roi_batch(P, sel, hp)
             eng.head_losses_only(hp, dl[k])
@@ -297,14 +353,7 @@ class TrainStep:
         return out
 
     def _gt(self, s):
-        """Device copy of a sample's ground truth (cached on the sample: uploaded once)."""
-        if "_gt_dev" not in s:
-            cm = self.eng.C.class_mapping
-            boxes = np.array([[b["x1"], b["y1"], b["x2"], b["y2"]] for b in s["bboxes"]], dtype=np.float64).reshape(-1, 4)
-            isbg = np.array([1 if b["class"] == "bg" else 0 for b in s["bboxes"]], dtype=np.int32)
-            cls = np.array([cm[b["class"]] for b in s["bboxes"]], dtype=np.int32)
-            s["_gt_dev"] = self.eng.upload_gt(boxes, isbg, cls)
-        return s["_gt_dev"]
+        return gt_on_device(self.eng, s)
 
     def _next_slot(self):
         self._slots += 1
@@ -369,7 +418,7 @@ class TrainStep:
             st["plans"] = [dict(F=bp["F"][i:i + 1], fh=bp["fh"], fw=bp["fw"], nb=1, x=bp["x"][i:i + 1], pair=bp)]
         return sts
 
-    def _rpn_phase(self, st, ntot, mark):
+    def _rpn_phase(self, st, ntot):
         """Phases A (host half) + C + the device part of D for a batch whose forward passes are enqueued: label maps
         subsampled on the host RNG, RPN losses + backward over the local images, [all-reduce], Adam #1, re-prediction with
         the updated weights, proposals, RoI labelling (async copy of the class codes)."""
@@ -392,11 +441,11 @@ class TrainStep:
             except KeyError as e:
                 dead[i] = True
                 self.dropped_images += 1
-                self._report_drop(batch[i], e)
+                report_drop(batch[i], e, self.on_drop)
                 if stacked:
                     eng.rpn_loss_image(rps[0], i, None, None)          # zero gradient rows for the dropped image
                 continue
-            mark("A: label maps on host, subsampled, packed")
+            self._mark("A: label maps on host, subsampled, packed")
             if stacked:
                 eng.rpn_loss_image(rps[0], i, ycls, yregr, self._rpn_l[slot][i])
             else:
@@ -415,7 +464,7 @@ class TrainStep:
         self._allreduce(eng.rpn_arena)
         eng.adam(eng.rpn_arena, grad_scale=1.0 / ntot)
         st["adam1"] = eng.mark() if hasattr(eng, "mark") else None
-        mark("C: rpn backward + adam enqueued")
+        self._mark("C: rpn backward + adam enqueued")
         if stacked:
             eng._run(rps[0].get("refwd", rps[0]["fwd"]))
         for i in range(nloc):
@@ -427,15 +476,7 @@ class TrainStep:
             R, Rn = eng.proposals(eng.rpn_image(rps[0], i) if stacked else rps[i], overlap_thresh=0.7, max_boxes=300)
             rw, rh = new_img_size(s["width"], s["height"], C.img_size)       # rpn.py:189 recomputes it from the config
             st["roi"][i] = (R, eng.roi_targets_launch(R, Rn, self._gt(s), s["width"], s["height"], rw, rh, slot=slot * nloc + i))
-        mark("D: rpn re-predict + proposals + roi targets enqueued")
-
-    def _report_drop(self, sample, exc):
-        if self.on_drop is not None:
-            self.on_drop(sample, exc)
-        else:
-            import sys
-            sys.stderr.write("radnet: anchor labelling failed (%s: %s); sample skipped as the reference's generator does\n"
-                             % (type(exc).__name__, exc))
+        self._mark("D: rpn re-predict + proposals + roi targets enqueued")
 
     def step(self, batch, next_batch=None, after_next=None, upcoming=None):
         """batch: list of dicts {img: uint8 BGR HWC (already at network size), bboxes: [{class,x1,x2,y1,y2}],
@@ -456,18 +497,9 @@ class TrainStep:
         chains fill those holes.  The host's order -- sample selection of this batch, then subsampling of the next
         batch's anchors -- and with it the order of draws from NumPy's global RNG is the reference's."""
         eng = self.eng
-        C = eng.C
         nloc = len(batch)
         ntot = nloc * self.world
-        marks = self.host_marks
-
-        def mark(label):
-            if marks is not None:
-                import time
-                marks.append((label, time.perf_counter()))
-
-        mark("start")
-        after = getattr(eng, "after", lambda ev: None)
+        self._mark("start")
         ahead = list(upcoming) if upcoming is not None else [b for b in (next_batch, after_next) if b is not None]
         ahead = ahead[:self.LOOKAHEAD]                 # lookahead; the further sets cover head phases still in flight
         pipelined = self.side_prefetch and bool(ahead) and not eng.ctx.timing_on
@@ -475,28 +507,60 @@ class TrainStep:
         # (contexts, recorded graphs) also in the calls that announce nothing -- the first and the last step of a run
         lanes = self.side_prefetch and not eng.ctx.timing_on and (pipelined or self._lane_mode)
         self._lane_mode = lanes
-        q = self._queue                                # states of the coming batches, in call order
-        st = q.popleft() if q and q[0]["batch"] is batch else None
-        if st is None:
-            if q and "roi" in q[0]:
-                # the announced batch's RPN phase -- an optimizer step -- has already been applied: dropping it silently would
-                # train the RPN on a batch whose classifier step never happens
-                raise RuntimeError("TrainStep.step: the previous call announced a different next batch (pass the same object)")
-            self._drop_prepared(q, 0)                  # not the announced batch: forward passes prepared for it are dropped
-            slot = self._next_slot()
-            if lanes:
-                k = slot % getattr(eng, "n_side_lanes", 1)
-                with eng.lane("side%d" % k if k else "side"):
-                    after(self._head_done.get(slot))
-                    st = self._launch_a(batch, slot)
-                    st["done"] = eng.mark()
-            else:
-                after(self._head_done.get(slot))       # one lane: only a prefetch that was dropped after flush() is still unordered
-                st = self._launch_a(batch, slot)
+        st = self._current_state(batch, lanes)
         if "roi" not in st:                            # first step of a run, or the previous call was not pipelined
-            after(st.get("done"))
+            self._after(st.get("done"))
             self._launch_b(st)
-            self._rpn_phase(st, ntot, mark)
+            self._rpn_phase(st, ntot)
+        nxt = self._prefetch(ahead, nloc, pipelined, lanes)
+        if pipelined and nxt.get("rps") is None:
+            # The next batch's RPN forward needs only its base forward and the RPN weights of Adam #1 of THIS batch, both
+            # enqueued long ago: it goes to the main lane now, ahead of the host's wait below, and is off the cycle
+            # "RoI codes -> sample selection -> anchor subsampling -> RPN backward ... -> RoI codes" that bounds the step.
+            self._after(nxt["done"])
+            self._launch_b(nxt)
+        self._mark("B: next batch's upload + base + rpn forward enqueued")
+        # ---- phase D, host half: RoI class codes -> sample selection on the host RNG (the step's host sync)
+        passes = self._head_passes(st, self._pick_rois(st))
+        crop_ev = self._crop_ahead(st, passes) if pipelined else None
+        # ---- pipelined: the next batch's RPN phase goes first -- the host sync of the NEXT call waits for it
+        if pipelined:
+            self._rpn_phase(nxt, ntot)                 # its RPN forward is already enqueued (above)
+        # ---- phase D, device half: classifier train step
+        det_rows = self._head_phase(st, passes, crop_ev, ntot, lanes)
+        self._mark("D: head forward + backward + adam enqueued")
+        self.last = (nloc, len(det_rows), st["slot"], list(st.get("dead", [False] * nloc)), det_rows)
+        return self
+
+    def _current_state(self, batch, lanes):
+        """The state of `batch`: the announced one, prepared by an earlier call, or phase A launched now for a batch nobody announced."""
+        q = self._queue                                # states of the coming batches, in call order
+        if q and q[0]["batch"] is batch:
+            return q.popleft()
+        if q and "roi" in q[0]:
+            # the announced batch's RPN phase -- an optimizer step -- has already been applied: dropping it silently would
+            # train the RPN on a batch whose classifier step never happens
+            raise RuntimeError("TrainStep.step: the previous call announced a different next batch (pass the same object)")
+        self._drop_prepared(q, 0)                      # not the announced batch: forward passes prepared for it are dropped
+        slot = self._next_slot()
+        with self._side_lane(slot) if lanes else contextlib.nullcontext():
+            # the head phase that last read this buffer set's feature map (one lane: only a prefetch that was dropped after
+            # flush() is still unordered)
+            self._after(self._head_done.get(slot))
+            st = self._launch_a(batch, slot)
+            if lanes:
+                st["done"] = self.eng.mark()
+        return st
+
+    def _side_lane(self, index):
+        """The prefetch lane of a buffer set (of a pair of sets: index = slot // 2)."""
+        k = index % getattr(self.eng, "n_side_lanes", 1)
+        return self.eng.lane("side%d" % k if k else "side")
+
+    def _prefetch(self, ahead, nloc, pipelined, lanes):
+        """Reconcile the prepared states with the announcements `ahead` and launch phase A of the new ones, each on the prefetch lane of its
+        buffer set.  Returns the next call's state (None: nothing prepared)."""
+        q = self._queue
         for j in range(len(q)):                        # announced batches must be the ones prepared, in order
             if j >= len(ahead) or q[j]["batch"] is not ahead[j]:
                 self._drop_prepared(q, j)
@@ -514,183 +578,175 @@ class TrainStep:
                 slot = self._next_slot()
                 # consecutive batches (pairs) alternate lanes; a buffer set keeps its lane (and with it its context: one graph
                 # per program)
-                k = ((slot // 2) if pairable else slot) % getattr(eng, "n_side_lanes", 1)
-                with eng.lane("side%d" % k if k else "side"):
-                    after(self._head_done.get(slot))   # the head phase that last read this buffer set's feature map
+                with self._side_lane((slot // 2) if pairable else slot):
+                    self._after(self._head_done.get(slot))         # the head phase that last read this buffer set's feature map
                     if pairable:
                         slot_b = self._next_slot()
-                        after(self._head_done.get(slot_b))
-                        pair = self._launch_pair(ahead[j], ahead[j + 1], slot, slot_b)
-                        ev = eng.mark()
-                        for nb in pair:
-                            nb["done"] = ev
-                            q.append(nb)
-                        j += 2
+                        self._after(self._head_done.get(slot_b))
+                        new = self._launch_pair(ahead[j], ahead[j + 1], slot, slot_b)
                     else:
-                        nb = self._launch_a(ahead[j], slot)
-                        nb["done"] = eng.mark()
-                        q.append(nb)
-                        j += 1
+                        new = [self._launch_a(ahead[j], slot)]
+                    ev = self.eng.mark()
+                    for nb in new:
+                        nb["done"] = ev
+                q.extend(new)
+                j += len(new)
         elif not lanes:
-            after(self._head_last)                     # the head phase below runs on the main lane
+            self._after(self._head_last)               # the head phase of this step runs on the main lane
             if ahead and not q:
-                q.append(self._launch_a(ahead[0], self._next_slot()))   # one lane: keeps the GPU busy across the sync below
-        nxt = q[0] if q else None
-        if pipelined and nxt.get("rps") is None:
-            # The next batch's RPN forward needs only its base forward and the RPN weights of Adam #1 of THIS batch, both
-            # enqueued long ago: it goes to the main lane now, ahead of the host's wait below, and is off the cycle
-            # "RoI codes -> sample selection -> anchor subsampling -> RPN backward ... -> RoI codes" that bounds the step.
-            after(nxt["done"])
-            self._launch_b(nxt)
-        mark("B: next batch's upload + base + rpn forward enqueued")
-        # ---- phase D, host half: RoI class codes -> sample selection on the host RNG (the step's host sync)
-        picks = []
+                q.append(self._launch_a(ahead[0], self._next_slot()))   # one lane: keeps the GPU busy across the step's host sync
+        return q[0] if q else None
+
+    def _pick_rois(self, st):
+        """Host half of phase D: RoI class codes -> sample selection on the host RNG (the step's host sync).  Per image the pick
+        (RoI plan, selected indices), or None for an image without a classifier step."""
+        eng = self.eng
+        nloc = len(st["batch"])
+        picks = [None] * nloc
         self.last_n_pos = [None] * nloc
         self.last_took_head = [False] * nloc
         for i in range(nloc):
             if st["roi"][i] is None:                               # dropped by the labeller (see _rpn_phase): not a head skip
-                picks.append(None)
                 continue
             R, P = st["roi"][i]
             P, cls, n = eng.roi_targets_finish(P)
-            mark("D: roi classes on host")
-            kept = np.nonzero(cls >= 0)[0]
-            if n <= 0 or len(kept) == 0:                           # calc_iou -> None: the reference skips the head step
+            self._mark("D: roi classes on host")
+            picked = select_rois(eng, cls, n)
+            if picked is None:                                     # calc_iou -> None: the reference skips the head step
                 self.skipped_head_steps += 1
                 self.last_n_pos[i] = 0
-                picks.append(None)
                 continue
-            sel_k, n_pos = E.select_samples(cls[kept], eng.bg, C.n_rois)
+            sel, sel_k, n_pos = picked
             self.last_n_pos[i] = int(n_pos)
             self.last_took_head[i] = True
-            picks.append((P, kept[np.asarray(sel_k, dtype=np.int64)]))
-            mark("D: samples selected")
+            picks[i] = (P, sel)
+            self._mark("D: samples selected")
             if self.capture is not None:
                 view = eng.rpn_image(st["rps"][0], i) if st.get("stacked") else st["rps"][i]
                 self.capture.append(dict(pred=view["pred"].cpu().numpy().copy(), R=R[:n].cpu().numpy().copy(),
                                          keep=(cls >= 0).copy(), cls=cls.copy(), sel_kept=list(sel_k)))
-        # ---- pipelined: RoI packing + crop-resize of THIS batch on the RPN lane, now -- the lane is idle until the host has subsampled the
-        # next batch's anchors (0.3 ms), and the classifier lane, the saturated one, starts at stage 5 (two launches fewer on it)
-        crop_ev = None
-        live_now = [i for i in range(nloc) if picks[i] is not None]
-        if pipelined and self.crop_ahead and live_now and getattr(eng, "CROP_AHEAD", False):
-            after(self._head_done.get(st["slot"]))      # the classifier phase that last used this buffer set's head plan
-            if st.get("stacked"):
-                bp0 = st["plans"][0]
-                hp0 = eng._plan_head(nloc * C.n_rois, bp0["fh"], bp0["fw"], bp0["F"], groups=nloc)
-                for i in range(nloc):
-                    if picks[i] is None:
-                        eng.idle_roi_group(hp0, i)
-                    else:
-                        eng.pack_roi_batch(picks[i][0], picks[i][1], hp0, group=i)
-                eng.head_crop(hp0)
+        return picks
+
+    def _head_passes(self, st, picks):
+        """The classifier passes of this step, in order: ONE pass over all images' RoIs for a stacked batch (GEMM M = nloc * n_rois * 49;
+        an image without a classifier step is an idle group: zero gradient rows), else one pass per image that takes a classifier step.
+        None at all when no image does."""
+        stacked = bool(st.get("stacked"))
+        live = [i for i, pick in enumerate(picks) if pick is not None]
+        if stacked and live:
+            members = [[(i, pick, i if pick is not None else None) for i, pick in enumerate(picks)]]      # row i = image i of the mini-batch
+        else:
+            members = [[(i, picks[i], row)] for row, i in enumerate(live)]                                # row = the running count of live images
+        passes = []
+        for k, groups in enumerate(members):
+            bp = st["plans"][groups[0][0]]
+            plan = (len(groups) * self.eng.C.n_rois, bp["fh"], bp["fw"], bp["F"])
+            passes.append(HeadPass(plan, {"groups": len(groups)} if stacked else {}, groups, stacked, k > 0, k == len(members) - 1))
+        return passes
+
+    def _pack_rois(self, p, hp):
+        """The RoI batch of pass `p` into its head plan."""
+        eng = self.eng
+        for g, (_, pick, _) in enumerate(p.groups):
+            if pick is None:
+                eng.idle_roi_group(hp, g)
+            elif p.stacked:
+                eng.pack_roi_batch(pick[0], pick[1], hp, group=g)
             else:
-                for i in live_now:
-                    bp0 = st["plans"][i]
-                    hp0 = eng._plan_head(C.n_rois, bp0["fh"], bp0["fw"], bp0["F"])
-                    eng.pack_roi_batch(picks[i][0], picks[i][1], hp0)
-                    eng.head_crop(hp0)
-            crop_ev = eng.mark()
-        # ---- pipelined: the next batch's RPN phase goes first -- the host sync of the NEXT call waits for it
-        if pipelined:
-            self._rpn_phase(nxt, ntot, mark)           # its RPN forward is already enqueued (above)
-        # ---- phase D, device half: classifier train step
-        head_lane = (lambda: eng.lane("head")) if lanes else contextlib.nullcontext
+                eng.pack_roi_batch(pick[0], pick[1], hp)
+
+    def _crop_ahead(self, st, passes):
+        """Pipelined: RoI packing + crop-resize of THIS batch on the RPN lane, now -- the lane is idle until the host has subsampled the
+        next batch's anchors (0.3 ms), and the classifier lane, the saturated one, starts at stage 5 (two launches fewer on it).
+        Returns the event behind the crops, None when nothing was cropped."""
+        eng = self.eng
+        if not (self.crop_ahead and passes and getattr(eng, "CROP_AHEAD", False)):
+            return None
+        self._after(self._head_done.get(st["slot"]))    # the classifier phase that last used this buffer set's head plan
+        for p in passes:
+            hp = eng._plan_head(*p.plan, **p.plan_kw)
+            self._pack_rois(p, hp)
+            eng.head_crop(hp)
+        return eng.mark()
+
+    def _head_phase(self, st, passes, crop_ev, ntot, lanes):
+        """Device half of phase D, on the head lane: the classifier train step over `passes`, then Adam #2 (or the start of its
+        exchange).  Returns the rows of the detector-loss slots that hold this step's losses."""
+        eng = self.eng
         slot = st["slot"]
-        n_head = 0
-        det_rows = None                 # rows of the detector-loss slots that hold this step's losses (default: the first n_head)
-        live = [i for i in range(nloc) if picks[i] is not None]
+        det_rows = [row for p in passes for _, _, row in p.groups if row is not None]
         # Bucketed exchange (deferred mode): during the LAST local image's backward each block's kernel gradients are
         # final as soon as that block is differentiated -- their all-reduce starts then, beside the blocks still to come
         # (res5c 18 MB, res5b 18 MB, res5a 24 MB); only the last slice and the small tail are left at the end.
         slices = eng.head_exchange_slices() if hasattr(eng, "head_exchange_slices") else None
         bucketed = self.defer_head_update and (self.world > 1 or FORCE_COLLECTIVES) and slices is not None and not self.native_comm
-        works = []
+        works = [] if bucketed else None
         # Deferred weight-gradient form of the head backward (engine.head_update_deferred): only where this step's gradient is complete
         # inside ONE backward program and goes straight into Adam #2 -- one rank, nothing exchanged, no deferred update, and not the
         # per-GPU batch that runs its images through separate programs and adds their gradients up.
         fuse_ok = (self.world == 1 and not FORCE_COLLECTIVES and not self.defer_head_update and not self.native_comm
-                   and (bool(st.get("stacked")) or nloc == 1) and hasattr(eng, "head_deferred_ok"))
+                   and (bool(st.get("stacked")) or len(st["batch"]) == 1) and hasattr(eng, "head_deferred_ok"))
         fused_hp = None
-
-        def exchange(lo, hi):
-            works.append(allreduce_grad_arena_start(eng.head_arena.g[lo:hi], self.world, self.group_head))
-
-        with head_lane():      # what it reads from the other lanes (feature map, RoI labels) is complete: the host waited
-            after(crop_ev)
-            crop_kw = {"cropped": True} if crop_ev is not None else {}
-            if st.get("stacked") and live:
-                # per-GPU mini-batch: all images' RoIs through stage 5 in ONE pass (GEMM M = nloc * n_rois * 49); losses per
-                # image, an image without a classifier step contributes zero gradient rows
-                bp = st["plans"][0]
-                hp = eng._plan_head(nloc * C.n_rois, bp["fh"], bp["fw"], bp["F"], groups=nloc)
-                slots = []
-                for i in range(nloc):
-                    if picks[i] is None:
-                        if crop_ev is None:
-                            eng.idle_roi_group(hp, i)
-                        slots.append(None)
-                    else:
-                        if crop_ev is None:
-                            eng.pack_roi_batch(picks[i][0], picks[i][1], hp, group=i)
-                        slots.append(self._det_l[slot][i])            # row i = image i of the mini-batch
-                        n_head += 1
-                det_rows = [i for i in range(nloc) if picks[i] is not None]
-                self._finish_head_update()               # deferred Adam #2 of the previous step: head weights are read next
-                eng.head_forward(hp, training=True, loss_out=self._det_l[slot], group_live=[p is not None for p in picks], **crop_kw)
-                eng.set_accumulate(hp["bwd"], False, prezeroed=True)
-                if fuse_ok and eng.head_deferred_ok(hp):
-                    fused_hp = hp
-                    eng.head_backward(hp, accumulate=True, loss_out=slots, defer_wgrad=True)
-                else:
-                    eng.head_backward(hp, accumulate=True, loss_out=slots, on_part=exchange if bucketed else None)
-                for i in det_rows:
-                    self._log_losses(self._rpn_l[slot][i], self._det_l[slot][i])
-            for i, bp in enumerate(st["plans"] if not st.get("stacked") else []):
-                if picks[i] is None:
-                    continue
-                hp = eng._plan_head(C.n_rois, bp["fh"], bp["fw"], bp["F"])
+        with eng.lane("head") if lanes else contextlib.nullcontext():
+            # what the lane reads from the other lanes (feature map, RoI labels) is complete: the host waited
+            self._after(crop_ev)
+            for p in passes:
+                hp = eng._plan_head(*p.plan, **p.plan_kw)
                 if crop_ev is None:
-                    eng.pack_roi_batch(picks[i][0], picks[i][1], hp)
+                    self._pack_rois(p, hp)
                 self._finish_head_update()               # deferred Adam #2 of the previous step: head weights are read next
-                eng.head_forward(hp, training=True, loss_out=self._det_l[slot][n_head], **crop_kw)
-                eng.set_accumulate(hp["bwd"], n_head > 0, prezeroed=True)
-                if fuse_ok and eng.head_deferred_ok(hp):
-                    fused_hp = hp
-                    eng.head_backward(hp, accumulate=True, loss_out=self._det_l[slot][n_head], defer_wgrad=True)
-                elif bucketed and i == live[-1]:
-                    eng.head_backward(hp, accumulate=True, loss_out=self._det_l[slot][n_head], on_part=exchange)
+                rows = [None if row is None else self._det_l[slot][row] for _, _, row in p.groups]
+                if p.stacked:       # losses per image; an image without a classifier step contributes zero gradient rows
+                    fwd_kw, loss_out = {"loss_out": self._det_l[slot], "group_live": [r is not None for r in rows]}, rows
                 else:
-                    eng.head_backward(hp, accumulate=True, loss_out=self._det_l[slot][n_head])
-                self._log_losses(self._rpn_l[slot][i], self._det_l[slot][n_head])
-                n_head += 1
-            if n_head > 0 or self.world > 1:
-                self._finish_head_update()               # only still pending when every local image skipped its head phase
-                if fused_hp is not None:                 # the weight gradients, Adam #2 in their epilogue, the Adam tail, the Winograd filters
-                    eng.head_update_deferred(fused_hp, grad_scale=1.0 / ntot)
-                elif bucketed:
-                    if not works:                        # every local image skipped its classifier step: the other ranks
-                        for lo, hi in slices:            # still exchange slice by slice -- same collectives, zeros from here
-                            exchange(lo, hi)
-                    exchange(eng.head_bias_off, eng.head_arena.n)      # biases + dense heads
-                    self._head_pending = (works, ntot)
-                elif self.native_comm and self.defer_head_update:
-                    self._head_pending = ([self._native_head_exchange()], ntot)
-                elif self.native_comm:
-                    self._native_head_exchange().wait()
-                    eng.adam(eng.head_arena, grad_scale=1.0 / ntot)
-                    eng.refresh_head_shift()
-                elif self.defer_head_update:
-                    self._head_pending = (allreduce_grad_arena_start(eng.head_arena.g, self.world, self.group_head), ntot)
+                    fwd_kw, loss_out = {"loss_out": rows[0]}, rows[0]
+                if crop_ev is not None:
+                    fwd_kw["cropped"] = True
+                eng.head_forward(hp, training=True, **fwd_kw)
+                eng.set_accumulate(hp["bwd"], p.accumulate, prezeroed=True)
+                if fuse_ok and eng.head_deferred_ok(hp):           # (asked behind set_accumulate: it looks at the accumulate flags)
+                    fused_hp, bwd_kw = hp, {"defer_wgrad": True}
+                elif bucketed and p.last:
+                    bwd_kw = {"on_part": lambda lo, hi: self._exchange_start(works, lo, hi)}
                 else:
-                    self._allreduce(eng.head_arena)
-                    eng.adam(eng.head_arena, grad_scale=1.0 / ntot)
-                    eng.refresh_head_shift()
+                    bwd_kw = {}
+                eng.head_backward(hp, accumulate=True, loss_out=loss_out, **bwd_kw)
+                for (i, _, _), row in zip(p.groups, rows):
+                    if row is not None:
+                        self._log_losses(self._rpn_l[slot][i], row)
+            if det_rows or self.world > 1:
+                self._head_update(ntot, fused_hp, works, slices)
             if lanes:
                 self._head_last = self._head_done[slot] = eng.mark()
-        mark("D: head forward + backward + adam enqueued")
-        self.last = (nloc, n_head, slot, list(st.get("dead", [False] * nloc)), det_rows if det_rows is not None else list(range(n_head)))
-        return self
+        return det_rows
+
+    def _exchange_start(self, works, lo, hi):
+        works.append(allreduce_grad_arena_start(self.eng.head_arena.g[lo:hi], self.world, self.group_head))
+
+    def _head_update(self, ntot, fused_hp, works, slices):
+        """How Adam #2 of this step is applied.  fused_hp: the head plan whose backward left its weight gradients to
+        engine.head_update_deferred (None: they are in the arena); works: the slice exchanges the bucketed backward has started
+        (None: not bucketed), slices: the arena's slices in the order the backward finishes them."""
+        eng = self.eng
+        self._finish_head_update()               # only still pending when every local image skipped its head phase
+        if fused_hp is not None:                 # the weight gradients, Adam #2 in their epilogue, the Adam tail, the Winograd filters
+            eng.head_update_deferred(fused_hp, grad_scale=1.0 / ntot)
+        elif works is not None:
+            if not works:                        # every local image skipped its classifier step: the other ranks
+                for lo, hi in slices:            # still exchange slice by slice -- same collectives, zeros from here
+                    self._exchange_start(works, lo, hi)
+            self._exchange_start(works, eng.head_bias_off, eng.head_arena.n)      # biases + dense heads
+            self._head_pending = (works, ntot)
+        elif self.native_comm and self.defer_head_update:
+            self._head_pending = ([self._native_head_exchange()], ntot)
+        elif self.native_comm:
+            self._native_head_exchange().wait()
+            self._apply_head_update(ntot)
+        elif self.defer_head_update:
+            self._head_pending = (allreduce_grad_arena_start(eng.head_arena.g, self.world, self.group_head), ntot)
+        else:
+            self._allreduce(eng.head_arena)
+            self._apply_head_update(ntot)
 
     def losses(self):
         """Host copy of the last step's mean losses (one device sync)."""

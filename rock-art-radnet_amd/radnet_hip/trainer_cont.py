@@ -13,8 +13,7 @@ with both optimizers, so neither update can be deferred across the next step's b
 import numpy as np
 import torch
 
-from . import engine as E
-from .trainer import allreduce_grad_arena, new_img_size
+from .trainer import allreduce_grad_arena, gt_on_device, new_img_size, report_drop, select_rois
 
 
 class ContTrainStep:
@@ -34,13 +33,7 @@ class ContTrainStep:
         self._det_l = torch.zeros(64, 3, dtype=torch.float32, device=dev)
 
     def _gt(self, s):
-        if "_gt_dev" not in s:
-            cm = self.eng.C.class_mapping
-            boxes = np.array([[b["x1"], b["y1"], b["x2"], b["y2"]] for b in s["bboxes"]], dtype=np.float64).reshape(-1, 4)
-            isbg = np.array([1 if b["class"] == "bg" else 0 for b in s["bboxes"]], dtype=np.int32)
-            cls = np.array([cm[b["class"]] for b in s["bboxes"]], dtype=np.int32)
-            s["_gt_dev"] = self.eng.upload_gt(boxes, isbg, cls)
-        return s["_gt_dev"]
+        return gt_on_device(self.eng, s)
 
     def _launch_stem(self, batch, slot):
         """What does not depend on any trainable weight: labelling kernels, upload, conv1 .. stage 2 (frozen).  Images are host
@@ -91,8 +84,7 @@ class ContTrainStep:
             try:
                 ycls, yregr, _ = eng.anchor_targets_finish(tp[i])
             except KeyError as e:
-                import sys
-                sys.stderr.write("radnet: anchor labelling failed (KeyError: %s); sample skipped as the reference's generator does\n" % (e,))
+                report_drop(batch[i], e)
                 dead[i] = True
                 self.dropped_images += 1
                 continue
@@ -120,12 +112,11 @@ class ContTrainStep:
             R, Rn = eng.proposals(rp, overlap_thresh=0.7, max_boxes=300)
             rw, rh = new_img_size(s["width"], s["height"], C.img_size)
             P, cls, n = eng.roi_targets(R, Rn, self._gt(s), s["width"], s["height"], rw, rh)
-            kept = np.nonzero(cls >= 0)[0]
-            if n <= 0 or len(kept) == 0:
+            picked = select_rois(eng, cls, n)
+            if picked is None:
                 self.skipped_head_steps += 1
                 continue
-            sel_k, _ = E.select_samples(cls[kept], eng.bg, C.n_rois)
-            sel = kept[np.asarray(sel_k, dtype=np.int64)]
+            sel, sel_k, _ = picked
             if self.capture is not None:
                 self.capture.append(dict(pred=rp["pred"].cpu().numpy().copy(), R=R[:n].cpu().numpy().copy(), keep=(cls >= 0).copy(),
                                          cls=cls.copy(), sel_kept=list(sel_k)))

@@ -172,6 +172,56 @@ def test_deferred_head_update_order_and_value(defer, bucketed):
         assert any(e[0] == "refresh" for e in log)
 
 
+@pytest.mark.parametrize("defer", [True, False])
+def test_native_exchange_head_update_order(defer):
+    """The two outcomes of the Adam #2 decision that go through the library's own exchange (TrainStep.native_comm), on the same stand-in,
+    in process: _native_head_exchange is replaced by a recorder whose handle logs its wait().  Deferred: Adam #2 of step k is applied
+    behind the exchange's wait(), after step k+1's RPN phase and before its head forward, the last one in flush().  Immediate: exchange,
+    wait, Adam #2, refresh of the folded shifts, in that order, inside step k."""
+    from radnet_hip.trainer import TrainStep
+    np.random.seed(64)
+    eng = FakeEngine(0)
+    ts = TrainStep(eng, world_size=1, defer_head_update=defer)
+    ts.native_comm = True
+
+    class Work:
+        def __init__(self, k):
+            self.k = k
+
+        def wait(self):
+            eng.log.append(("wait", self.k))
+
+    def exchange():
+        eng.log.append(("exchange", eng.k))
+        return Work(eng.k)
+    ts._native_head_exchange = exchange
+    ts._allreduce = lambda arena: eng.log.append(("allreduce", "head" if arena is eng.head_arena else "rpn"))      # (AR#1 is native too: no library here)
+    batch = [dict(img=np.zeros((4, 4, 3), np.uint8), bboxes=[dict({"class": "fg"}, x1=0, x2=2, y1=0, y2=2)], width=8, height=8)]
+    for _ in range(3):
+        ts.step(batch)
+    n_before_flush = len(eng.log)
+    ts.flush()
+    log = eng.log
+    names = [e[0] for e in log]
+    assert names.count("exchange") == names.count("wait") == names.count("adam_head") == names.count("refresh") == 3
+    assert [e[1] for e in log if e[0] == "allreduce"] == ["rpn"] * 3       # the head gradients travel through the native exchange only
+    assert np.allclose(eng.head_arena.p.numpy(), -(1 + 2 + 3))          # every step's gradient applied exactly once
+    for k in range(3):
+        i_ex, i_wait = log.index(("exchange", k)), log.index(("wait", k))
+        i_adam = [i for i, e in enumerate(log) if e[0] == "adam_head"][k]
+        assert abs(log[i_adam][2] - (k + 1)) < 1e-12                      # ... and it is step k's
+        assert i_ex < i_wait and i_adam == i_wait + 1 and names[i_wait:i_wait + 3] == ["wait", "adam_head", "refresh"]
+        i_fwd = [i for i, e in enumerate(log) if e[0] == "head_fwd"]
+        assert i_fwd[k] < i_ex                                            # the exchange follows the step's own head pass
+        if not defer:
+            assert i_wait == i_ex + 1 and log[i_adam][1] == k and i_adam < n_before_flush      # inside step k
+        elif k < 2:
+            i_rpn = [i for i, e in enumerate(log) if e[0] == "adam_rpn" and e[1] == k + 1][0]
+            assert i_rpn < i_wait and i_adam < i_fwd[k + 1]                # under step k+1's RPN phase, before its head forward
+        else:
+            assert i_wait >= n_before_flush                               # the last one: flush()
+
+
 def _worker_skip(rank, world, port, out):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)

@@ -2,7 +2,7 @@
 
 Every scenario runs the real step / flush / losses / validate code on the recording stand-in and asserts that no two conflicting accesses
 to one buffer are left unordered by the lanes' events and the host's waits.  The mutants then take the ordering edges away one at a time:
-every after(...) of TrainStep.step / flush and each of the three host waits is either NEEDED (some scenario reports a race without it) or
+every after(...) of TrainStep.step, of the phases it is made of and of flush, and each of the three host waits is either NEEDED (some scenario reports a race without it) or
 listed in REDUNDANT with the path that orders the same accesses anyway -- both directions are asserted, so the table cannot rot and a wait
 that is not needed shows up as such."""
 import ast
@@ -56,6 +56,26 @@ def n_steps(scn):
 Result = collections.namedtuple("Result", "pairs examined trace eng ts sites_hit")
 
 
+def trainstep_functions():
+    """Every function defined in class TrainStep, found from the class (methods, static and class methods, property accessors), in source
+    order: an ordering edge may live in any of them."""
+    from radnet_hip.trainer import TrainStep
+    fns = []
+    for v in vars(TrainStep).values():
+        if isinstance(v, (staticmethod, classmethod)):
+            v = v.__func__
+        fns += [f for f in ((v.fget, v.fset, v.fdel) if isinstance(v, property) else (v,)) if inspect.isfunction(f)]
+    return sorted(fns, key=lambda f: f.__code__.co_firstlineno)
+
+
+def _code_objects(code):
+    """A function's code object and those of the functions nested in it."""
+    yield code
+    for c in code.co_consts:
+        if inspect.iscode(c):
+            yield from _code_objects(c)
+
+
 def run(scn, skip_site=None, skip_wait=None):
     """One scenario on the real TrainStep.  skip_site: line in trainer.py of an after(...) that is left out; skip_wait: a host wait that does
     not join the host clock."""
@@ -67,9 +87,11 @@ def run(scn, skip_site=None, skip_wait=None):
     sites_hit = set()
     real_after = eng.after
 
-    def after(ev):                      # the ordering edges of step / flush, known by the caller's line
+    codes = {c for fn in trainstep_functions() for c in _code_objects(fn.__code__)}
+
+    def after(ev):                      # the ordering edges of TrainStep's methods, known by the caller's line
         f = sys._getframe(1)
-        if f.f_code.co_filename == T.__file__ and f.f_code.co_name in ("step", "flush"):
+        if f.f_code in codes:
             sites_hit.add(f.f_lineno)
             if f.f_lineno == skip_site:
                 return
@@ -207,14 +229,14 @@ def test_scenarios_reach_what_they_are_named_for(clean_runs):
 
 # ------------------------------------------------------------------------------------------------ mutants
 def after_sites():
-    """{site: line} of every after(...) call in TrainStep.step and TrainStep.flush, named by function and argument."""
-    from radnet_hip import trainer as T
+    """{site: line} of every after(...) call in the functions of class TrainStep (after(...), eng.after(...) or self._after(...), the
+    accessor the phases of step go through), named by function and argument."""
     sites, seen = {}, collections.Counter()
-    for fn in (T.TrainStep.step, T.TrainStep.flush):
+    for fn in trainstep_functions():
         src, first = inspect.getsourcelines(fn)
         tree = ast.parse(textwrap.dedent("".join(src)))
         calls = [c for c in ast.walk(tree) if isinstance(c, ast.Call) and
-                 ((isinstance(c.func, ast.Name) and c.func.id == "after") or (isinstance(c.func, ast.Attribute) and c.func.attr == "after"))]
+                 ((isinstance(c.func, ast.Name) and c.func.id == "after") or (isinstance(c.func, ast.Attribute) and c.func.attr in ("after", "_after")))]
         for c in sorted(calls, key=lambda c: c.lineno):
             key = "%s: after(%s)" % (fn.__name__, ast.unparse(c.args[0]))
             seen[key] += 1
@@ -222,25 +244,29 @@ def after_sites():
     return sites
 
 
-# the after(...) call sites of TrainStep.step and TrainStep.flush, in source order (a repeated argument is numbered)
+# the after(...) call sites of step, its phases and flush (a repeated argument is numbered within its function)
 AFTER_SITES = [
-    "step: after(self._head_done.get(slot))",          # un-announced batch, prefetch lane: in front of _launch_a
-    "step: after(self._head_done.get(slot)) #2",       # un-announced batch, one lane: in front of _launch_a
-    "step: after(st.get('done'))",                     # current batch: in front of _launch_b
-    "step: after(self._head_done.get(slot)) #3",       # announced batch, prefetch lane: in front of _launch_a / _launch_pair
-    "step: after(self._head_done.get(slot_b))",        # ... the pair's second buffer set
-    "step: after(self._head_last)",                    # one lane: the head phase runs on the main lane
-    "step: after(nxt['done'])",                        # announced batch: in front of _launch_b
-    "step: after(self._head_done.get(st['slot']))",    # in front of crop-ahead
-    "step: after(crop_ev)",                            # head lane: behind crop-ahead
+    "_current_state: after(self._head_done.get(slot))",        # un-announced batch, on its prefetch lane or on the one lane: in front of _launch_a
+    "step: after(st.get('done'))",                             # current batch: in front of _launch_b
+    "_prefetch: after(self._head_done.get(slot))",             # announced batch, prefetch lane: in front of _launch_a / _launch_pair
+    "_prefetch: after(self._head_done.get(slot_b))",           # ... the pair's second buffer set
+    "_prefetch: after(self._head_last)",                       # one lane: the head phase runs on the main lane
+    "step: after(nxt['done'])",                                # announced batch: in front of _launch_b
+    "_crop_ahead: after(self._head_done.get(st['slot']))",     # in front of crop-ahead
+    "_head_phase: after(crop_ev)",                             # head lane: behind crop-ahead
     "flush: after(self._head_last)",
 ]
+# after(...) calls of TrainStep that the audit does not reach, and why (lane_audit.py, SCOPE): found by after_sites() like the others, so
+# that none can be added unseen, but no scenario runs them and no mutant takes them away
+NOT_MODELLED = {
+    "_native_head_exchange: after(ready)": "on the head communicator's stream of the data-parallel step; the scenarios are world size 1",
+}
 HOST_WAITS = {"host wait: anchor_targets_finish": "anchor_targets_finish", "host wait: roi_targets_finish": "roi_targets_finish",
               "host wait: losses()": "event.synchronize"}
 
 # Ordering edges whose removal leaves every scenario race-free, and why.
 REDUNDANT = {
-    "step: after(self._head_done.get(st['slot']))":
+    "_crop_ahead: after(self._head_done.get(st['slot']))":
         "ordered through the prefetch lane: the launch of phase A into this buffer set waited for the same event (the after in front of "
         "_launch_a / _launch_pair), and the main lane waited for that launch's `done` before _launch_b, long before crop-ahead",
 }
@@ -256,13 +282,13 @@ def test_the_after_sites_are_the_ones_the_audit_knows():
     lines = inspect.getsource(T).splitlines()
     for key, line in sites.items():
         assert "after(" in lines[line - 1], (key, line, lines[line - 1])
-    assert sorted(sites) == sorted(AFTER_SITES), sorted(sites)
-    assert set(REDUNDANT) <= set(sites) | set(HOST_WAITS)
+    assert sorted(sites) == sorted(AFTER_SITES + list(NOT_MODELLED)), sorted(sites)
+    assert set(REDUNDANT) <= set(AFTER_SITES) | set(HOST_WAITS)
 
 
 def test_every_after_site_is_reached_by_some_scenario(clean_runs):
     hit = set().union(*(r.sites_hit for r in clean_runs.values()))
-    assert set(after_sites().values()) <= hit
+    assert {line for site, line in after_sites().items() if site not in NOT_MODELLED} <= hit
 
 
 @pytest.mark.parametrize("site", AFTER_SITES + sorted(HOST_WAITS))

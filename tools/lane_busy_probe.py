@@ -58,12 +58,12 @@ def main():
     eng.lane = lane
     orig_rpn = ts._rpn_phase
 
-    def rpn_phase(st, ntot, mark):
+    def rpn_phase(st, ntot):
         if not on[0]:
-            return orig_rpn(st, ntot, mark)
+            return orig_rpn(st, ntot)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        r = orig_rpn(st, ntot, mark)
+        r = orig_rpn(st, ntot)
         e1.record()
         rec.setdefault("main: rpn phase", []).append((e0, e1))
         return r
