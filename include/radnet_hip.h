@@ -951,6 +951,52 @@ int radnet_crc32_plan_segments(const radnet_crc32_segment* table, int32_t count,
  * grow it waits for the context's stream first). */
 int radnet_crc32_segments(radnet_ctx* ctx, const uint8_t* buf, int64_t n, const radnet_crc32_segment* table_host,
                           const radnet_crc32_segment* table_dev, int32_t count, uint32_t* crc, int32_t* result);
+/* ---- A PNG's IDAT payloads joined on the device (csrc/png_join.hip, csrc/png_join_plan.cpp) ------------------------------------------
+ * The file's bytes go up as they are; one launch gathers the payloads of its IDAT chunks into the zlib stream the inflate entries
+ * take.  Piece k of the table says  out[dst_k + j] = file[src_k + j]  for 0 <= j < length_k.  dst is the exclusive prefix sum of
+ * the lengths in table order -- the pieces tile out[0 .. n) without a gap, in order; a length of 0 is legal, anywhere and any number
+ * of times in a row; the src ranges may come in any order and may overlap. */
+typedef struct radnet_png_piece {
+  int64_t src;    /* of the piece's first byte in the file */
+  int64_t dst;    /* of the piece's first byte in the joined stream: the sum of the lengths in front of it */
+  int64_t length; /* in bytes; 0 is legal */
+} radnet_png_piece; /* 24 bytes */
+/* THE GRAIN RULE: a lane writes one grain, the RADNET_PNG_JOIN_GRAIN bytes between two 16-byte boundaries of DEVICE MEMORY, clipped
+ * to [out, out + n); a workgroup takes a span of RADNET_PNG_JOIN_SPAN_GRAINS grains (4096 bytes).  With out standing `misalign`
+ * bytes behind a boundary there are ceil((misalign + n) / 16) grains; only the first and the last can be clipped. */
+#define RADNET_PNG_JOIN_GRAIN 16
+#define RADNET_PNG_JOIN_SPAN_GRAINS 256
+#define RADNET_PNG_JOIN_MAX_SPANS 2147483647
+typedef struct radnet_png_join_plan {
+  int64_t grains; /* ceil((misalign + n) / RADNET_PNG_JOIN_GRAIN); 0 for n == 0 */
+  int64_t spans;  /* ceil(grains / RADNET_PNG_JOIN_SPAN_GRAINS): the workgroups of the launch */
+} radnet_png_join_plan;
+/* Host only (csrc/png_join_plan.cpp; no context, no device): the validation and the span count radnet_png_join_u8 runs before it
+ * launches.  table: `count` pieces in HOST memory of a file of file_len bytes, for an output of n bytes whose first byte stands
+ * `misalign` (0..15) bytes behind a 16-byte boundary.  RADNET_ERR_ARG, with the reason in msg (msg_cap bytes; may be null) and the
+ * first bad entry's index in *bad_entry (-1 when the arguments themselves are refused, and for a total that is not n; may be null):
+ * a null plan, count < 0, file_len < 0, n < 0, misalign outside 0..15, a null table with count > 0; a piece with src < 0, length < 0
+ * or src + length > file_len (checked without overflow); a piece whose dst is not the sum of the lengths in front of it, or whose
+ * end passes n; a total length other than n.  More than RADNET_PNG_JOIN_MAX_SPANS spans is RADNET_ERR_UNSUPPORTED.  *plan is
+ * written on RADNET_OK only. */
+int radnet_png_plan_join(const radnet_png_piece* table, int32_t count, int64_t file_len, int64_t n, int32_t misalign,
+                         radnet_png_join_plan* plan, int32_t* bad_entry, char* msg, int32_t msg_cap);
+/* out[0 .. n) = the pieces of file[0 .. file_len) joined, as above.  file and out are device buffers at any byte address;
+ * table_host and table_dev hold the SAME table on the host and on the device (the caller uploads it, as for
+ * radnet_crc32_segments); table_dev is 8-byte aligned.
+ * The host table is validated before anything is launched (radnet_png_plan_join, with its message); a null ctx, a null pointer that
+ * the counts do not excuse (file, out and table_dev with n > 0, table_host with count > 0), a misaligned table_dev, and
+ * [out, out + n) overlapping [file, file + file_len) are RADNET_ERR_ARG too.  Nothing is written on a refusal.  n == 0 (with any
+ * count of empty pieces) is RADNET_OK without a launch.
+ * Otherwise ONE launch of plan.spans workgroups.  A lane finds the piece of its grain's first byte p by bisection over dst -- the
+ * last k with dst_k <= p, which steps over empty pieces -- takes that piece's bytes up to the grain's end, and bisects again, from
+ * the next entry on, whenever the grain goes on into the next non-empty piece: at most 16 bisections of log2(count) steps and 16
+ * bytes per lane, so a run of thousands of empty pieces costs one more bisection and never a walk.  Every byte of out[0 .. n) is
+ * written by exactly one lane, and no byte outside is written: a full grain is one aligned 16-byte store, a clipped one (the
+ * first, the last) byte stores.  The file is read byte by byte, and no load touches a byte outside file[0 .. file_len).  No scratch
+ * memory, no atomics, no flags; no workgroup waits on another. */
+int radnet_png_join_u8(radnet_ctx* ctx, const uint8_t* file, int64_t file_len, const radnet_png_piece* table_host,
+                       const radnet_png_piece* table_dev, int32_t count, uint8_t* out, int64_t n);
 /* Rectangles painted into a uint8 [h][w][3] device image (rows pitch_bytes apart) IN PLACE.  The contract is this package's own:
  *   the corners (x1, y1), (x2, y2) come in either order, as cv2.rectangle takes them, and are normalised to x1 <= x2, y1 <= y2;
  *   thickness < 0 (cv2.FILLED): pixel (x, y) is painted iff x1 <= x <= x2 and y1 <= y <= y2;

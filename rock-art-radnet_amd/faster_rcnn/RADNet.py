@@ -94,6 +94,7 @@ class RADNet():
     device_resident = True      # engine-backed models: keep tiles on the device between the stages (see _detect)
     device_tail = True          # ... and decode + per-class NMS + source-pixel coordinates too (see _tail_on_device)
     png_unfilter = "band"       # predict_from_path: "tiles" reconstructs the maps' adaptive-filter rows on all CUs (png.decode_device(unfilter=))
+    png_join = "host"           # predict_from_path: "device" joins the maps' IDAT payloads on the device (png.decode_device(join=); needs a device png_inflate)
     png_crc = "host"            # predict_from_path: "device" sums the maps' IDAT CRC-32s on the device (png.decode_device(crc=); needs a device png_inflate)
     png_inflate = "host"        # predict_from_path: "device" / "device-lz" inflate the maps' IDAT streams on the device (png.decode_device(inflate=))
     scan_tail = False           # ... and the merge of a scan's tiles: final_nms per image, NMS across images (see _scan_tail_on)
@@ -594,7 +595,8 @@ class RADNet():
         `png_inflate = "device"` or `"device-lz"` is handed to get_image as inflate=: the same images, inflated on the device where
         the file allows (run-length streams, or any deflate stream).  `png_unfilter = "tiles"` is handed on as unfilter=: the same
         images, their scanlines reconstructed by tiles.  `png_crc = "device"` is handed on as crc=: the IDAT chunks' CRC-32 summed on
-        the device (with `png_inflate = "host"` that is png.decode_device's ValueError)."""
+        the device (with `png_inflate = "host"` that is png.decode_device's ValueError).  `png_join = "device"` is handed on as join=:
+        the file goes up as it is and its IDAT payloads are joined on the device (the same rule)."""
         from . import utils_io
         C = self.C
         to_host = not self._takes_device_images()
@@ -603,6 +605,8 @@ class RADNet():
             how["unfilter"] = self.png_unfilter
         if self.png_crc != "host":
             how["crc"] = self.png_crc
+        if self.png_join != "host":
+            how["join"] = self.png_join
         if C.use_img_type:
             images = [utils_io.get_image(img_path, [img_type], random_type=False, to_host=to_host, **how) for img_type in C.img_types]
         else:

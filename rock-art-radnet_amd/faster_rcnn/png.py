@@ -20,6 +20,8 @@ decode_device(inflate="device-lz") does so for any deflate stream (csrc/inflate_
 source position, pointer jumping flattens the sources, a gather copies each byte from its root.
 decode_device(unfilter="tiles"), and decode_device_many likewise, reconstructs rows of Up / Average / Paeth type, which allow no
 segment cut, on all CUs (csrc/png_tiles.hip): tiles of 64 rows by TILE_PIXELS pixels, one launch per sweep of independent tiles.
+decode_device(join="device"), beside a device inflate, uploads the FILE as it is instead of the joined IDAT payloads, and
+radnet_png_join_u8 (csrc/png_join.hip) gathers the zlib stream on the device in one launch, a lane per 16-byte grain of the output.
 
 Every leg of the read side goes through the same few statements: the container's structure is _chunks (parse sums each chunk's
 CRC as the walk yields it, parse_compressed takes the whole walk first); where the streams, the palettes, a table and the device's
@@ -242,11 +244,19 @@ INFLATE_LZ_CHAIN = INFLATE_CHAIN + ("a match that reaches in front of the stream
 # container, geometry and the compressed IDAT stream of a file: staged is a pinned uint8 tensor that holds the n bytes of the zlib
 # stream and, behind them, the 768 bytes of the palette; expected is the length of the inflated stream the geometry asks for
 # crc_segments (parse_compressed(crc="device") alone, else None): the radnet_crc32_segment table of the IDAT chunks over the joined stream
-Compressed = collections.namedtuple("Compressed", "header palette passes bpp expected staged n crc_segments", defaults=(None,))
+# trailer: the Adler-32 the zlib stream ends in, as an integer
+# file_len, pieces (parse_compressed(join="device") alone, else None): staged then holds the WHOLE FILE, file_len bytes, in front of
+# the palette, and the radnet_png_piece table of its IDAT payloads behind it (join_layout); the n bytes of the stream exist on the
+# device only, once radnet_png_join_u8 has gathered them
+Compressed = collections.namedtuple("Compressed", "header palette passes bpp expected staged n crc_segments file_len pieces trailer",
+                                    defaults=(None, None, None, None))
 CRC_SEGMENT = np.dtype([("offset", np.int64), ("length", np.int64), ("init", np.uint32), ("expect", np.uint32)])      # radnet_crc32_segment, 24 bytes
 INFLATE_MODES = ("host", "device", "device-lz")
 CRC_MODES = ("host", "device")
+JOIN_MODES = ("host", "device")
+JOIN_PIECE = np.dtype([("src", np.int64), ("dst", np.int64), ("length", np.int64)])      # radnet_png_piece, 24 bytes
 Staging = collections.namedtuple("Staging", "palettes pad table sums result total")      # staging_layout
+JoinStaging = collections.namedtuple("JoinStaging", "palettes pad pieces table sums result total")      # staging_layout(pieces=)
 
 
 def _check_crc(crc):
@@ -254,10 +264,15 @@ def _check_crc(crc):
         raise ValueError("PNG: crc=%r (\"host\" or \"device\")" % (crc,))
 
 
-def check_modes(inflate="host", unfilter="band", crc="host"):
+def _check_join(join):
+    if join not in JOIN_MODES:
+        raise ValueError("PNG: join=%r (\"host\" or \"device\")" % (join,))
+
+
+def check_modes(inflate="host", unfilter="band", crc="host", join="host"):
     """The legal values of the modes of decode_device, and of whoever hands them on to it (decode_device_many,
-    utils_io.DeviceImageLoader), stated once: ValueError for an inflate, unfilter or crc that is none of them, and for crc="device"
-    without a device inflate."""
+    utils_io.DeviceImageLoader), stated once: ValueError for an inflate, unfilter, crc or join that is none of them, and for
+    crc="device" or join="device" without a device inflate."""
     if inflate not in INFLATE_MODES:
         raise ValueError("PNG: inflate=%r (\"host\", \"device\" or \"device-lz\")" % (inflate,))
     if unfilter not in UNFILTER_MODES:
@@ -265,18 +280,29 @@ def check_modes(inflate="host", unfilter="band", crc="host"):
     _check_crc(crc)
     if crc == "device" and inflate == "host":
         raise ValueError("PNG: crc=\"device\" sums the uploaded IDAT stream and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\"")
+    _check_join(join)
+    if join == "device" and inflate == "host":
+        raise ValueError("PNG: join=\"device\" joins the IDAT stream of the uploaded file and needs inflate=\"device\" or \"device-lz\", not inflate=\"host\"")
 
 
-def staging_layout(n, palettes=1, record=0, count=0, sums=False):
+def staging_layout(n, palettes=1, record=0, count=0, sums=False, pieces=None):
     """Where everything stands in the ONE pinned buffer a decode uploads, as Staging(palettes, pad, table, sums, result, total) byte
     offsets: the n bytes of the stream(s), `palettes` palettes of 768 bytes, the pad up to the next multiple of 8, a table of
     `count` records of `record` bytes (SEGMENT or CRC_SEGMENT) and, with sums, the `count` sums and the 2 result words the device
     writes into the uploaded copy (radnet_crc32_segments).  Without a table (record 0) nothing is padded and nothing follows the
-    palettes."""
+    palettes.
+    pieces (join="device": n is then the length of the whole FILE, which stands where the stream stands otherwise): a table of that
+    many JOIN_PIECE records stands behind the pad, 8-byte aligned, in front of the other table, which follows it without a gap;
+    the result is JoinStaging(palettes, pad, pieces, table, sums, result, total)."""
     pad = n + 768 * palettes
-    table = (pad + 7) & ~7 if record else pad
+    if pieces is None:
+        table = (pad + 7) & ~7 if record else pad
+    else:
+        at = (pad + 7) & ~7
+        table = at + JOIN_PIECE.itemsize * pieces      # a multiple of 8 again
     result = table + record * count + (4 * count if sums else 0)
-    return Staging(n, pad, table, table + record * count, result, result + (8 if sums else 0))
+    rest = (table, table + record * count, result, result + (8 if sums else 0))
+    return Staging(n, pad, *rest) if pieces is None else JoinStaging(n, pad, at, *rest)
 
 
 def _stage_table(host, at, table):
@@ -294,7 +320,41 @@ def crc_layout(n, count):
     return at.table, at.sums, at.result, at.total
 
 
-def parse_compressed(data, crc="host"):
+def join_pieces(idat):
+    """The JOIN_PIECE table (radnet_png_piece) of the chunk walk's IDAT payloads, a list of (start, end) file offsets: src = start,
+    length = end - start, dst = the sum of the lengths in front -- zero-length chunks keep their entries."""
+    table = np.zeros(len(idat), JOIN_PIECE)
+    if len(idat):
+        bounds = np.asarray(idat, np.int64).reshape(-1, 2)
+        table["src"], table["length"] = bounds[:, 0], bounds[:, 1] - bounds[:, 0]
+        table["dst"] = np.cumsum(table["length"]) - table["length"]
+    return table
+
+
+def joined_bytes(source, pieces, a, b):
+    """Bytes [a, b) of the joined stream, gathered from the file's bytes `source` (uint8 array) through the JOIN_PIECE table `pieces`
+    without joining anything else: the zlib header and the Adler-32 trailer, either of which may straddle chunks."""
+    out = bytearray()
+    k = int(np.searchsorted(pieces["dst"], a, side="right")) - 1      # the last piece with dst <= a
+    while a < b and 0 <= k < len(pieces):
+        src, dst, length = (int(v) for v in pieces[k])
+        take = min(b, dst + length) - a
+        if take > 0:
+            out += source[src + a - dst:src + a - dst + take].tobytes()
+            a += take
+        k += 1
+    return bytes(out)
+
+
+def join_layout(comp):
+    """The staging_layout of a Compressed record, whichever modes parse_compressed ran in."""
+    record, count, sums = (0, 0, False) if comp.crc_segments is None else (CRC_SEGMENT.itemsize, len(comp.crc_segments), True)
+    if comp.pieces is None:
+        return staging_layout(comp.n, 1, record, count, sums=sums)
+    return staging_layout(comp.file_len, 1, record, count, sums=sums, pieces=len(comp.pieces))
+
+
+def parse_compressed(data, crc="host", join="host"):
     """The container walk of parse() WITHOUT the inflate: Compressed(header, palette, passes, bpp, expected, staged, n).  The IDAT
     payloads are joined directly into the pinned staging buffer (the palette rides behind them, as in decode_device); the chunk
     CRCs are summed on up to 8 host threads (fixed, like MANY_DEFAULT_WORKERS: one thread's zlib.crc32 over a 35 MB map would be
@@ -303,8 +363,15 @@ def parse_compressed(data, crc="host"):
     crc="device": the sums of the IDAT chunks are left to radnet_crc32_segments -- every other chunk is still summed here -- and
     the result carries crc_segments, one CRC_SEGMENT per IDAT chunk (zero-length ones too) over the JOINED stream: offset where the
     chunk's payload starts in it, its length, init = zlib.crc32(b"IDAT"), expect = the chunk's CRC field.  The staging buffer
-    then holds the table behind the palette and room for the sums and the result (crc_layout)."""
+    then holds the table behind the palette and room for the sums and the result (crc_layout).
+    join="device": nothing is joined here.  The staging buffer holds the WHOLE FILE, copied in one piece, then the palette, the pad,
+    the JOIN_PIECE table of the IDAT payloads (join_pieces) and, for crc="device", the CRC table, the sums and the result
+    (staging_layout(pieces=), join_layout); radnet_png_join_u8 gathers the stream behind the upload.  The walk, the checks and
+    their order are the same; the host's CRC sums run on the caller's bytes; the zlib header and the trailer are read through the
+    table (joined_bytes); the CRC segments stay offsets into the joined stream.  The result carries file_len, pieces and, in
+    both modes, trailer."""
     _check_crc(crc)
+    _check_join(join)
     import concurrent.futures
     import torch
     view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, np.uint8)).cast("B")
@@ -324,11 +391,12 @@ def parse_compressed(data, crc="host"):
             return _crc_ok(view, at + 8, end)      # one call per chunk
         return _crc32_threads(view[at + 8:end], zlib.crc32(kind), workers=workers) == int.from_bytes(view[end:end + 4], "big")
     n = sum(e - s for s, e in idat)
-    on_device = crc == "device"
+    on_device, join_device = crc == "device", join == "device"
     small_file = sum(e - at for _, at, e in jobs) < 1 << 20
     if on_device:
         jobs = [j for j in jobs if j[0] != b"IDAT"]
-    lay = staging_layout(n, 1, CRC_SEGMENT.itemsize, len(idat), sums=True) if on_device else staging_layout(n)
+    record, count = (CRC_SEGMENT.itemsize, len(idat)) if on_device else (0, 0)
+    lay = staging_layout(len(view) if join_device else n, 1, record, count, sums=on_device, pieces=len(idat) if join_device else None)
     staged = torch.empty(lay.total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
     host = staged.numpy()
     source = np.frombuffer(view, np.uint8)
@@ -337,9 +405,13 @@ def parse_compressed(data, crc="host"):
     def join(k):
         s, e = idat[k]
         host[starts[k]:starts[k] + e - s] = source[s:e]
+    to_join = len(idat)
+    if join_device:
+        host[:len(source)] = source      # the file as it is, in one copy: the device gathers the payloads
+        to_join = 0
     if small_file:
         oks = {j: crc_ok(j) for j in jobs}
-        for k in range(len(idat)):
+        for k in range(to_join):
             join(k)
     else:
         # a chunk of 4 MiB or more is cut into ranges summed on host threads (one large IDAT: this package's writer); the others
@@ -354,24 +426,36 @@ def parse_compressed(data, crc="host"):
             if bad < 0:
                 raise RuntimeError("PNG: radnet_png_check_crcs failed (%d)" % bad)
             oks.update((j, k < bad) for k, j in enumerate(small))      # chunks behind the first bad one are not looked at: it is reported
-        with concurrent.futures.ThreadPoolExecutor(max_workers=MANY_DEFAULT_WORKERS) as pool:
-            list(pool.map(lambda g: [join(k) for k in range(g, len(idat), MANY_DEFAULT_WORKERS)], range(min(len(idat), MANY_DEFAULT_WORKERS))))
+        if to_join:
+            with concurrent.futures.ThreadPoolExecutor(max_workers=MANY_DEFAULT_WORKERS) as pool:
+                list(pool.map(lambda g: [join(k) for k in range(g, to_join, MANY_DEFAULT_WORKERS)], range(min(to_join, MANY_DEFAULT_WORKERS))))
     for kind, at, end in jobs:
         if not oks[(kind, at, end)]:
             raise _crc_mismatch(kind, at + 8)
     host[lay.palettes:lay.pad] = palette.reshape(-1)
-    segments = None
+    segments = pieces = None
+    if join_device:
+        pieces = join_pieces(idat)
+        host[lay.pad:lay.pieces] = 0
+        host[lay.pieces:lay.table] = pieces.view(np.uint8)
     if on_device:
         segments = np.zeros(len(idat), CRC_SEGMENT)
         segments["offset"] = starts[:-1]
         segments["length"] = [e - s for s, e in idat]
         segments["init"] = zlib.crc32(b"IDAT")
         segments["expect"] = [int.from_bytes(view[e:e + 4], "big") for _, e in idat]
-        _stage_table(host, lay, segments)
-    if n < 2 or host[0] & 15 != 8 or host[0] >> 4 > 7 or (int(host[0]) * 256 + int(host[1])) % 31 or host[1] & 32:
+        if join_device:      # the CRC table follows the piece table without a gap
+            host[lay.table:lay.sums] = segments.view(np.uint8)
+            host[lay.sums:lay.total] = 0
+        else:
+            _stage_table(host, lay, segments)
+    head = joined_bytes(source, pieces, 0, 2) if join_device else host[:min(n, 2)].tobytes()
+    if n < 2 or head[0] & 15 != 8 or head[0] >> 4 > 7 or (head[0] * 256 + head[1]) % 31 or head[1] & 32:
         raise ValueError("PNG: the IDAT stream has no zlib header the device inflate takes (deflate, a window of at most 32 KiB, FCHECK, no dictionary)")
     passes, expected = pass_geometry(header)
-    return Compressed(header, palette, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8), expected, staged, n, segments)
+    tail = joined_bytes(source, pieces, max(n - 4, 0), n) if join_device else host[max(n - 4, 0):n].tobytes()
+    return Compressed(header, palette, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8), expected, staged, n, segments,
+                      len(source) if join_device else None, pieces, int.from_bytes(tail, "big"))
 
 
 def _lap(report, name):
@@ -518,7 +602,7 @@ def _checked_stream(comp, ctx, report, stream):
     """`stream` (the inflated bytes on the device) once its Adler-32, summed there, equals the zlib trailer, else None with the
     reason "adler"; the filter-type column comes back as report["column"].  One sync."""
     import torch
-    n, expected = comp.n, comp.expected
+    expected = comp.expected
     chunks = -(-expected // _constant("RADNET_DEFLATE_CHUNK"))
     rows = sum(p.pass_h for p in comp.passes)
     tail = torch.zeros(DEFLATE_SYMBOLS * 4 + chunks * 16 + rows, dtype=torch.uint8, device="cuda")      # counts (not used), Adler parts, column
@@ -531,8 +615,7 @@ def _checked_stream(comp, ctx, report, stream):
     tail_host = tail.cpu().numpy()
     _lap(report, "download_adler_column_ms")
     parts = tail_host[DEFLATE_SYMBOLS * 4:DEFLATE_SYMBOLS * 4 + chunks * 16].view(np.uint64)
-    trailer = struct.unpack(">I", comp.staged.numpy()[n - 4:n].tobytes())[0]
-    if adler32_of_parts(parts, expected) != trailer:
+    if adler32_of_parts(parts, expected) != comp.trailer:
         report["reason"] = "adler"
         return None
     report["column"] = tail_host[DEFLATE_SYMBOLS * 4 + chunks * 16:]
@@ -587,7 +670,7 @@ def _expand_passes(call, header, passes, base, palette, out):
              header.height, header.width, p.y0, p.x0, p.dy, p.dx)
 
 
-def _report_host_path(report, inflate, unfilter, crc):
+def _report_host_path(report, inflate, unfilter, crc, join="host"):
     """What the report says of a file the host path decodes, with the keys of the active modes; reason and candidates are not
     touched: after a refusal they say why, and what the device search had found."""
     report.update(path="host", false_candidates=0, units=0, blocks=0, reconstruction=None)
@@ -597,18 +680,26 @@ def _report_host_path(report, inflate, unfilter, crc):
         report["sweeps"] = 0
     if crc == "device":
         report["crc"] = "host"
+    if join == "device":
+        report["join"] = "host"
 
 
-def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_device=False):
+def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_device=False, join_device=False):
     """decode_device's device inflate (lz: the one for any stream): the image, or None when the host path has to take the file
     (report["reason"]).  tiles: unfilter="tiles" -- segments of at most 64 rows go to radnet_png_unfilter_segments_u8, all longer ones
     to radnet_png_unfilter_tiles_u8, whether or not the segments spread the passes.  crc_device: crc="device" -- the IDAT chunks' sums
-    come from radnet_crc32_segments, and a mismatch is the reason "crc: IDAT chunk k"."""
+    come from radnet_crc32_segments, and a mismatch is the reason "crc: IDAT chunk k".  join_device: join="device" -- the whole file goes
+    up and radnet_png_join_u8 gathers the stream into a buffer of its own, which the CRC and the inflate entries then take; the
+    launches stand on the context's stream in that order, join, CRC, search."""
     import torch
+    from radnet_hip.lib import RadnetError
     from . import augmentation_device as AD
     _lap(report, "_skip")
     try:
-        comp = parse_compressed(data, crc="device") if crc_device else parse_compressed(data)
+        if join_device:
+            comp = parse_compressed(data, crc="device" if crc_device else "host", join="device")
+        else:
+            comp = parse_compressed(data, crc="device") if crc_device else parse_compressed(data)
     except ValueError as e:
         report["reason"] = "container: %s" % e
         return None
@@ -616,16 +707,27 @@ def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_dev
     with AD.feed_stream(ctx) as (ctx, side):
         dev = comp.staged.cuda(non_blocking=True)
         _lap(report, "upload_ms")
+        at = join_layout(comp)
+        zdev = dev                               # what holds the zlib stream at its byte 0
+        if join_device:
+            zdev = torch.empty(max(comp.n, 1), dtype=torch.uint8, device="cuda")
+            try:
+                _launch(report, ctx, "radnet_png_join_u8", dev.data_ptr(), comp.file_len, comp.staged.data_ptr() + at.pieces, dev.data_ptr() + at.pieces,
+                        len(comp.pieces), zdev.data_ptr(), comp.n)
+            except RadnetError as e:
+                report["reason"] = "join: %s" % e
+                return None
+            report["join"] = "device"
         if crc_device:
             # the IDAT sums right behind the upload: the table stands behind the palette, the sums and the result go into the uploaded
             # copy, and the 8 bytes of the result are on their way down before the search starts -- its first download delivers them
             count = len(comp.crc_segments)
-            table_at, sums_at, result_at, _ = crc_layout(comp.n, count)
-            _launch(report, ctx, "radnet_crc32_segments", dev.data_ptr(), comp.n, comp.staged.data_ptr() + table_at, dev.data_ptr() + table_at, count,
+            table_at, sums_at, result_at = at.table, at.sums, at.result
+            _launch(report, ctx, "radnet_crc32_segments", zdev.data_ptr(), comp.n, comp.staged.data_ptr() + table_at, dev.data_ptr() + table_at, count,
                     dev.data_ptr() + sums_at, dev.data_ptr() + result_at)
             verdict = torch.empty(2, dtype=torch.int32, pin_memory=True)
             verdict.copy_(dev[result_at:result_at + 8].view(torch.int32), non_blocking=True)
-        stream = (_inflate_device_lz if lz else _inflate_device)(comp, dev, ctx, report)
+        stream = (_inflate_device_lz if lz else _inflate_device)(comp, zdev, ctx, report)
         if crc_device:
             if stream is None:
                 torch.cuda.current_stream().synchronize()      # a refusal may come before the first download; the host path is next anyway
@@ -642,7 +744,7 @@ def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_dev
             return None
         h = comp.header
         out = torch.empty((h.height, h.width, 3), dtype=torch.uint8, device="cuda")
-        base, palette = stream.data_ptr(), dev.data_ptr() + comp.n
+        base, palette = stream.data_ptr(), dev.data_ptr() + at.palettes
         call = functools.partial(_launch, report, ctx)
         # segments when they spread a pass over the device: the longest is at most half its pass
         tables, row0, spread = [], 0, True
@@ -674,7 +776,7 @@ def _decode_inflated_on_device(data, ctx, report, lz=False, tiles=False, crc_dev
     return AD.hand_over(out, side)
 
 
-def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band", crc="host"):
+def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band", crc="host", join="host"):
     """The decoded image as a uint8 [H][W][3] (B, G, R) cuda tensor: parse, ONE pinned upload of the inflated stream (the palette
     rides behind it), then reconstruction and expansion per pass.  ctx: a radnet context whose stream is torch's current one;
     None = the calling thread's default context, on a BackgroundFeed worker thread on that thread's own stream.
@@ -705,19 +807,28 @@ def decode_device(data, ctx=None, inflate="host", report=None, unfilter="band", 
     of the file, is summed on the uploaded stream by radnet_crc32_segments (csrc/crc32.hip) right behind the upload instead of on
     host threads in front of it; the other chunks are summed on the host as before.  The verdict comes down with the search's
     candidates.  A mismatch sends the file to the host path (reason "crc: IDAT chunk k"), which raises the default's ValueError.
-    In this mode alone the report carries crc: "device" when the sums were checked there, "host" when the host path took the file."""
+    In this mode alone the report carries crc: "device" when the sums were checked there, "host" when the host path took the file.
+    join="device" (opt-in; needs a device inflate, with inflate="host" it is a ValueError): the IDAT payloads are not joined on the
+    host.  The file's bytes go into the pinned buffer in ONE copy and up as they are -- the palette, the table of the payloads
+    (join_pieces) and, for crc="device", the CRC table ride behind them --, and ONE launch, radnet_png_join_u8 (csrc/png_join.hip),
+    gathers the zlib stream into a device buffer of its own, which the CRC sums and the search then take: join, CRC, search, in
+    that order on the context's stream.  The container's checks, their order and their ValueErrors are the default's.  In this
+    mode alone the report carries join: "device" when the stream was joined there, "host" when the host path took the file."""
     import torch
     from . import augmentation_device as AD
-    check_modes(inflate, unfilter, crc)
+    check_modes(inflate, unfilter, crc, join)
     tiles = unfilter == "tiles"
     report = {} if report is None else report
     report.update(reason=None, candidates=0)
-    _report_host_path(report, inflate, unfilter, crc)
+    _report_host_path(report, inflate, unfilter, crc, join)
     if inflate != "host":
-        out = _decode_inflated_on_device(data, ctx, report, lz=inflate == "device-lz", tiles=tiles, crc_device=crc == "device")
+        if join == "device":
+            out = _decode_inflated_on_device(data, ctx, report, lz=inflate == "device-lz", tiles=tiles, crc_device=crc == "device", join_device=True)
+        else:
+            out = _decode_inflated_on_device(data, ctx, report, lz=inflate == "device-lz", tiles=tiles, crc_device=crc == "device")
         if out is not None:
             return out
-        _report_host_path(report, inflate, unfilter, crc)
+        _report_host_path(report, inflate, unfilter, crc, join)
         report.pop("column", None)
     img = parse(data)
     n = len(img.stream)
@@ -772,7 +883,8 @@ def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
     work.  Then ONE pinned staging buffer and ONE upload: the streams, the palettes, the segment table (8-byte aligned, short
     segments first inside each bpp); one radnet_png_unfilter_segments_u8 per distinct bpp; one radnet_png_expand_bgr_u8 per pass.
     ctx and the stream rules are decode_device's.  unfilter="tiles": inside each bpp the segments of at most 64 rows go as above and
-    the longer ones to one radnet_png_unfilter_tiles_u8; the bytes are the same."""
+    the longer ones to one radnet_png_unfilter_tiles_u8; the bytes are the same.  The files inflate on the host, which needs each
+    stream there: this entry takes no join= (decode_device's join="device" needs a device inflate)."""
     import concurrent.futures
     import torch
     from . import augmentation_device as AD

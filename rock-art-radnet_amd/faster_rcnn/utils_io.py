@@ -19,14 +19,15 @@ def image_path(img_path, img_type):
     return os.path.join(*parts)
 
 
-def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, inflate="host", unfilter="band", crc="host"):
+def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, inflate="host", unfilter="band", crc="host", join="host"):
     """utils.get_image, draw for draw: types[0], or with random_type one rng.choice(types, 1, p=probs)[0] where the first type has
     probability 0.5 (up to three types) or 0.3 and the others share the rest.  Returns the uint8 BGR HWC image as a NumPy array,
     or with to_host=False as a cuda tensor (nothing is downloaded).  inflate="device" inflates the file's IDAT stream on the device
     (png.decode_device: run-length streams; anything else takes the host path as before), inflate="device-lz" does so for a stream
     with matches at any distance; another value is png.decode_device's ValueError.  unfilter="tiles" reconstructs the scanlines by
     tiles on all CUs (png.decode_device: the same image); another value than "band" or "tiles" is its ValueError too.  crc="device"
-    sums the IDAT chunks' CRC-32 on the device (png.decode_device: needs a device inflate; with inflate="host" its ValueError)."""
+    sums the IDAT chunks' CRC-32 on the device (png.decode_device: needs a device inflate; with inflate="host" its ValueError).
+    join="device" uploads the file as it is and joins its IDAT payloads on the device (png.decode_device: the same rule)."""
     img_type = types[0]
     if random_type:
         first_prob = 0.3
@@ -35,11 +36,13 @@ def get_image(img_path, types, random_type=False, rng=np.random, to_host=True, i
         probs = [first_prob] + [(1.0 - first_prob) / (len(types) - 1) for i in range(len(types) - 1)]
         img_type = rng.choice(types, 1, p=probs)[0]
     buf = np.fromfile(image_path(img_path, img_type), np.uint8)
-    if inflate == "host" and unfilter == "band" and crc == "host":
+    if inflate == "host" and unfilter == "band" and crc == "host" and join == "host":
         return png.imdecode_color(buf) if to_host else png.decode_device(buf)
     tiles = {} if unfilter == "band" else dict(unfilter=unfilter)      # the default call is the one it was
     if crc != "host":
         tiles["crc"] = crc
+    if join != "host":
+        tiles["join"] = join
     img = png.decode_device(buf, inflate=inflate, **tiles)
     return img.cpu().numpy() if to_host else img
 
@@ -65,13 +68,13 @@ class DeviceImageLoader:
     prefetch() fills the cache ahead of the calls, many files per decode (png.decode_device_many): the types of a scan, the next
     images of a feed.  The cache holds one decoder's images: with decode= set and decode_many= not, prefetch decodes through
     decode, file by file.  unfilter="tiles" is handed to the default decoders of both (png.decode_device and decode_many's
-    unfilter=); a decoder of the caller's is called as it is.  inflate= and crc= are handed to the default png.decode_device of
-    __call__ in the same way (crc="device" needs inflate="device" or "device-lz": png.decode_device's ValueError, raised here);
-    decode_many keeps the host parse and takes neither."""
+    unfilter=); a decoder of the caller's is called as it is.  inflate=, crc= and join= are handed to the default png.decode_device
+    of __call__ in the same way (crc="device" and join="device" need inflate="device" or "device-lz": png.decode_device's
+    ValueError, raised here); decode_many keeps the host parse and takes none of them, so prefetch is unchanged."""
 
-    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band", inflate="host", crc="host"):
-        png.check_modes(inflate, unfilter, crc)
-        self.unfilter, self.inflate, self.crc = unfilter, inflate, crc
+    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band", inflate="host", crc="host", join="host"):
+        png.check_modes(inflate, unfilter, crc, join)
+        self.unfilter, self.inflate, self.crc, self.join = unfilter, inflate, crc, join
         self.cache_bytes = int(cache_bytes)
         self.decode = decode                       # (file bytes as uint8 array) -> image; default: png.decode_device
         # (list of file bytes) -> list of images, for prefetch; default: png.decode_device_many, or `decode` on each file if that is set
@@ -156,6 +159,8 @@ class DeviceImageLoader:
                 how["inflate"] = self.inflate
             if self.crc != "host":
                 how["crc"] = self.crc
+            if self.join != "host":
+                how["join"] = self.join
             img = png.decode_device(buf, **how)
         self._insert(key, img)
         return img

@@ -326,6 +326,8 @@ def load_library():
         "radnet_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, i64]),
         "radnet_crc32_plan_segments": (C.c_int, [vp, i32, i64, i32, vp, C.POINTER(i32), C.c_char_p, i32]),
         "radnet_crc32_segments": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp]),
+        "radnet_png_plan_join": (C.c_int, [vp, i32, i64, i64, i32, vp, C.POINTER(i32), C.c_char_p, i32]),
+        "radnet_png_join_u8": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, i64]),
         "radnet_draw_rects_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32]),
         "radnet_draw_list_u8": (C.c_int, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, i32]),
         "radnet_draw_glyph_rows": (C.c_int, [i32, vp]),
@@ -428,6 +430,18 @@ def crc32_plan_segments(table, n, misalign=0, count=None):
     plan, bad, msg = (C.c_int64 * 2)(-1, -1), C.c_int32(-2), C.create_string_buffer(256)
     rc = load_library().radnet_crc32_plan_segments(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(n),
                                                    int(misalign), C.cast(plan, C.c_void_p), C.byref(bad), msg, len(msg))
+    return rc, plan[0], plan[1], bad.value, msg.value.decode()
+
+
+def png_plan_join(table, file_len, n, misalign=0, count=None):
+    """radnet_png_plan_join (host only, no context, no device) on a table of radnet_png_piece rows -- a NumPy array of 24 bytes per
+    entry, or None for a null table -- of a file of file_len bytes, for an output of n bytes that stands `misalign` bytes behind a
+    16-byte boundary: (rc, grains, spans, index of the bad entry or -1, the message).  count defaults to the table's length."""
+    import numpy as np
+    rows = np.zeros((0, 24), np.uint8) if table is None else np.ascontiguousarray(table).view(np.uint8).reshape(-1, 24)
+    plan, bad, msg = (C.c_int64 * 2)(-1, -1), C.c_int32(-2), C.create_string_buffer(256)
+    rc = load_library().radnet_png_plan_join(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(file_len), int(n),
+                                             int(misalign), C.cast(plan, C.c_void_p), C.byref(bad), msg, len(msg))
     return rc, plan[0], plan[1], bad.value, msg.value.decode()
 
 
