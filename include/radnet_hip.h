@@ -833,6 +833,66 @@ int radnet_inflate_lz_resolve(radnet_ctx* ctx, uint32_t* src, int64_t out_len, i
 /* s = src[i]; if (s < i) buf[i] = buf[s], one thread per position, IN PLACE: race-free once src is flat, because a root is never
  * written; memory-safe on any content of src.  Refusals as radnet_inflate_lz_resolve's. */
 int radnet_inflate_lz_gather(radnet_ctx* ctx, const uint32_t* src, uint8_t* buf, int64_t out_len);
+/* ---- inflate of MANY streams in one pass (csrc/inflate_many.hip, csrc/inflate_plan.cpp) -----------------------------------------
+ * The two sections above for a batch of zlib streams that stand in ONE device buffer z[0 .. z_len) and inflate into ONE output
+ * out[0 .. out_len): one search, one measure and one emit serve the batch, and radnet_inflate_lz_resolve / radnet_inflate_lz_gather
+ * run as they are on the common src / buf.  The stream table says where each stream stands; it lives on the host (validated before
+ * any launch) and on the device (the SAME table, uploaded by the caller, 8-byte aligned) like the segment and piece tables.
+ * THE BOUNDARY RULE: a bit, a unit or a link belongs to the stream whose bytes [z_offset, z_offset + n) hold its (start) bit, and
+ * to no stream when it stands in a gap.  THE READING RULE's 8 * n is that stream's end: bits behind it read as zero and end the
+ * header or the unit with PAST_END, whatever stands in the gap or in the next stream.  Bit offsets are GLOBAL, 8 * z_offset + p for
+ * bit p of the stream; output positions are absolute in `out`.  Per stream, every result is what the one-stream entry gives for
+ * that stream alone, shifted by 8 * z_offset and out_offset.  The host chain stays per stream (radnet_inflate_chain /
+ * radnet_inflate_lz_chain on the stream's slice of the sorted records with its bits shifted back; the links are shifted forward).
+ * The kernels are the one-stream ones (csrc/inflate_units_body.h); a wave finds its stream by bisection over the table. */
+typedef struct radnet_inflate_stream {
+  int64_t z_offset;    /* byte of z at which this zlib stream's byte 0 stands */
+  int64_t n;           /* its length in bytes, zlib header and Adler-32 included; 3 at least, as for one stream */
+  int64_t out_offset;  /* where its inflated bytes begin in the common output */
+  int64_t expected;    /* how many there are; 0 is legal */
+} radnet_inflate_stream; /* 32 bytes */
+#define RADNET_INFLATE_MANY_MAX_STREAMS 4096
+/* Host only (csrc/inflate_plan.cpp; no context, no device): the validation every _many entry runs before it launches.  The table
+ * must ascend in z_offset and in out_offset with disjoint ranges of both kinds (gaps are allowed: radnet_png_join_u8 writes 16-byte
+ * grains, so a caller may align its streams) that lie inside z_len / out_len.  RADNET_ERR_ARG, with the reason in msg (msg_cap
+ * bytes; may be null) and the first bad stream's index in *bad_stream (-1 when the arguments themselves are refused; may be null):
+ * a null table, count < 1 or > RADNET_INFLATE_MANY_MAX_STREAMS, z_len < 0, out_len < 0; a stream with z_offset < 0, n < 3,
+ * out_offset < 0 or expected < 0, or one that passes z_len or out_len (checked without overflow); a stream that begins in front
+ * of its predecessor (unsorted) or inside it (overlapping), in z or in the output.  z_len >= 2^29 (a global bit offset could pass
+ * 2^32) and out_len >= 2^31 (positions leave 31 bits) are RADNET_ERR_UNSUPPORTED, judged before the streams. */
+int radnet_inflate_streams_check(const radnet_inflate_stream* streams, int32_t count, int64_t z_len, int64_t out_len, int32_t* bad_stream,
+                                 char* msg, int32_t msg_cap);
+/* radnet_inflate_find_blocks over the batch, one thread per bit of z[0 .. z_len): a bit that lies in stream k is appended exactly
+ * when radnet_inflate_find_blocks(z + z_offset_k, n_k, first_bit = 16, ...) would append it, as the GLOBAL offset 8 * z_offset_k + p;
+ * "every bit read lies inside the stream" means inside stream k.  Bits in a gap are never appended.  A workgroup takes 256 bits:
+ * it bisects the device table once for the stream that holds or precedes its first byte, stages the few entries that can touch
+ * its 32 bytes in LDS (streams are 3 bytes at least), and each thread bisects those.  The append, cand_cap and *count are as
+ * there.  Refusals: radnet_inflate_streams_check's (out_len taken as the end of the last stream's output); a null pointer,
+ * cand_cap < 0 or a table_dev that is not 8-byte aligned is RADNET_ERR_ARG; nothing is launched then. */
+int radnet_inflate_find_blocks_many(radnet_ctx* ctx, const uint8_t* z, int64_t z_len, const radnet_inflate_stream* streams_host,
+                                    const radnet_inflate_stream* streams_dev, int32_t n_streams, uint32_t* cand, int32_t cand_cap, uint32_t* count);
+/* radnet_inflate_rle_measure / radnet_inflate_lz_measure over the batch: units[u].start_bit is GLOBAL; the unit's stream is the one
+ * that holds that bit, a start in a gap or behind z_len gives PAST_END; end_bit is GLOBAL; every other field is the one-stream
+ * entry's for the same unit of the same stream alone.  Refusals as above; count < 1 or a null table is RADNET_ERR_ARG. */
+int radnet_inflate_rle_measure_many(radnet_ctx* ctx, const uint8_t* z, int64_t z_len, const radnet_inflate_stream* streams_host,
+                                    const radnet_inflate_stream* streams_dev, int32_t n_streams, radnet_inflate_unit* units, int32_t count);
+int radnet_inflate_lz_measure_many(radnet_ctx* ctx, const uint8_t* z, int64_t z_len, const radnet_inflate_stream* streams_host,
+                                   const radnet_inflate_stream* streams_dev, int32_t n_streams, radnet_inflate_lz_unit* units, int32_t count);
+/* radnet_inflate_rle_emit / radnet_inflate_lz_emit over the batch: links[u].start_bit is GLOBAL and links[u].out_offset ABSOLUTE in
+ * out (buf) of out_len bytes.  Reading is bounded by the link's own stream (the one that holds its start bit; a link in a gap
+ * writes nothing).  Writing is bounded by the link's [out_offset, out_offset + out_bytes) AND by its stream's [out_offset,
+ * out_offset + expected): a link that begins outside its stream's output writes nothing.  LZ: src holds ABSOLUTE positions; a
+ * source that would fall in front of the stream's own out_offset is written as the position itself (the per-stream chain's REACH
+ * check makes that unreachable), so no byte of one stream is ever a copy of another's.  Refusals as above and as the one-stream
+ * entries' (streams_check is run against out_len). */
+int radnet_inflate_rle_emit_many(radnet_ctx* ctx, const uint8_t* z, int64_t z_len, const radnet_inflate_stream* streams_host,
+                                 const radnet_inflate_stream* streams_dev, int32_t n_streams, const radnet_inflate_link* links, int32_t count,
+                                 uint8_t* out, int64_t out_len);
+int radnet_inflate_lz_emit_many(radnet_ctx* ctx, const uint8_t* z, int64_t z_len, const radnet_inflate_stream* streams_host,
+                                const radnet_inflate_stream* streams_dev, int32_t n_streams, const radnet_inflate_link* links, int32_t count,
+                                uint8_t* buf, uint32_t* src, int64_t out_len);
+/* For a batch, radnet_crc32_segments is ONE launch group over the common z (its table takes any ranges of one buffer), and
+ * radnet_png_join_u8 is one launch PER FILE: its pieces tile out[0 .. n) from dst 0 on, so a file joins into z + z_offset. */
 /* The filter-type column of an inflated stream on the device: column[k] = stream[offset[p] + r * (1 + rowbytes[p])] for the rows r
  * of the passes p = 0 .. passes - 1 in order (k counts them through), one launch; offsets, rows and rowbytes are HOST arrays of
  * `passes` (1..7) entries that travel with the launch.  The pass must lie inside stream_len.  png.py downloads the column, refuses

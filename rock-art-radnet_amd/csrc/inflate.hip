@@ -15,12 +15,7 @@ __global__ void __launch_bounds__(256) inflate_find_kernel(const uint8_t* __rest
                                                            unsigned* __restrict__ count) {
   const u64 nbits = 8ull * (u64)n, p = first_bit + (u64)blockIdx.x * 256 + threadIdx.x;
   if (p >= nbits) return;
-  const GlobalBits bits{z, n};
-  const unsigned v = bits.peek(p);
-  if (((v >> 1) & 3) != 2 || ((v >> 3) & 31) > 29 || ((v >> 8) & 31) > 29) return;      // BTYPE, HLIT, HDIST: three offsets in four end here
-  u64 pos = p + 3;
-  int nlen, ndist;
-  if (parse_dynamic(bits, pos, nbits, [](int, int) {}, nlen, ndist) != RADNET_INFLATE_OK) return;
+  if (!dynamic_header_at(GlobalBits{z, n}, p, nbits)) return;
   const unsigned idx = atomicAdd(count, 1u);
   if (idx < (unsigned)cand_cap) cand[idx] = (unsigned)p;
 }

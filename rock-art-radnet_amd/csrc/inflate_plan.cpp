@@ -1,5 +1,6 @@
 // ---- host side of the device inflate (inflate.hip): the measured units -> the chain of units that is the stream ------------------
 // No device call and no HIP header: compiled by g++, runs without a GPU (contract: include/radnet_hip.h).
+#include <cstdio>
 #include <thread>
 #include <vector>
 
@@ -153,4 +154,53 @@ extern "C" int radnet_png_check_crcs(const uint8_t* file, int64_t file_len, cons
   for (int32_t w = 0; w < workers; ++w)
     if (first_bad[(size_t)w] < count) return first_bad[(size_t)w];
   return count;
+}
+
+extern "C" int radnet_inflate_streams_check(const radnet_inflate_stream* streams, int32_t count, int64_t z_len, int64_t out_len, int32_t* bad_stream,
+                                            char* msg, int32_t msg_cap) {
+  int code = RADNET_ERR_ARG;
+  char text[200];
+  text[0] = 0;
+  int32_t bad = -1;
+  auto refuse = [&](int32_t k) {
+    if (bad_stream) *bad_stream = k;
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "inflate streams: %s", text);
+    return code;
+  };
+  if (!streams || count < 1 || count > RADNET_INFLATE_MANY_MAX_STREAMS || z_len < 0 || out_len < 0) {
+    std::snprintf(text, sizeof text, "a null table, %d streams (1..%d), or buffers of %lld and %lld bytes", count, RADNET_INFLATE_MANY_MAX_STREAMS,
+                  (long long)z_len, (long long)out_len);
+    return refuse(bad);
+  }
+  if (z_len >= (1ll << 29) || out_len >= (1ll << 31)) {
+    code = RADNET_ERR_UNSUPPORTED;
+    std::snprintf(text, sizeof text, "%lld compressed bytes (below 2^29: global bit offsets keep 32 bits) or %lld inflated ones (below 2^31)",
+                  (long long)z_len, (long long)out_len);
+    return refuse(bad);
+  }
+  for (int32_t k = 0; k < count; ++k) {
+    const radnet_inflate_stream& s = streams[k];
+    if (s.z_offset < 0 || s.n < 3 || s.out_offset < 0 || s.expected < 0) {
+      std::snprintf(text, sizeof text, "stream %d: z_offset %lld, n %lld (3 at least), out_offset %lld, expected %lld", k, (long long)s.z_offset,
+                    (long long)s.n, (long long)s.out_offset, (long long)s.expected);
+      return refuse(k);
+    }
+    if (s.n > z_len - s.z_offset || s.expected > out_len - s.out_offset) {      // no sum that could overflow
+      std::snprintf(text, sizeof text, "stream %d: [%lld, +%lld) of %lld compressed bytes or [%lld, +%lld) of %lld inflated ones lies outside", k,
+                    (long long)s.z_offset, (long long)s.n, (long long)z_len, (long long)s.out_offset, (long long)s.expected, (long long)out_len);
+      return refuse(k);
+    }
+    if (k == 0) continue;
+    const radnet_inflate_stream& f = streams[k - 1];      // f lies inside the buffers, so its ends do not overflow
+    if (s.z_offset < f.z_offset || s.out_offset < f.out_offset) {
+      std::snprintf(text, sizeof text, "stream %d begins in front of stream %d: the table is not sorted", k, k - 1);
+      return refuse(k);
+    }
+    if (s.z_offset < f.z_offset + f.n || s.out_offset < f.out_offset + f.expected) {
+      std::snprintf(text, sizeof text, "stream %d overlaps stream %d", k, k - 1);
+      return refuse(k);
+    }
+  }
+  if (bad_stream) *bad_stream = -1;
+  return RADNET_OK;
 }

@@ -225,26 +225,42 @@ __device__ __forceinline__ int decode_batch(UnitShared& sh, const WindowBits& bi
   return RADNET_INFLATE_OK;
 }
 
-// units: radnet_inflate_unit (kLz: radnet_inflate_lz_unit) records, measure only; links, out, out_len: emit only; src: kLz emit only
+// The zlib stream a unit belongs to, as the body sees it: the n bytes at z, whose bit 0 is bit `bit_base` of what the caller's
+// start_bit / end_bit count in, and whose inflated bytes are [out_base, out_end) of `out` / `src`.  One stream alone (inflate.hip,
+// inflate_lz.hip): {z, n, 0, 0, out_len}.  One of many (inflate_many.hip): the table entry that holds the unit's start; a start
+// that no stream holds gets n = 0 and bit_base = the start itself, which the reading rule ends with PAST_END before any byte is read.
+struct UnitSpan {
+  const uint8_t* z;
+  long long n;
+  unsigned bit_base;
+  long long out_base, out_end;
+};
+
+// the bit the caller gave unit u (measure: its record, emit: its link), in the caller's count
 template <bool kEmit, bool kLz>
-__global__ void __launch_bounds__(kWave) inflate_units_kernel(const uint8_t* __restrict__ z, long long n, void* __restrict__ units,
-                                                              const radnet_inflate_link* __restrict__ links, uint8_t* __restrict__ out,
-                                                              uint32_t* __restrict__ src, long long out_len) {
-  __shared__ UnitShared sh;
+__device__ __forceinline__ unsigned unit_start_bit(const void* units, const radnet_inflate_link* links, int u) {
+  if (kEmit) return links[u].start_bit;
+  return kLz ? static_cast<const radnet_inflate_lz_unit*>(units)[u].start_bit : static_cast<const radnet_inflate_unit*>(units)[u].start_bit;
+}
+
+// One unit by one wave, the whole body.  units: radnet_inflate_unit (kLz: radnet_inflate_lz_unit) records, measure only; links, out:
+// emit only; src: kLz emit only.  Everything read lies in span.z[0 .. span.n), everything written in [span.out_base, span.out_end).
+template <bool kEmit, bool kLz>
+__device__ __forceinline__ void inflate_unit(UnitShared& sh, const UnitSpan span, void* __restrict__ units, const radnet_inflate_link* __restrict__ links,
+                                             uint8_t* __restrict__ out, uint32_t* __restrict__ src) {
+  const uint8_t* __restrict__ z = span.z;
+  const long long n = span.n;
   const int lane = (int)threadIdx.x, u = (int)blockIdx.x;
   const u64 nbits = 8ull * (u64)n;
   UnitState st;
-  unsigned start;
+  const unsigned start = unit_start_bit<kEmit, kLz>(units, links, u) - span.bit_base;      // from here on bits count inside the stream
   long long out_pos = 0, out_stop = 0;            // emit: where the next byte goes and where the unit's bytes end; every lane keeps them
   if (kEmit) {
     const radnet_inflate_link link = links[u];
-    start = link.start_bit;
     out_pos = link.out_offset;
-    out_stop = min(link.out_offset + (long long)link.out_bytes, out_len);
-    if (out_pos < 0 || out_pos > out_stop) return;      // a table no chain gives: nothing is written
+    out_stop = min(link.out_offset + (long long)link.out_bytes, span.out_end);
+    if (out_pos < span.out_base || out_pos > out_stop) return;      // a table no chain gives: nothing is written
     st.prev = link.prev_byte & 255u;
-  } else {
-    start = kLz ? static_cast<const radnet_inflate_lz_unit*>(units)[u].start_bit : static_cast<const radnet_inflate_unit*>(units)[u].start_bit;
   }
   if (lane == 0) {
     sh.pos = start, sh.wbase = -1, sh.act = kActHeader, sh.status = RADNET_INFLATE_OK, sh.fixed = 0, sh.bfinal = 0, sh.n_tok = 0;
@@ -395,14 +411,14 @@ __global__ void __launch_bounds__(kWave) inflate_units_kernel(const uint8_t* __r
           if (!kLz) {
             out[out_pos + j] = sh.tok_byte[lo];
           } else {
-            const long long p = out_pos + j;      // 0 <= p < out_stop <= out_len < 2^31
+            const long long p = out_pos + j;      // span.out_base <= p < out_stop <= span.out_end < 2^31
             const unsigned len = sh.tok_len[lo];
             if (len == 1) {
               out[p] = sh.tok_byte[lo], src[p] = (uint32_t)p;
             } else {                              // byte k of a match that begins at m copies m - dist + k % dist: a run points in front of itself directly
               const unsigned k = (unsigned)j - (sh.tok_end[lo] - len), dist = (unsigned)sh.tok_dist[lo] + 1u;
               const long long from = out_pos + (long long)(sh.tok_end[lo] - len) - (long long)dist + (long long)(k % dist);
-              src[p] = (uint32_t)(from < 0 ? p : from);      // a chained unit never reaches in front of the stream (RADNET_INFLATE_CHAIN_REACH)
+              src[p] = (uint32_t)(from < span.out_base ? p : from);      // a chained unit never reaches in front of its stream (RADNET_INFLATE_CHAIN_REACH)
             }
           }
         }
@@ -425,21 +441,41 @@ __global__ void __launch_bounds__(kWave) inflate_units_kernel(const uint8_t* __r
   if (!kEmit && lane == 0) {
     const int status = sh.status;
     if (kLz) {
-      radnet_inflate_lz_unit r = {start, 0u, 0u, 0u, 0u, (uint32_t)status, 0u, 0u, 0u, 0u};
+      radnet_inflate_lz_unit r = {start + span.bit_base, 0u, 0u, 0u, 0u, (uint32_t)status, 0u, 0u, 0u, 0u};
       if (status == RADNET_INFLATE_OK) {
-        r.end_bit = (uint32_t)sh.pos, r.out_bytes = (uint32_t)st.produced, r.symbols = st.symbols, r.blocks = st.blocks;
+        r.end_bit = (uint32_t)sh.pos + span.bit_base, r.out_bytes = (uint32_t)st.produced, r.symbols = st.symbols, r.blocks = st.blocks;
         r.flags = st.flags & RADNET_INFLATE_FLAG_FINAL, r.reach = st.reach, r.far_matches = st.far_matches;
       }
       static_cast<radnet_inflate_lz_unit*>(units)[u] = r;
     } else {
-      radnet_inflate_unit r = {start, 0u, 0u, 0u, 0u, (uint32_t)status, 0u, 0u};
+      radnet_inflate_unit r = {start + span.bit_base, 0u, 0u, 0u, 0u, (uint32_t)status, 0u, 0u};
       if (status == RADNET_INFLATE_OK) {
-        r.end_bit = (uint32_t)sh.pos, r.out_bytes = (uint32_t)st.produced, r.symbols = st.symbols, r.blocks = st.blocks;
+        r.end_bit = (uint32_t)sh.pos + span.bit_base, r.out_bytes = (uint32_t)st.produced, r.symbols = st.symbols, r.blocks = st.blocks;
         r.flags = st.flags, r.last_byte = (st.flags & RADNET_INFLATE_FLAG_LAST_KNOWN) ? st.last : 0u;
       }
       static_cast<radnet_inflate_unit*>(units)[u] = r;
     }
   }
+}
+
+// one stream alone: the kernel of inflate.hip and inflate_lz.hip
+template <bool kEmit, bool kLz>
+__global__ void __launch_bounds__(kWave) inflate_units_kernel(const uint8_t* __restrict__ z, long long n, void* __restrict__ units,
+                                                              const radnet_inflate_link* __restrict__ links, uint8_t* __restrict__ out,
+                                                              uint32_t* __restrict__ src, long long out_len) {
+  __shared__ UnitShared sh;
+  inflate_unit<kEmit, kLz>(sh, UnitSpan{z, n, 0u, 0ll, out_len}, units, links, out, src);
+}
+
+// Whether a dynamic block header that zlib's inflate accepts begins at bit p of the stream `bits` reads, nbits long (the rule:
+// include/radnet_hip.h, radnet_inflate_find_blocks).  Three offsets in four end at BTYPE, HLIT or HDIST.
+template <class Bits>
+__device__ __forceinline__ bool dynamic_header_at(const Bits& bits, u64 p, u64 nbits) {
+  const unsigned v = bits.peek(p);
+  if (((v >> 1) & 3) != 2 || ((v >> 3) & 31) > 29 || ((v >> 8) & 31) > 29) return false;
+  u64 pos = p + 3;
+  int nlen, ndist;
+  return parse_dynamic(bits, pos, nbits, [](int, int) {}, nlen, ndist) == RADNET_INFLATE_OK;
 }
 
 int check_stream(radnet_ctx* ctx, const char* what, const void* z, int64_t n) {

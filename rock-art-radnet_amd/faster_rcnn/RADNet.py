@@ -96,6 +96,7 @@ class RADNet():
     png_unfilter = "band"       # predict_from_path: "tiles" reconstructs the maps' adaptive-filter rows on all CUs (png.decode_device(unfilter=))
     png_join = "host"           # predict_from_path: "device" joins the maps' IDAT payloads on the device (png.decode_device(join=); needs a device png_inflate)
     png_crc = "host"            # predict_from_path: "device" sums the maps' IDAT CRC-32s on the device (png.decode_device(crc=); needs a device png_inflate)
+    png_many = False            # predict_from_path: True reads the types of C.use_img_type through ONE png.decode_device_many with the four modes below
     png_inflate = "host"        # predict_from_path: "device" / "device-lz" inflate the maps' IDAT streams on the device (png.decode_device(inflate=))
     scan_tail = False           # ... and the merge of a scan's tiles: final_nms per image, NMS across images (see _scan_tail_on)
 
@@ -596,8 +597,11 @@ class RADNet():
         the file allows (run-length streams, or any deflate stream).  `png_unfilter = "tiles"` is handed on as unfilter=: the same
         images, their scanlines reconstructed by tiles.  `png_crc = "device"` is handed on as crc=: the IDAT chunks' CRC-32 summed on
         the device (with `png_inflate = "host"` that is png.decode_device's ValueError).  `png_join = "device"` is handed on as join=:
-        the file goes up as it is and its IDAT payloads are joined on the device (the same rule)."""
-        from . import utils_io
+        the file goes up as it is and its IDAT payloads are joined on the device (the same rule).
+        `png_many = True`, when C.use_img_type gives more than one type: the types' files are read through ONE
+        png.decode_device_many with the same four modes -- one upload, and with a device inflate one search, measure and emit for
+        all of them -- instead of one get_image per type; the images are the same."""
+        from . import png, utils_io
         C = self.C
         to_host = not self._takes_device_images()
         how = dict(inflate=self.png_inflate)
@@ -607,7 +611,13 @@ class RADNet():
             how["crc"] = self.png_crc
         if self.png_join != "host":
             how["join"] = self.png_join
-        if C.use_img_type:
+        if C.use_img_type and self.png_many and len(C.img_types) > 1:
+            paths = [utils_io.image_path(img_path, img_type) for img_type in C.img_types]
+            files = paths if self.png_join == "device" else [np.fromfile(p, np.uint8) for p in paths]
+            images = png.decode_device_many(files, inflate=self.png_inflate, unfilter=self.png_unfilter, crc=self.png_crc, join=self.png_join)
+            if to_host:
+                images = [img.cpu().numpy() for img in images]
+        elif C.use_img_type:
             images = [utils_io.get_image(img_path, [img_type], random_type=False, to_host=to_host, **how) for img_type in C.img_types]
         else:
             images = [utils_io.get_image(img_path, C.img_types, random_type=False, to_host=to_host, **how)]

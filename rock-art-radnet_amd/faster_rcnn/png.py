@@ -12,6 +12,9 @@ Many files at once (decode_device_many): the files inflate on host threads (zlib
 stream, every palette and a table of segments -- runs of scanlines that start on a row of filter type 0 or 1 and so do not read the
 row above them (radnet_png_plan_segments cuts each pass on the host) -- and one radnet_png_unfilter_segments_u8 per distinct bpp
 reconstructs all passes of all files, one workgroup per segment; the bytes are decode_device's.
+decode_device_many(inflate="device" / "device-lz", crc=, join=) brings the device modes below to a whole batch: the compressed
+streams of all files in ONE buffer behind a radnet_inflate_stream table, ONE search, measure and emit (csrc/inflate_many.hip), the
+host chain per stream, the checks of all files in front of ONE download; a file the device refuses goes to the path above alone.
 
 decode_device(inflate="device") uploads the COMPRESSED stream instead (parse_compressed) and inflates it on the device
 (csrc/inflate.hip: a speculative search for dynamic block headers at every bit offset, the units measured, chained on the host and
@@ -372,9 +375,49 @@ def parse_compressed(data, crc="host", join="host"):
     both modes, trailer."""
     _check_crc(crc)
     _check_join(join)
-    import concurrent.futures
     import torch
-    view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, np.uint8)).cast("B")
+    view = _byte_view(data)
+    on_device, join_device = crc == "device", join == "device"
+    w = _walk_compressed(view, crc)
+    idat, n, source = w.idat, w.n, w.source
+    record, count = (CRC_SEGMENT.itemsize, len(idat)) if on_device else (0, 0)
+    lay = staging_layout(len(view) if join_device else n, 1, record, count, sums=on_device, pieces=len(idat) if join_device else None)
+    staged = torch.empty(lay.total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    host = staged.numpy()
+    if join_device:
+        host[:len(source)] = source      # the file as it is, in one copy: the device gathers the payloads
+    else:
+        _join_payloads(host, 0, source, idat, 1 if w.small_file else MANY_DEFAULT_WORKERS)
+    host[lay.palettes:lay.pad] = w.palette.reshape(-1)
+    segments = pieces = None
+    if join_device:
+        pieces = join_pieces(idat)
+        host[lay.pad:lay.pieces] = 0
+        host[lay.pieces:lay.table] = pieces.view(np.uint8)
+    if on_device:
+        segments = crc_segments(view, idat)
+        if join_device:      # the CRC table follows the piece table without a gap
+            host[lay.table:lay.sums] = segments.view(np.uint8)
+            host[lay.sums:lay.total] = 0
+        else:
+            _stage_table(host, lay, segments)
+    return Compressed(w.header, w.palette, w.passes, w.bpp, w.expected, staged, n, segments, len(source) if join_device else None, pieces, w.trailer)
+
+
+# what the container walk of parse_compressed finds before anything is staged: idat is the list of (start, end) file offsets of
+# the IDAT payloads, n their total, source the file's bytes as a uint8 array, small_file whether the chunks were summed one by one
+Walk = collections.namedtuple("Walk", "header palette passes bpp expected n idat trailer source small_file")
+
+
+def _byte_view(data):
+    return memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, np.uint8)).cast("B")
+
+
+def _walk_compressed(view, crc="host"):
+    """The container walk and the checks of parse_compressed, which stages what this finds (decode_device_many stages many of them
+    in one buffer): the whole walk first, so the structure is judged before any sum; the palette; the chunks' CRC-32 on the host
+    (crc="device": all but the IDAT chunks); the zlib header and the trailer, read through the payload table because either may
+    straddle chunks.  Raises parse_compressed's ValueErrors in its order."""
     header = _header(bytes(view[:33]))
     idat, plte, jobs = [], None, []
     for kind, start, end in _chunks(view):      # the whole walk: the structure is judged before any sum
@@ -384,6 +427,7 @@ def parse_compressed(data, crc="host", join="host"):
         elif kind == b"IDAT":
             idat.append((start, end))
     palette = _palette(header, plte)
+    source = np.frombuffer(view, np.uint8)
 
     def crc_ok(job, workers=1):
         kind, at, end = job
@@ -391,28 +435,11 @@ def parse_compressed(data, crc="host", join="host"):
             return _crc_ok(view, at + 8, end)      # one call per chunk
         return _crc32_threads(view[at + 8:end], zlib.crc32(kind), workers=workers) == int.from_bytes(view[end:end + 4], "big")
     n = sum(e - s for s, e in idat)
-    on_device, join_device = crc == "device", join == "device"
     small_file = sum(e - at for _, at, e in jobs) < 1 << 20
-    if on_device:
+    if crc == "device":
         jobs = [j for j in jobs if j[0] != b"IDAT"]
-    record, count = (CRC_SEGMENT.itemsize, len(idat)) if on_device else (0, 0)
-    lay = staging_layout(len(view) if join_device else n, 1, record, count, sums=on_device, pieces=len(idat) if join_device else None)
-    staged = torch.empty(lay.total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-    host = staged.numpy()
-    source = np.frombuffer(view, np.uint8)
-    starts = np.concatenate([[0], np.cumsum([e - s for s, e in idat])]).astype(np.int64).tolist()
-
-    def join(k):
-        s, e = idat[k]
-        host[starts[k]:starts[k] + e - s] = source[s:e]
-    to_join = len(idat)
-    if join_device:
-        host[:len(source)] = source      # the file as it is, in one copy: the device gathers the payloads
-        to_join = 0
     if small_file:
         oks = {j: crc_ok(j) for j in jobs}
-        for k in range(to_join):
-            join(k)
     else:
         # a chunk of 4 MiB or more is cut into ranges summed on host threads (one large IDAT: this package's writer); the others
         # (8 KiB IDAT chunks by the thousand) go to radnet_png_check_crcs in one call, which spreads them over threads of its own
@@ -426,36 +453,46 @@ def parse_compressed(data, crc="host", join="host"):
             if bad < 0:
                 raise RuntimeError("PNG: radnet_png_check_crcs failed (%d)" % bad)
             oks.update((j, k < bad) for k, j in enumerate(small))      # chunks behind the first bad one are not looked at: it is reported
-        if to_join:
-            with concurrent.futures.ThreadPoolExecutor(max_workers=MANY_DEFAULT_WORKERS) as pool:
-                list(pool.map(lambda g: [join(k) for k in range(g, to_join, MANY_DEFAULT_WORKERS)], range(min(to_join, MANY_DEFAULT_WORKERS))))
     for kind, at, end in jobs:
         if not oks[(kind, at, end)]:
             raise _crc_mismatch(kind, at + 8)
-    host[lay.palettes:lay.pad] = palette.reshape(-1)
-    segments = pieces = None
-    if join_device:
-        pieces = join_pieces(idat)
-        host[lay.pad:lay.pieces] = 0
-        host[lay.pieces:lay.table] = pieces.view(np.uint8)
-    if on_device:
-        segments = np.zeros(len(idat), CRC_SEGMENT)
-        segments["offset"] = starts[:-1]
-        segments["length"] = [e - s for s, e in idat]
-        segments["init"] = zlib.crc32(b"IDAT")
-        segments["expect"] = [int.from_bytes(view[e:e + 4], "big") for _, e in idat]
-        if join_device:      # the CRC table follows the piece table without a gap
-            host[lay.table:lay.sums] = segments.view(np.uint8)
-            host[lay.sums:lay.total] = 0
-        else:
-            _stage_table(host, lay, segments)
-    head = joined_bytes(source, pieces, 0, 2) if join_device else host[:min(n, 2)].tobytes()
+    pieces = join_pieces(idat)
+    head = joined_bytes(source, pieces, 0, 2)
     if n < 2 or head[0] & 15 != 8 or head[0] >> 4 > 7 or (head[0] * 256 + head[1]) % 31 or head[1] & 32:
         raise ValueError("PNG: the IDAT stream has no zlib header the device inflate takes (deflate, a window of at most 32 KiB, FCHECK, no dictionary)")
     passes, expected = pass_geometry(header)
-    tail = joined_bytes(source, pieces, max(n - 4, 0), n) if join_device else host[max(n - 4, 0):n].tobytes()
-    return Compressed(header, palette, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8), expected, staged, n, segments,
-                      len(source) if join_device else None, pieces, int.from_bytes(tail, "big"))
+    tail = joined_bytes(source, pieces, max(n - 4, 0), n)
+    return Walk(header, palette, passes, max(1, CHANNELS[header.color_type] * header.bit_depth // 8), expected, n, idat, int.from_bytes(tail, "big"), source,
+                small_file)
+
+
+def _join_payloads(host, at, source, idat, workers=1):
+    """The IDAT payloads `idat` ((start, end) offsets into `source`) one behind the other into host[at ..], on `workers` threads."""
+    import concurrent.futures
+    starts = np.concatenate([[0], np.cumsum([e - s for s, e in idat])]).astype(np.int64).tolist()
+
+    def join(k):
+        s, e = idat[k]
+        host[at + starts[k]:at + starts[k] + e - s] = source[s:e]
+    if workers == 1 or len(idat) < 2:
+        for k in range(len(idat)):
+            join(k)
+    else:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
+            list(pool.map(lambda g: [join(k) for k in range(g, len(idat), workers)], range(min(len(idat), workers))))
+
+
+def crc_segments(view, idat, base=0):
+    """The CRC_SEGMENT table of the IDAT chunks `idat` ((start, end) file offsets) over the JOINED stream, which stands at `base` of
+    the buffer the device sums: offset where the chunk's payload starts in it, its length, init = zlib.crc32(b"IDAT"), expect =
+    the chunk's CRC field."""
+    segments = np.zeros(len(idat), CRC_SEGMENT)
+    lengths = np.array([e - s for s, e in idat], np.int64)
+    segments["offset"] = base + np.cumsum(lengths) - lengths
+    segments["length"] = lengths
+    segments["init"] = zlib.crc32(b"IDAT")
+    segments["expect"] = [int.from_bytes(view[e:e + 4], "big") for _, e in idat]
+    return segments
 
 
 def _lap(report, name):
@@ -876,27 +913,23 @@ def plan_segments(img, base_offset=0, target_rows=0):
                            for p in img.passes])
 
 
-def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
-    """decode_device for a list of files in one pass: a list of uint8 [H][W][3] (B, G, R) cuda tensors, byte for byte what
-    [decode_device(d) for d in datas] returns.  The files are parsed (CRC, inflate) on `workers` host threads (default
-    min(len(datas), 8), at most 16); a file that fails raises its ValueError prefixed with "file <index>: " before any device
-    work.  Then ONE pinned staging buffer and ONE upload: the streams, the palettes, the segment table (8-byte aligned, short
-    segments first inside each bpp); one radnet_png_unfilter_segments_u8 per distinct bpp; one radnet_png_expand_bgr_u8 per pass.
-    ctx and the stream rules are decode_device's.  unfilter="tiles": inside each bpp the segments of at most 64 rows go as above and
-    the longer ones to one radnet_png_unfilter_tiles_u8; the bytes are the same.  The files inflate on the host, which needs each
-    stream there: this entry takes no join= (decode_device's join="device" needs a device inflate)."""
+def _read_file(item):
+    """An item of decode_device_many as the file's bytes: a path is read as np.fromfile reads it, anything else is taken as it is."""
+    return np.fromfile(item, np.uint8) if isinstance(item, (str, os.PathLike)) else item
+
+
+def _decode_many_host(datas, ctx, workers, unfilter, indices=None):
+    """decode_device_many with inflate="host": the files (bytes, no paths) parsed on host threads, one upload, one segment table.
+    indices: what the files are called in a ValueError ("file <index>: "), default their positions."""
     import concurrent.futures
     import torch
     from . import augmentation_device as AD
-    check_modes(unfilter=unfilter)
-    datas = list(datas)
-    if not datas:
-        return []
+    indices = range(len(datas)) if indices is None else indices
     workers = min(len(datas), MANY_DEFAULT_WORKERS) if workers is None else int(workers)
     workers = max(1, min(workers, MANY_MAX_WORKERS))
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=workers)
     try:
-        futures = [pool.submit(_parse_indexed, item) for item in enumerate(datas)]
+        futures = [pool.submit(_parse_indexed, item) for item in zip(indices, datas)]
         try:
             imgs = [f.result() for f in futures]                          # the first failure, in index order, is raised here
         except BaseException:
@@ -905,11 +938,7 @@ def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
         starts = np.concatenate([[0], np.cumsum([len(im.stream) for im in imgs])]).astype(np.int64)
         n_streams = int(starts[-1])
         tables = list(pool.map(lambda k: plan_segments(imgs[k], int(starts[k])), range(len(imgs))))
-        # one table: grouped by bpp, inside a group the segments of at most 64 rows first (the one-wave launch), then the long ones
-        bpps = np.concatenate([np.full(len(t), im.bpp, np.int64) for t, im in zip(tables, imgs)])
-        table = np.concatenate(tables)
-        order = np.lexsort((table["rows"] > SEGMENT_ONE_WAVE_ROWS, bpps))
-        table, bpps = table[order], bpps[order]
+        table, bpps = _sorted_segments(tables, [im.bpp for im in imgs])
         at = staging_layout(n_streams, len(imgs), SEGMENT.itemsize, len(table))
         staged = torch.empty(at.total, dtype=torch.uint8, pin_memory=True)
         host = staged.numpy()
@@ -921,12 +950,7 @@ def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
     finally:
         pool.shutdown(wait=True)                                          # the host threads are done before any device work
     _stage_table(host, at, table)
-    groups, first = [], 0
-    for bpp, n in zip(*np.unique(bpps, return_counts=True)):
-        # with tiles the long segments, which stand behind the short ones of their bpp, leave the segments call for the tiles call
-        short = int((table["rows"][first:first + int(n)] <= TILE_ROWS).sum()) if unfilter == "tiles" else int(n)
-        groups.append((int(bpp), first, short, int(n)))
-        first += int(n)
+    groups = _segment_groups(table, bpps, unfilter)
     with AD.feed_stream(ctx) as (ctx, side):
         dev = staged.cuda(non_blocking=True)
         base = dev.data_ptr()
@@ -937,6 +961,449 @@ def decode_device_many(datas, ctx=None, workers=None, unfilter="band"):
             _expand_passes(ctx.call, im.header, im.passes, base + int(starts[k]), base + at.palettes + 768 * k, out)
             outs.append(out)
     return [AD.hand_over(out, side) for out in outs]
+
+
+def _sorted_segments(tables, bpp_of):
+    """ONE segment table of many files' tables: grouped by bpp, inside a group the segments of at most 64 rows first (the one-wave
+    launch), then the long ones.  (table, the bpp of every entry)."""
+    bpps = np.concatenate([np.full(len(t), bpp, np.int64) for t, bpp in zip(tables, bpp_of)])
+    table = np.concatenate(tables)
+    order = np.lexsort((table["rows"] > SEGMENT_ONE_WAVE_ROWS, bpps))
+    return table[order], bpps[order]
+
+
+def _segment_groups(table, bpps, unfilter):
+    """The (bpp, first, short, count) groups _reconstruct takes of a table _sorted_segments made."""
+    groups, first = [], 0
+    for bpp, n in zip(*np.unique(bpps, return_counts=True)):
+        # with tiles the long segments, which stand behind the short ones of their bpp, leave the segments call for the tiles call
+        short = int((table["rows"][first:first + int(n)] <= TILE_ROWS).sum()) if unfilter == "tiles" else int(n)
+        groups.append((int(bpp), first, short, int(n)))
+        first += int(n)
+    return groups
+
+
+INFLATE_STREAM = np.dtype([("z_offset", np.int64), ("n", np.int64), ("out_offset", np.int64), ("expected", np.int64)])      # radnet_inflate_stream, 32 bytes
+INFLATE_MANY_MAX_STREAMS = _constant("RADNET_INFLATE_MANY_MAX_STREAMS")
+MANY_MAX_COMPRESSED, MANY_MAX_INFLATED = 1 << 29, 1 << 31      # a batch stays below both (radnet_inflate_streams_check)
+MANY_GRAIN = 16      # RADNET_PNG_JOIN_GRAIN: every file and every stream of a batch begins on a 16-byte boundary of the device buffer
+# where everything stands in the ONE pinned buffer of a batch: the stream table (room for one entry per file) in front, then the
+# compressed bytes from `z` on (join="host": the joined streams; join="device": the files as they are), then what staging_layout
+# arranges behind them: the palettes, the pad, the piece tables, the CRC table, its sums and its result
+ManyStaging = collections.namedtuple("ManyStaging", "streams z palettes pad pieces table sums result total")
+
+
+def many_layout(files, z_bytes, pieces=None, crc_count=0, sums=False):
+    """ManyStaging of a batch of `files` files whose compressed bytes take z_bytes (every file's share rounded up to MANY_GRAIN)."""
+    z = INFLATE_STREAM.itemsize * files      # a multiple of 16
+    at = staging_layout(z + z_bytes, files, CRC_SEGMENT.itemsize if sums else 0, crc_count, sums=sums, pieces=pieces)
+    return ManyStaging(0, z, at.palettes, at.pad, at.pieces if pieces is not None else at.table, at.table, at.sums, at.result, at.total)
+
+
+def _grain(n):
+    return (n + MANY_GRAIN - 1) & ~(MANY_GRAIN - 1)
+
+
+def _count_idat(path):
+    """How many IDAT chunks the file at `path` holds, by its chunk headers alone (a seek per chunk): the room its piece table needs
+    in the pinned buffer before the file is read into it.  A broken file gives what was seen; the walk speaks later."""
+    count = 0
+    with open(path, "rb") as f:
+        f.seek(33)
+        while True:
+            head = f.read(8)
+            if len(head) < 8:
+                return count
+            length, kind = struct.unpack(">I4s", head)
+            count += kind == b"IDAT"
+            if kind == b"IEND":
+                return count
+            f.seek(length + 4, 1)
+
+
+def _chain_stream(units, entry, z_offset, n, expected, out_offset, names):
+    """The host chain of ONE stream of a batch: `units` is its slice of the batch's sorted records, whose bits are shifted back by
+    8 * z_offset for radnet_inflate_chain / radnet_inflate_lz_chain (`entry`) and whose links are shifted forward again.
+    (links, None, stats) or (None, the reason as decode_device words it, None)."""
+    import ctypes
+    from radnet_hip import lib as L
+    if n < 7:
+        return None, "a zlib stream of %d bytes" % n, None
+    local = units.copy()
+    shift = np.uint32(8 * z_offset)
+    local["start_bit"] -= shift
+    ok = local["status"] == 0
+    local["end_bit"][ok] -= shift
+    links = np.zeros(len(local), INFLATE_LINK)
+    n_links, n_false, bad = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(-1)
+    rc = getattr(L.load_library(), entry)(local.ctypes.data, len(local), 16, n, expected, links.ctypes.data, len(links), ctypes.byref(n_links),
+                                          ctypes.byref(n_false), ctypes.byref(bad))
+    if rc != 0:
+        if rc < 0:
+            raise RuntimeError("PNG: %s failed (%d)" % (entry, rc))
+        why = "chain: " + names[rc]
+        if rc == 2:
+            why += " (%s)" % INFLATE_STATUS[int(local["status"][bad.value])]
+        return None, why, None
+    links = links[:n_links.value]
+    chained = local[np.searchsorted(local["start_bit"], links["start_bit"])]
+    stats = dict(false_candidates=n_false.value, units=len(links), blocks=int(chained["blocks"].sum()))
+    if "far_matches" in (local.dtype.names or ()):
+        stats["far_units"] = int((chained["far_matches"] > 0).sum())
+    links["start_bit"] += shift
+    links["out_offset"] += out_offset
+    return links, None, stats
+
+
+def _decode_batch_on_device(items, ctx, workers, unfilter, inflate, crc, join, reports, report):
+    """One batch of decode_device_many's device inflate.  items: the files (bytes or paths); reports: one dict per file, filled as
+    decode_device fills its report.  Returns (images, refused): images[k] is the device image of file k or None, refused the
+    indices the host path has to take (reports[k]["reason"] says why); or None when the common candidate counter passed its cap."""
+    import concurrent.futures
+    import torch
+    from radnet_hip.lib import RadnetError
+    from . import augmentation_device as AD
+    lz, tiles, crc_device, join_device = inflate == "device-lz", unfilter == "tiles", crc == "device", join == "device"
+    count = len(items)
+    is_path = [isinstance(d, (str, os.PathLike)) for d in items]
+    workers = min(count, MANY_DEFAULT_WORKERS) if workers is None else max(1, min(int(workers), MANY_MAX_WORKERS))
+    _lap(report, "_skip")
+    walks, views = [None] * count, [None] * count
+
+    def walk(k):
+        try:
+            walks[k] = _walk_compressed(views[k], crc)
+        except ValueError as e:
+            reports[k]["reason"] = "container: %s" % e
+    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
+        if join_device:
+            # the files go up as they are: a path is read straight into its place in the pinned buffer, and walked there
+            sizes = [os.path.getsize(d) if p else len(_byte_view(d)) for d, p in zip(items, is_path)]
+            file_at = np.concatenate([[0], np.cumsum([_grain(n) for n in sizes])]).astype(np.int64)
+            for k in range(count):
+                if not is_path[k]:
+                    views[k] = _byte_view(items[k])
+            list(pool.map(walk, [k for k in range(count) if not is_path[k]]))
+            piece_room = [_count_idat(items[k]) if is_path[k] else (len(walks[k].idat) if walks[k] else 0) for k in range(count)]
+            at = many_layout(count, int(file_at[-1]), pieces=sum(piece_room), crc_count=sum(piece_room) if crc_device else 0, sums=crc_device)
+            staged = torch.empty(at.total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+            host = staged.numpy()
+
+            def load(k):
+                place = host[at.z + int(file_at[k]):at.z + int(file_at[k]) + sizes[k]]
+                if is_path[k]:
+                    with open(items[k], "rb") as f:
+                        got = f.readinto(memoryview(place))
+                    if got != sizes[k]:
+                        reports[k]["reason"] = "container: PNG: the file changed while it was read (%d of %d bytes)" % (got, sizes[k])
+                        return
+                    views[k] = memoryview(place)
+                    walk(k)
+                    if walks[k] is not None and len(walks[k].idat) > piece_room[k]:
+                        walks[k], reports[k]["reason"] = None, "container: PNG: the file changed while it was read"
+                else:
+                    place[:] = np.frombuffer(views[k], np.uint8)
+            list(pool.map(load, range(count)))
+        else:
+            def read(k):
+                views[k] = _byte_view(_read_file(items[k]))
+                walk(k)
+            list(pool.map(read, range(count)))
+            z_room = [_grain(w.n) if w else 0 for w in walks]
+            file_at = np.concatenate([[0], np.cumsum(z_room)]).astype(np.int64)      # here: where the joined streams stand
+            idat_count = sum(len(w.idat) for w in walks if w) if crc_device else 0
+            at = many_layout(count, int(file_at[-1]), crc_count=idat_count, sums=crc_device)
+            staged = torch.empty(at.total, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+            host = staged.numpy()
+            list(pool.map(lambda k: walks[k] and _join_payloads(host, at.z + int(file_at[k]), walks[k].source, walks[k].idat), range(count)))
+    live = [k for k in range(count) if walks[k] is not None]      # the files the device is given
+    refused = [k for k in range(count) if walks[k] is None]
+    images = [None] * count
+    if not live:
+        return images, refused
+    # the stream table: where each zlib stream stands in the common z (16-byte grains apart) and in the common output (back to back)
+    streams = np.zeros(len(live), INFLATE_STREAM)
+    z_at = np.concatenate([[0], np.cumsum([_grain(walks[k].n) for k in live])]).astype(np.int64) if join_device else file_at[live]
+    out_at = np.concatenate([[0], np.cumsum([walks[k].expected for k in live])]).astype(np.int64)
+    streams["z_offset"], streams["n"] = z_at[:len(live)], [walks[k].n for k in live]
+    streams["out_offset"], streams["expected"] = out_at[:-1], [walks[k].expected for k in live]
+    z_len = int(z_at[-1]) if join_device else int(file_at[-1])
+    out_len = int(out_at[-1])
+    host[at.streams:at.z] = 0
+    host[at.streams:at.streams + streams.nbytes] = streams.view(np.uint8)
+    host[at.pad:at.pieces] = 0
+    for j, k in enumerate(live):
+        host[at.palettes + 768 * k:at.palettes + 768 * (k + 1)] = walks[k].palette.reshape(-1)
+    crc_tables, piece_tables, piece_at = [], [], []
+    for j, k in enumerate(live):
+        w = walks[k]
+        if join_device:
+            piece_at.append(sum(len(t) for t in piece_tables))
+            piece_tables.append(join_pieces(w.idat))
+        if crc_device:
+            crc_tables.append(crc_segments(views[k], w.idat, int(z_at[j])))
+    if join_device:
+        pieces = np.concatenate(piece_tables)
+        host[at.pieces:at.table] = 0
+        host[at.pieces:at.pieces + pieces.nbytes] = pieces.view(np.uint8)
+    if crc_device:
+        crc_table = np.concatenate(crc_tables)
+        crc_first = np.concatenate([[0], np.cumsum([len(t) for t in crc_tables])])      # where each file's chunks begin in the table
+        host[at.table:at.total] = 0
+        host[at.table:at.table + crc_table.nbytes] = crc_table.view(np.uint8)
+        sums_at = at.table + crc_table.nbytes      # the sums and the result follow the entries there are
+        result_at = sums_at + 4 * len(crc_table)
+    _lap(report, "container_crc_ms")
+    refuse = lambda k, why: (reports[k].update(reason=why), refused.append(k))      # noqa: E731
+    with AD.feed_stream(ctx) as (ctx, side):
+        call = functools.partial(_launch, report, ctx)
+        dev = staged.cuda(non_blocking=True)
+        _lap(report, "upload_ms")
+        base = dev.data_ptr()
+        if join_device:
+            # one launch per file: a piece table tiles its output from 0 on, so each file joins into its own place of the common z
+            zdev = torch.empty(max(z_len, 1), dtype=torch.uint8, device="cuda")
+            zbase = zdev.data_ptr()
+            for j, k in enumerate(live):
+                shift = JOIN_PIECE.itemsize * piece_at[j]
+                try:
+                    call("radnet_png_join_u8", base + at.z + int(file_at[k]), sizes[k], staged.data_ptr() + at.pieces + shift, base + at.pieces + shift,
+                         len(piece_tables[j]), zbase + int(z_at[j]), walks[k].n)
+                except RadnetError as e:
+                    refuse(k, "join: %s" % e)
+        else:
+            zdev, zbase = dev, base + at.z
+        if crc_device:
+            call("radnet_crc32_segments", zbase, z_len, staged.data_ptr() + at.table, base + at.table, len(crc_table), base + sums_at, base + result_at)
+            verdict = torch.empty(2, dtype=torch.int32, pin_memory=True)
+            verdict.copy_(dev[result_at:result_at + 8].view(torch.int32), non_blocking=True)
+        head = (zbase, z_len, staged.data_ptr() + at.streams, base + at.streams, len(live))
+        cap = z_len // 32 + 1024
+        found = torch.zeros(cap + 1, dtype=torch.int32, device="cuda")      # the count, then the candidates
+        call("radnet_inflate_find_blocks_many", *head, found.data_ptr() + 4, cap, found)
+        found_host = found.cpu().numpy().view(np.uint32)
+        _lap(report, "download_candidates_ms")
+        n_cand = int(found_host[0])
+        if n_cand > cap:
+            return None      # the overflow belongs to no file: the caller decodes the batch file by file
+        if crc_device:
+            first_bad, n_bad = (int(v) for v in verdict)
+            if n_bad:      # rare: the sums the device left say whose chunks they are
+                sums = dev[sums_at:result_at].cpu().numpy().view(np.uint32)
+                wrong = np.flatnonzero(sums != crc_table["expect"])
+                for j in sorted(set(np.searchsorted(crc_first, wrong, side="right") - 1)):
+                    refuse(live[j], "crc: IDAT chunk %d" % (int(wrong[wrong >= crc_first[j]][0]) - int(crc_first[j])))
+        dtype, measure, chain, names, emit = ((INFLATE_LZ_UNIT, "radnet_inflate_lz_measure_many", "radnet_inflate_lz_chain", INFLATE_LZ_CHAIN, "radnet_inflate_lz_emit_many")
+                                              if lz else (INFLATE_UNIT, "radnet_inflate_rle_measure_many", "radnet_inflate_chain", INFLATE_CHAIN, "radnet_inflate_rle_emit_many"))
+        first_bits = (8 * streams["z_offset"] + 16).astype(np.uint32)
+        starts = np.union1d(found_host[1:1 + n_cand], first_bits)
+        units = np.zeros(len(starts), dtype)
+        units["start_bit"] = starts
+        units_dev = torch.from_numpy(units.view(np.uint8)).cuda()
+        _lap(report, "sort_upload_units_ms")
+        call(measure, *head, units_dev, len(units))
+        units = units_dev.cpu().numpy().view(dtype)
+        _lap(report, "download_units_ms")
+        lo = np.searchsorted(starts, 8 * streams["z_offset"])
+        hi = np.searchsorted(starts, 8 * (streams["z_offset"] + streams["n"]))
+        cand_sorted = np.sort(found_host[1:1 + n_cand])
+        all_links = []
+        for j, k in enumerate(live):
+            zo, n = int(streams["z_offset"][j]), int(streams["n"][j])
+            reports[k]["candidates"] = int(np.searchsorted(cand_sorted, 8 * (zo + n)) - np.searchsorted(cand_sorted, 8 * zo))
+            if k in refused:
+                continue
+            links, why, stats = _chain_stream(units[lo[j]:hi[j]], chain, zo, n, int(streams["expected"][j]), int(streams["out_offset"][j]), names)
+            if links is None:
+                refuse(k, why)
+            else:
+                reports[k].update(stats)
+                all_links.append(links)
+        going = [j for j, k in enumerate(live) if k not in refused]
+        if not going:
+            return images, sorted(refused)
+        links = np.concatenate(all_links)
+        links_dev = torch.from_numpy(links.view(np.uint8)).cuda()
+        stream = torch.empty(max(out_len, 1), dtype=torch.uint8, device="cuda")
+        _lap(report, "chain_upload_links_ms")
+        if lz:
+            # no link writes the sources of a refused stream's bytes: they are zeroed then, which is flat (0 is a root), so that the
+            # shared rounds count the streams that go on and nothing else
+            src = (torch.empty if len(going) == len(live) else torch.zeros)(max(out_len, 1), dtype=torch.int32, device="cuda")
+            call(emit, *head, links_dev, len(links), stream, src, out_len)
+            bound, ran, rounds = max(1, (max(out_len, 2) - 1).bit_length()), 0, None
+            while rounds is None:
+                if ran >= bound:
+                    raise RuntimeError("PNG: the source table of %d bytes is not flat after %d rounds of radnet_inflate_lz_resolve" % (out_len, bound))
+                group = min(4, bound - ran)
+                changed = torch.zeros(group, dtype=torch.int32, device="cuda")
+                call("radnet_inflate_lz_resolve", src, out_len, group, changed)
+                still = np.flatnonzero(changed.cpu().numpy() == 0)
+                _lap(report, "download_changed_ms")
+                if len(still):
+                    rounds = ran + int(still[0])
+                ran += group
+            call("radnet_inflate_lz_gather", src, stream, out_len)
+        else:
+            call(emit, *head, links_dev, len(links), stream, out_len)
+        # the Adler-32 parts and the filter-type column of every stream that is still going, all enqueued in front of ONE download
+        chunk = _constant("RADNET_DEFLATE_CHUNK")
+        rooms = [DEFLATE_SYMBOLS * 4 + -(-int(streams["expected"][j]) // chunk) * 16 + sum(p.pass_h for p in walks[live[j]].passes) for j in going]
+        tail_at = np.concatenate([[0], np.cumsum([(r + 7) & ~7 for r in rooms])]).astype(np.int64)
+        tail = torch.zeros(int(tail_at[-1]), dtype=torch.uint8, device="cuda")
+        for i, j in enumerate(going):
+            w, expected, t = walks[live[j]], int(streams["expected"][j]), tail.data_ptr() + int(tail_at[i])
+            sptr = stream.data_ptr() + int(streams["out_offset"][j])
+            parts = t + DEFLATE_SYMBOLS * 4
+            call("radnet_deflate_rle_scan_u8", sptr, expected, t, parts)
+            offsets = np.array([p.stream_offset for p in w.passes], np.int64)
+            pass_rows = np.array([p.pass_h for p in w.passes], np.int32)
+            rowbytes = np.array([p.rowbytes for p in w.passes], np.int32)
+            call("radnet_png_gather_column_u8", sptr, expected, offsets.ctypes.data, pass_rows.ctypes.data, rowbytes.ctypes.data, len(w.passes),
+                 parts + -(-expected // chunk) * 16)
+        tail_host = tail.cpu().numpy()
+        _lap(report, "download_adler_column_ms")
+        tables, taken = [], []
+        for i, j in enumerate(going):
+            k, expected = live[j], int(streams["expected"][j])
+            w, t = walks[k], tail_host[int(tail_at[i]):int(tail_at[i]) + rooms[i]]
+            n_parts = -(-expected // chunk)
+            parts = t[DEFLATE_SYMBOLS * 4:DEFLATE_SYMBOLS * 4 + n_parts * 16].view(np.uint64)
+            column = t[DEFLATE_SYMBOLS * 4 + n_parts * 16:]
+            if adler32_of_parts(parts, expected) != w.trailer:
+                refuse(k, "adler")
+                continue
+            if int(column.max()) > 4:
+                refuse(k, "a filter type above 4")
+                continue
+            row0, mine = 0, []
+            for p in w.passes:
+                col = np.ascontiguousarray(column[row0:row0 + p.pass_h])
+                mine.append(_plan_pass("radnet_png_plan_segments_column", col.ctypes.data, p, int(streams["out_offset"][j]) + p.stream_offset))
+                row0 += p.pass_h
+            tables.append(np.concatenate(mine))
+            taken.append(j)
+        if not taken:
+            return images, sorted(refused)
+        table, bpps = _sorted_segments(tables, [walks[live[j]].bpp for j in taken])
+        table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
+        _lap(report, "plan_segments_ms")
+        _reconstruct(call, table.ctypes.data, table_dev.data_ptr(), stream.data_ptr(), out_len, _segment_groups(table, bpps, unfilter))
+        for j, mine in zip(taken, tables):
+            k = live[j]
+            w, r = walks[k], reports[k]
+            out = torch.empty((w.header.height, w.header.width, 3), dtype=torch.uint8, device="cuda")
+            _expand_passes(call, w.header, w.passes, stream.data_ptr() + int(streams["out_offset"][j]), base + at.palettes + 768 * k, out)
+            images[k] = out
+            r.update(path="device", reason=None, reconstruction="segments")
+            if lz:
+                r["rounds"] = rounds
+            if tiles:
+                long_ones = mine[mine["rows"] > TILE_ROWS]
+                r["reconstruction"] = "segments+tiles" if len(long_ones) < len(mine) else "tiles"
+                r["sweeps"] = max([plan_tiles(int(t["rows"]), int(t["rowbytes"]), w.bpp).sweeps for t in long_ones], default=0)
+            if crc_device:
+                r["crc"] = "device"
+            if join_device:
+                r["join"] = "device"
+    return [im if im is None else AD.hand_over(im, side) for im in images], sorted(refused)
+
+
+def _batches(items):
+    """decode_device_many's batches: consecutive runs of the files whose lengths (each rounded up to 16; an upper bound of the
+    compressed stream) stay below 2^29 in total, whose inflated streams stay below 2^31 and whose count stays within
+    RADNET_INFLATE_MANY_MAX_STREAMS.  A file whose first 33 bytes give no geometry counts as empty: the walk refuses it."""
+    runs, z, out = [[]], 0, 0
+    for k, d in enumerate(items):
+        try:
+            size = os.path.getsize(d) if isinstance(d, (str, os.PathLike)) else len(_byte_view(d))
+            expected = pass_geometry(read_header(d))[1]
+        except (ValueError, OSError):
+            size, expected = _grain(0), 0
+        if runs[-1] and (z + _grain(size) >= MANY_MAX_COMPRESSED or out + expected >= MANY_MAX_INFLATED or len(runs[-1]) >= INFLATE_MANY_MAX_STREAMS):
+            runs.append([])
+            z = out = 0
+        runs[-1].append(k)
+        z, out = z + _grain(size), out + expected
+    return runs
+
+
+class HostInflateModeError(ValueError, TypeError):
+    """decode_device_many asked for crc= or join= on the device beside its host inflate.  It is check_modes' ValueError, message
+    included, as decode_device raises it; and it is still a TypeError, which is what the entry raised for these keywords while it
+    had only the host inflate, so a caller that asked "does the many-file entry take this?" that way gets the answer it got."""
+
+
+def decode_device_many(datas, ctx=None, workers=None, unfilter="band", inflate="host", crc="host", join="host", report=None):
+    """decode_device for a list of files in one pass: a list of uint8 [H][W][3] (B, G, R) cuda tensors, byte for byte what
+    [decode_device(d) for d in datas] returns.  The files are parsed (CRC, inflate) on `workers` host threads (default
+    min(len(datas), 8), at most 16); a file that fails raises its ValueError prefixed with "file <index>: " before any device
+    work.  Then ONE pinned staging buffer and ONE upload: the streams, the palettes, the segment table (8-byte aligned, short
+    segments first inside each bpp); one radnet_png_unfilter_segments_u8 per distinct bpp; one radnet_png_expand_bgr_u8 per pass.
+    ctx and the stream rules are decode_device's.  unfilter="tiles": inside each bpp the segments of at most 64 rows go as above and
+    the longer ones to one radnet_png_unfilter_tiles_u8; the bytes are the same.  An item may be a path (str / os.PathLike): it is
+    read as np.fromfile reads it.
+    inflate="device" / "device-lz" (opt-in; crc="device" and join="device" need one of them, as check_modes says -- beside the host
+    inflate that ValueError is a HostInflateModeError, which is also the TypeError the entry raised before it had the keywords): the result is
+    byte for byte [decode_device(d, inflate=, unfilter=, crc=, join=) for d in datas], but the batch pays decode_device's host
+    round trips once, not once per file.  The compressed streams go into ONE pinned buffer with ONE upload, every stream on a
+    16-byte boundary, behind the radnet_inflate_stream table and in front of the palettes and the other tables (many_layout);
+    with join="device" the FILES go up as they are -- a path is read with readinto straight into its place in the pinned
+    buffer -- and one radnet_png_join_u8 per file gathers its stream into the common buffer.  Then ONE radnet_crc32_segments
+    (crc="device"), ONE radnet_inflate_find_blocks_many, ONE measure, radnet_inflate_chain / radnet_inflate_lz_chain per stream on
+    the host, ONE emit, for "device-lz" ONE shared resolve loop and gather, the Adler scan and the column gather of every file in
+    front of ONE download, and the reconstruction over ONE segment table (planned from the downloaded columns) as above.
+    A file the device refuses -- for decode_device's reasons: far matches under "device", a unit over the symbol cap, a chain
+    refusal, Adler, a filter type above 4, a CRC mismatch, a container parse_compressed refuses -- goes, alone, to the path above
+    together with the other refused ones; the rest keep the device path and the result keeps the order of `datas`.  An invalid
+    file therefore raises what it raises today, "file <index>: ...", the lowest index first.  When the common candidate counter
+    passes its cap (compressed bytes / 32 + 1024) the overflow belongs to no file, and the batch is decoded file by file through
+    decode_device with the same modes; that is rare -- a stream needs a valid-looking dynamic header every 32 bytes.
+    A list whose files reach 2^29 bytes in total (their lengths stand in for the compressed streams'), whose inflated streams reach
+    2^31, or that holds more than RADNET_INFLATE_MANY_MAX_STREAMS files is cut into consecutive batches here.  "device-lz" keeps a
+    source table of 4 bytes per inflated byte of a batch on the device beside the 1 byte of the stream itself.
+    report (a dict): report["files"][k] carries decode_device's keys for file k (path, reason, candidates, false_candidates, units,
+    blocks, reconstruction -- "segments", or with unfilter="tiles" "segments+tiles" / "tiles" -- and rounds, far_units, sweeps, crc,
+    join in their modes; rounds is the batch's), report["batches"] the number of batches, report["overflow"] how many of them
+    went file by file; a dict under report["stages"] receives the staged timing as in decode_device."""
+    try:
+        check_modes(inflate, unfilter, crc, join)
+    except ValueError as e:
+        if inflate == "host" and unfilter in UNFILTER_MODES and "device" in (crc, join):
+            raise HostInflateModeError(str(e)) from None
+        raise
+    datas = list(datas)
+    report = {} if report is None else report
+    files = [dict(reason=None, candidates=0) for _ in datas]
+    for r in files:
+        _report_host_path(r, inflate, unfilter, crc, join)
+    report.update(files=files, batches=0, overflow=0)
+    if not datas:
+        return []
+    if inflate == "host":
+        return _decode_many_host([_read_file(d) for d in datas], ctx, workers, unfilter)
+    images, refused = [None] * len(datas), []
+    for run in _batches(datas):
+        report["batches"] += 1
+        got = _decode_batch_on_device([datas[k] for k in run], ctx, workers, unfilter, inflate, crc, join, [files[k] for k in run], report)
+        if got is None:
+            report["overflow"] += 1
+            for k in run:
+                try:
+                    images[k] = decode_device(_read_file(datas[k]), ctx, inflate=inflate, report=files[k], unfilter=unfilter, crc=crc, join=join)
+                except ValueError as e:
+                    raise ValueError("file %d: %s" % (k, e)) from e
+            continue
+        for k, im in zip(run, got[0]):
+            images[k] = im
+        refused += [run[i] for i in got[1]]
+    if refused:
+        refused = sorted(refused)
+        for k in refused:
+            _report_host_path(files[k], inflate, unfilter, crc, join)
+        for k, im in zip(refused, _decode_many_host([_read_file(datas[k]) for k in refused], ctx, workers, unfilter, indices=refused)):
+            images[k] = im
+    return images
 
 
 def imdecode_color(data):

@@ -70,11 +70,15 @@ class DeviceImageLoader:
     decode, file by file.  unfilter="tiles" is handed to the default decoders of both (png.decode_device and decode_many's
     unfilter=); a decoder of the caller's is called as it is.  inflate=, crc= and join= are handed to the default png.decode_device
     of __call__ in the same way (crc="device" and join="device" need inflate="device" or "device-lz": png.decode_device's
-    ValueError, raised here); decode_many keeps the host parse and takes none of them, so prefetch is unchanged."""
+    ValueError, raised here).  prefetch keeps the host parse of png.decode_device_many unless prefetch_modes=True: then inflate,
+    crc and join go to the default png.decode_device_many as well (its device inflate: one search, one measure, one emit for the
+    batch), and with join="device" prefetch hands it the files' paths, which it reads straight into its pinned buffer.  The
+    default, False, leaves prefetch as it was; a caller's own decode / decode_many is called as it is either way."""
 
-    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band", inflate="host", crc="host", join="host"):
+    def __init__(self, cache_bytes=1 << 30, decode=None, decode_many=None, unfilter="band", inflate="host", crc="host", join="host", prefetch_modes=False):
         png.check_modes(inflate, unfilter, crc, join)
         self.unfilter, self.inflate, self.crc, self.join = unfilter, inflate, crc, join
+        self.prefetch_modes = bool(prefetch_modes)
         self.cache_bytes = int(cache_bytes)
         self.decode = decode                       # (file bytes as uint8 array) -> image; default: png.decode_device
         # (list of file bytes) -> list of images, for prefetch; default: png.decode_device_many, or `decode` on each file if that is set
@@ -108,10 +112,14 @@ class DeviceImageLoader:
         call would move it.  A batch holds at most cache_bytes of decoded images (judged by the files' headers); a file that alone
         exceeds the bound is left to __call__; pairs that together exceed cache_bytes evict the least recently used among them, as
         calls in that order would.  hits / misses do not move.  Returns the number of images decoded (also added to `prefetched`)."""
+        as_paths = False
         if self.decode_many is not None:
             decode_many = self.decode_many
         elif self.decode is not None:
             decode_many = lambda files: [self.decode(f) for f in files]      # noqa: E731  (one decoder fills the cache)
+        elif self.prefetch_modes and self.inflate != "host":
+            as_paths = self.join == "device"      # the files are read straight into the decoder's pinned buffer
+            decode_many = lambda files: png.decode_device_many(files, unfilter=self.unfilter, inflate=self.inflate, crc=self.crc, join=self.join)      # noqa: E731
         else:
             decode_many = png.decode_device_many if self.unfilter == "band" else lambda files: png.decode_device_many(files, unfilter=self.unfilter)      # noqa: E731
         todo, seen = [], set()
@@ -130,7 +138,7 @@ class DeviceImageLoader:
         done, batch, held = 0, [], 0
         for item in todo + [None]:
             if batch and (item is None or held + item[2] > self.cache_bytes):
-                files = [np.fromfile(path, np.uint8) for path, _, _ in batch]
+                files = [path if as_paths else np.fromfile(path, np.uint8) for path, _, _ in batch]
                 imgs = decode_many(files)
                 for (_, key, _), img in zip(batch, imgs):
                     self._insert(key, img)

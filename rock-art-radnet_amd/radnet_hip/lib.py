@@ -316,6 +316,12 @@ def load_library():
         "radnet_inflate_lz_emit": (C.c_int, [vp, vp, i64, vp, i32, vp, vp, i64]),
         "radnet_inflate_lz_resolve": (C.c_int, [vp, vp, i64, i32, vp]),
         "radnet_inflate_lz_gather": (C.c_int, [vp, vp, vp, i64]),
+        "radnet_inflate_streams_check": (C.c_int, [vp, i32, i64, i64, C.POINTER(i32), C.c_char_p, i32]),
+        "radnet_inflate_find_blocks_many": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, i32, vp]),
+        "radnet_inflate_rle_measure_many": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, i32]),
+        "radnet_inflate_lz_measure_many": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, i32]),
+        "radnet_inflate_rle_emit_many": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, i32, vp, i64]),
+        "radnet_inflate_lz_emit_many": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, i32, vp, vp, i64]),
         "radnet_png_gather_column_u8": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, vp]),
         "radnet_png_plan_segments_column": (C.c_int, [vp, i64, i32, i32, i32, vp, i32]),
         "radnet_png_plan_tiles": (C.c_int, [i32, i32, i32, vp]),
@@ -443,6 +449,18 @@ def png_plan_join(table, file_len, n, misalign=0, count=None):
     rc = load_library().radnet_png_plan_join(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(file_len), int(n),
                                              int(misalign), C.cast(plan, C.c_void_p), C.byref(bad), msg, len(msg))
     return rc, plan[0], plan[1], bad.value, msg.value.decode()
+
+
+def inflate_streams_check(table, z_len, out_len, count=None):
+    """radnet_inflate_streams_check (host only, no context, no device) on a table of radnet_inflate_stream rows -- a NumPy array of
+    32 bytes per entry, or None for a null table -- for z_len compressed and out_len inflated bytes: (rc, index of the bad stream
+    or -1, the message).  count defaults to the table's length."""
+    import numpy as np
+    rows = np.zeros((0, 32), np.uint8) if table is None else np.ascontiguousarray(table).view(np.uint8).reshape(-1, 32)
+    bad, msg = C.c_int32(-2), C.create_string_buffer(256)
+    rc = load_library().radnet_inflate_streams_check(rows.ctypes.data if len(rows) else None, len(rows) if count is None else int(count), int(z_len),
+                                                     int(out_len), C.byref(bad), msg, len(msg))
+    return rc, bad.value, msg.value.decode()
 
 
 def scan_merge_check(table, pool_words, slot_rows, count=None):
