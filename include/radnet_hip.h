@@ -676,6 +676,70 @@ int radnet_deflate_pack(radnet_ctx* ctx, const uint8_t* pieces, int64_t piece_ca
  * 1 for distance symbol 0, four bits each: 1222 bits.  A match's distance code is therefore one zero bit (dist_nbits = 1).
  * A null pointer or header_cap < 153 is RADNET_ERR_ARG and nothing is written. */
 int radnet_deflate_build_code(const uint32_t* hist, radnet_deflate_code* code, uint8_t* header, int32_t header_cap, int32_t* header_nbits);
+/* ---- deflate with far matches on the device (csrc/deflate_lz.hip, csrc/deflate_plan.cpp): LZ77 tokens, two Huffman codes -------------
+ * The section above restated with matches at any distance of deflate's window.  THE LZ TOKEN RULE, constants first: */
+#define RADNET_DEFLATE_LZ_GROUP 256
+#define RADNET_DEFLATE_LZ_FAR_MIN 10
+#define RADNET_DEFLATE_LZ_FAR_MIN2 12
+#define RADNET_DEFLATE_LZ_FAR_D 4096
+#define RADNET_DEFLATE_DIST_SYMBOLS 30
+/* Chunks and tiles: the stream is cut into chunks of RADNET_DEFLATE_CHUNK bytes, one chunk is one deflate block and one piece, as
+ *   above.  No match reads in front of its chunk and none crosses a multiple of RADNET_DEFLATE_TILE counted from the chunk's start.
+ *   Positions below are counted from the chunk's start.
+ * Candidates of position p, up to three: distance 1 (p >= 1); distance `near`, an argument (p >= near; faster_rcnn/png.py passes the
+ *   pixel stride, 3 for RGB and 1 for grey; near == 1 is the candidate above); the HASH CANDIDATE: the greatest q that lies in a
+ *   GROUP in front of p's own and has H(q) == H(p).  Groups are RADNET_DEFLATE_LZ_GROUP positions; H(x) =
+ *   ((the little-endian uint32 at x) * 2654435761 mod 2^32) >> 17, 15 bits, defined only while x + 4 <= the chunk's end (p has no
+ *   hash candidate beyond that).  The hash candidate is refused when p - q > 32768.  Only earlier groups are sources, so the table
+ *   of greatest positions is kept per group by "read, barrier, integer max, barrier" and needs no sort: 2^15 entries of 16 bits,
+ *   64 KiB of LDS beside the 64 KiB of the chunk's bytes, within the 160 KiB of a CU.
+ * Length of a candidate: the number of equal bytes byte[p + i] == byte[p + i - distance], i = 0, 1, ..., at most 258 and at most
+ *   the bytes left in p's tile; a source that overlaps the position (distance < length) is legal.
+ * Acceptance: distances 1 and `near` from 3 bytes; the hash candidate from RADNET_DEFLATE_LZ_FAR_MIN bytes when its distance is at
+ *   most RADNET_DEFLATE_LZ_FAR_D, from RADNET_DEFLATE_LZ_FAR_MIN2 bytes beyond.
+ * Choice: the longest accepted candidate; on equal length the smaller distance.
+ * Parse: greedy from every tile's start -- the token at p is the chosen match, or the literal byte[p] when there is none; the next
+ *   token is at p + max(1, length).
+ * The rule is deterministic and depends on no launch order: tests/deflate_lz_cases.py states it in Python and the kernels are
+ * compared with it byte for byte.  The constants were chosen with that model.
+ * THE TOKEN TABLE: one uint32 per stream byte -- 0: the position is covered by a match that starts in front of it; 1 << 31: a
+ * literal starts here; 1 << 31 | length << 16 | (distance - 1): a match starts here (length 3..258, distance 1..32768). */
+/* First pass (device): one workgroup per chunk finds the candidates and parses the chunk.  tokens (device, uint32 [n], 16-byte
+ * aligned) receives the token table; hist_ll[286] and hist_d[30] (device, uint32; the caller zeroes them; integer atomics) have the
+ * counts of the literal/length symbols, one end-of-block per chunk included, and of the distance symbols (RFC 1951 3.2.5) ADDED;
+ * adler_parts as radnet_deflate_rle_scan_u8 writes them.  near: 1..32768.  A null pointer, n < 1, near outside 1..32768 or a
+ * misaligned table is RADNET_ERR_ARG, n >= 2^32 RADNET_ERR_UNSUPPORTED; nothing is launched then. */
+int radnet_deflate_lz_scan_u8(radnet_ctx* ctx, const uint8_t* stream, int64_t n, int32_t near, uint32_t* tokens, uint32_t* hist_ll, uint32_t* hist_d,
+                              uint64_t* adler_parts);
+/* Second pass: the pieces of radnet_deflate_rle_emit_u8 -- its layout, sync flush, BFINAL, bit order and "no byte at or beyond
+ * sizes[c]" -- from the token table of the first pass (device, 16-byte aligned; the caller answers for a table that pass wrote for
+ * this stream).  A match is its length symbol's code, that symbol's extra bits, the distance symbol's code out of code_d (30
+ * entries) and the distance's extra bits, least significant bit first (RFC 1951 3.2.5); a token takes at most 48 bits.  Bit offsets
+ * come from a workgroup prefix sum over the token starts.  code_ll, code_d and header_bits are HOST memory.  piece_cap must be at
+ * least radnet_deflate_lz_piece_cap(code_ll, code_d, header_nbits).  Refused as radnet_deflate_rle_emit_u8 refuses (code_d's
+ * lengths and bits are checked like code_ll's); a misaligned table is RADNET_ERR_ARG. */
+int radnet_deflate_lz_emit_u8(radnet_ctx* ctx, const uint8_t* stream, int64_t n, const uint32_t* tokens, const radnet_deflate_code* code_ll,
+                              const radnet_deflate_code* code_d, const uint8_t* header_bits, int32_t header_nbits, uint8_t* pieces, int64_t piece_cap,
+                              uint32_t* sizes);
+/* Host only (csrc/deflate_plan.cpp; no context, no device).  From the counts of radnet_deflate_lz_scan_u8 two complete canonical
+ * codes of at most 15 bits (built as radnet_deflate_build_code builds its one; with fewer than two used distance symbols, symbol 0
+ * -- or 1 -- joins them) and the dynamic block header: BFINAL 0, BTYPE 10, HLIT 29, HDIST 29, HCLEN 15, the code-length code of
+ * radnet_deflate_build_code, then the 286 + 30 lengths, four bits each: 17 + 57 + 316 * 4 = 1338 bits, 168 bytes.  A null pointer
+ * or header_cap < 168 is RADNET_ERR_ARG and nothing is written. */
+int radnet_deflate_build_codes_lz(const uint32_t* hist_ll, const uint32_t* hist_d, radnet_deflate_code* code_ll, radnet_deflate_code* code_d,
+                                  uint8_t* header, int32_t header_cap, int32_t* header_nbits);
+/* Host only: the bound an LZ piece cannot pass, ceil(header_nbits / 8) + ceil(w * RADNET_DEFLATE_CHUNK / 8) + 16 with w = the larger
+ * of the longest literal/length code and ceil(the most bits a match can take / 3) -- a match covers three bytes at least, and takes
+ * its two codes and their symbols' extra bits.  Negative (RADNET_ERR_ARG) for what radnet_deflate_lz_emit_u8 refuses. */
+int64_t radnet_deflate_lz_piece_cap(const radnet_deflate_code* code_ll, const radnet_deflate_code* code_d, int32_t header_nbits);
+/* Host only: the bits of all block headers, tokens and end-of-blocks that emit writes for these counts and codes over `chunks`
+ * pieces -- each symbol's extra bits are fixed, so the counts decide it.  The flush and the zero bits up to a byte are not counted:
+ * they depend on where each piece ends and are at most 7 bits a piece more for one rule than for another, which is why
+ * png.deflate_device_lz takes the LZ stream only when bits_lz + 7 * chunks < bits_rle.  hist_d and code_d null (both): the
+ * run-length rule, every match followed by dist_nbits bits.  Negative (RADNET_ERR_ARG): a null hist_ll or code_ll, one of hist_d and
+ * code_d null alone, an illegal code, header_nbits or dist_nbits, chunks outside 1..65536. */
+int64_t radnet_deflate_stream_bits(const uint32_t* hist_ll, const uint32_t* hist_d, const radnet_deflate_code* code_ll, const radnet_deflate_code* code_d,
+                                   int32_t dist_nbits, int32_t header_nbits, int64_t chunks);
 /* ---- inflate of run-length streams on the device (csrc/inflate.hip, csrc/inflate_plan.cpp): speculative block search ----------------
  * The reader's counterpart of the section above, for the streams this project meets: zlib level 1 with Z_RLE (cv2.imwrite's
  * defaults), png.assemble and the device deflate.  Every match of such a stream has distance 1, so a block's output depends on the

@@ -5,42 +5,17 @@
 // tile by tile: a workgroup of 256 threads holds a tile of RADNET_DEFLATE_TILE bytes in LDS, 16 consecutive positions per thread.  A
 // position's token follows from the first and the last position of its run, which come from a prefix maximum of the run starts and
 // a suffix minimum of the run ends over the workgroup; bit offsets from a prefix sum.  wave64, integers only, no inline assembly.
-#include "radnet_internal.h"
+#include "deflate_device.h"
 
 namespace {
 
-constexpr int kChunk = RADNET_DEFLATE_CHUNK, kTile = RADNET_DEFLATE_TILE, kThreads = 256, kPer = kTile / kThreads;
-constexpr int kSymbols = RADNET_DEFLATE_SYMBOLS, kEob = 256, kMaxLen = 15, kNone = 1 << 20;
-constexpr int kHeaderWords = RADNET_DEFLATE_HEADER_MAX_BITS / 32;
+using namespace radnet_deflate_device;            // the cut, length symbols, tile load, prefix sum, bit window, Adler parts
+constexpr int kNone = 1 << 20;
 // the bits one tile can add (15 per position at most: a literal's longest code; a match spends at most 25 on three positions) behind
 // a header or a carried partial word, and the word a token may spill into
 constexpr int kWindowWords = kHeaderWords + kTile * kMaxLen / 32 + 4;
-static_assert(kPer == 16 && kChunk % kTile == 0, "a thread reads its 16 positions as one uint4");
 
 enum { kSkip = 0, kLiteral = 1, kMatch = 2 };
-
-// RFC 1951, 3.2.5: the symbol of a match length 3..258, its number of extra bits and their value
-__device__ __forceinline__ void length_symbol(int len, int& symbol, int& extra_bits, int& extra) {
-  const int l = len - 3;
-  if (len == 258) {
-    symbol = 285, extra_bits = 0, extra = 0;
-  } else if (l < 8) {
-    symbol = 257 + l, extra_bits = 0, extra = 0;
-  } else {
-    extra_bits = 29 - __clz(l);                   // floor(log2(l)) - 2
-    symbol = 261 + 4 * extra_bits + ((l >> extra_bits) & 3);
-    extra = l & ((1 << extra_bits) - 1);
-  }
-}
-
-// bytes [0, len) of a tile from global memory; a whole tile at a 16-byte aligned address moves as one uint4 per thread
-__device__ __forceinline__ void load_tile(uint8_t* tile, const uint8_t* __restrict__ g, int len, int tid) {
-  if (len == kTile && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-    reinterpret_cast<uint4*>(tile)[tid] = reinterpret_cast<const uint4*>(g)[tid];
-  } else {
-    for (int i = tid; i < len; i += kThreads) tile[i] = g[i];
-  }
-}
 
 // per thread: the largest `start` of the threads in front of it (-1: none) and the smallest `end` of the threads behind it (kNone)
 __device__ __forceinline__ void scan_runs(int start, int end, int tid, int* sh, int& start_in, int& end_in) {
@@ -61,22 +36,6 @@ __device__ __forceinline__ void scan_runs(int start, int end, int tid, int* sh, 
   for (int w = wave + 1; w < kThreads / 64; ++w) eb = min(eb, sh[4 + w]);
   start_in = ea;
   end_in = eb;
-}
-
-// exclusive prefix sum of v over the workgroup; total = the sum
-__device__ __forceinline__ int scan_sum(int v, int tid, int* sh, int& total) {
-  const int lane = tid & 63, wave = tid >> 6;
-  int a = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(a, d, 64);
-    if (lane >= d) a += o;
-  }
-  if (lane == 63) sh[wave] = a;
-  __syncthreads();
-  int before = a - v;
-  for (int w = 0; w < wave; ++w) before += sh[w];
-  total = sh[0] + sh[1] + sh[2] + sh[3];
-  return before;
 }
 
 // THE TOKEN RULE on a tile of len bytes in LDS: f(k, i, byte, kind, match_length) for each of the thread's positions i = 16 tid + k
@@ -153,8 +112,7 @@ __global__ void __launch_bounds__(kThreads) deflate_scan_kernel(const uint8_t* _
     load_tile(tile, stream + base + t0, tl, tid);
     __syncthreads();
     tile_tokens(tile, tl, tid, sh, [&](int, int i, int byte, int kind, int mlen) {
-      s1 += (unsigned)byte;
-      s2 += (unsigned long long)(len - t0 - i) * (unsigned)byte;
+      adler_add(s1, s2, len, t0 + i, byte);
       if (kind == kLiteral) {
         atomicAdd(&counts[byte], 1u);
       } else if (kind == kMatch) {
@@ -164,29 +122,15 @@ __global__ void __launch_bounds__(kThreads) deflate_scan_kernel(const uint8_t* _
       }
     });
   }
-  for (int d = 32; d > 0; d >>= 1) {
-    s1 += __shfl_down(s1, d, 64);
-    s2 += __shfl_down(s2, d, 64);
-  }
-  if ((tid & 63) == 0) sums[tid >> 6][0] = s1, sums[tid >> 6][1] = s2;
-  __syncthreads();
+  adler_store(s1, s2, tid, sums, parts, (long long)blockIdx.x);      // holds the barrier behind which `counts` is complete
   for (int s = tid; s < kSymbols; s += kThreads)
     if (counts[s]) atomicAdd(&hist[s], counts[s]);
-  if (tid < 2) parts[2 * (long long)blockIdx.x + tid] = sums[0][tid] + sums[1][tid] + sums[2][tid] + sums[3][tid];
 }
 
 struct EmitTables {
   uint32_t code[kSymbols];                        // bits | length << 16
   uint32_t header[kHeaderWords];                  // the header's bits, zero behind them
 };
-
-// v's low nb bits into the window from bit p on; the window is zero where nothing has been put
-__device__ __forceinline__ void put_bits(unsigned* window, int p, unsigned v, int nb) {
-  if (nb == 0) return;
-  const unsigned long long x = (unsigned long long)v << (p & 31);
-  atomicOr(&window[p >> 5], (unsigned)x);
-  if (x >> 32) atomicOr(&window[(p >> 5) + 1], (unsigned)(x >> 32));
-}
 
 __global__ void __launch_bounds__(kThreads) deflate_emit_kernel(const uint8_t* __restrict__ stream, long long n, const EmitTables tables, int header_nbits,
                                                                 int dist_nbits, uint8_t* __restrict__ pieces, long long piece_cap,
@@ -200,7 +144,6 @@ __global__ void __launch_bounds__(kThreads) deflate_emit_kernel(const uint8_t* _
   const int len = (int)min((long long)kChunk, n - base);
   const bool last = base + len == n;
   uint8_t* piece = pieces + (long long)blockIdx.x * piece_cap;
-  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(window);
   for (int s = tid; s < kSymbols; s += kThreads) {
     const unsigned c = tables.code[s], l = c >> 16;
     rcode[s] = l ? (__brev(c & 0xffffu) >> (32 - l)) | (l << 16) : 0u;
@@ -237,31 +180,9 @@ __global__ void __launch_bounds__(kThreads) deflate_emit_kernel(const uint8_t* _
     }
     bitpos += total;
     __syncthreads();
-    const int whole = (bitpos >> 5) - flushed;    // whole words of the window: out they go, the partial one moves to the front
-    for (int i = tid; i < 4 * whole; i += kThreads) piece[4ll * flushed + i] = bytes[i];
-    const unsigned carry = window[whole];
-    __syncthreads();
-    for (int w = tid; w <= whole; w += kThreads) window[w] = w == 0 ? carry : 0u;
-    flushed += whole;
+    flushed = flush_window(window, piece, bitpos, flushed, tid);      // whole words out, the partial one to the front
   }
-  __syncthreads();
-  if (tid == 0) {
-    int p = bitpos - 32 * flushed;
-    put_bits(window, p, rcode[kEob] & 0xffffu, (int)(rcode[kEob] >> 16));
-    p += (int)(rcode[kEob] >> 16);
-    if (!last) {
-      p = (p + 3 + 7) & ~7;                       // 000: an empty stored block, not the last; zero bits up to the byte
-      put_bits(window, p + 16, 0xffffu, 16);      // LEN 0, NLEN 0xFFFF
-      p += 32;
-    } else {
-      p = (p + 7) & ~7;
-    }
-    end_bits = p;
-  }
-  __syncthreads();
-  const int tail = end_bits >> 3;
-  for (int i = tid; i < tail; i += kThreads) piece[4ll * flushed + i] = bytes[i];
-  if (tid == 0) sizes[blockIdx.x] = (unsigned)(4 * flushed + tail);
+  finish_piece(window, piece, bitpos, flushed, rcode[kEob], last, &end_bits, &sizes[blockIdx.x], tid);
 }
 
 __global__ void __launch_bounds__(kThreads) deflate_pack_kernel(const uint8_t* __restrict__ pieces, long long piece_cap, const unsigned* __restrict__ sizes,

@@ -763,7 +763,8 @@ class RADNet():
         own font at label_scale, not OpenCV's glyphs or metrics; unpinned against cv2); the boat and human maps stay outlines
         only.  The default leaves the labels out and writes the same bytes as before they existed.  deflate / huffman go to
         png.encode_device as they are (deflate="device": the four streams are compressed on the device and only the files' bytes
-        come down; crc="device" with it: the IDAT chunks' CRC-32 is summed there too, the same bytes); the defaults are the host
+        come down; crc="device" with it: the IDAT chunks' CRC-32 is summed there too, the same bytes; deflate="device-lz": the
+        device deflate with far matches, per map the smaller of its stream and the run-length one); the defaults are the host
         deflate and the bytes it always wrote.  Returns the five paths."""
         import json
         import os

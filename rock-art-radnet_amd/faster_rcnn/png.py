@@ -1508,6 +1508,7 @@ def check_writable(img):
 # ---- deflate on the device ---------------------------------------------------------------------------------------------------------
 DEFLATE_CODE = np.dtype([("bits", np.uint16), ("length", np.uint16)])      # radnet_deflate_code, 4 bytes
 DEFLATE_SYMBOLS = 286
+DEFLATE_DIST_SYMBOLS = 30
 HuffmanCode = collections.namedtuple("HuffmanCode", "code header header_nbits dist_nbits")      # the arguments of radnet_deflate_rle_emit_u8
 
 
@@ -1661,7 +1662,6 @@ def deflate_device(dev, ctx, huffman="dynamic", crc="host"):
     download of the packed bytes."""
     import torch
     _check_crc(crc)
-    from radnet_hip import lib as L
     n = int(dev.numel())
     chunk = _constant("RADNET_DEFLATE_CHUNK")
     chunks = -(-n // chunk)
@@ -1673,18 +1673,117 @@ def deflate_device(dev, ctx, huffman="dynamic", crc="host"):
     hist = scan_host.numpy()[:DEFLATE_SYMBOLS * 4].view(np.uint32)
     adler = adler32_of_parts(scan_host.numpy()[DEFLATE_SYMBOLS * 4:].view(np.uint64), n)
     hc = fixed_code() if huffman == "fixed" else huffman_code(hist)
+    return _emit_rle(dev, ctx, hc, hist, adler, crc)
+
+
+def _emit_rle(dev, ctx, hc, hist, adler, crc):
+    """deflate_device behind its scan: the run-length pieces of `dev` with the code hc built from the counts hist."""
+    from radnet_hip import lib as L
+    n = int(dev.numel())
+    chunks = -(-n // _constant("RADNET_DEFLATE_CHUNK"))
     piece_cap = int(L.load_library().radnet_deflate_piece_cap(hc.code.ctypes.data, hc.header_nbits, hc.dist_nbits))
     if piece_cap < 0:
         raise ValueError("PNG: radnet_deflate_piece_cap failed (%d)" % piece_cap)
-    pieces = torch.empty(chunks * piece_cap, dtype=torch.uint8, device="cuda")
-    sizes = torch.empty(chunks, dtype=torch.int32, device="cuda")
     header = np.frombuffer(hc.header, np.uint8)
-    ctx.call("radnet_deflate_rle_emit_u8", dev, n, hc.code.ctypes.data, header.ctypes.data, hc.header_nbits, hc.dist_nbits, pieces, piece_cap, sizes)
+    emit = lambda pieces, sizes: ctx.call("radnet_deflate_rle_emit_u8", dev, n, hc.code.ctypes.data, header.ctypes.data, hc.header_nbits,      # noqa: E731
+                                          hc.dist_nbits, pieces, piece_cap, sizes)
     # the bits of all tokens follow from the counts (a match: at most 5 extra bits and the distance code); per piece the header,
     # the flush and the padding come on top
     counts = hist.astype(np.int64)
     token_bits = int((counts * hc.code["length"].astype(np.int64)).sum()) + int(counts[257:].sum()) * (5 + hc.dist_nbits)
     out_cap = (token_bits + 7) // 8 + chunks * ((hc.header_nbits + 7) // 8 + 16)
+    return _emit_pack_download(ctx, emit, chunks, piece_cap, out_cap, adler, crc)
+
+
+def huffman_codes_lz(hist_ll, hist_d):
+    """The two codes of an image from the counts of radnet_deflate_lz_scan_u8 and the dynamic block header that describes them
+    (radnet_deflate_build_codes_lz: host only, no device): (code_ll [286], code_d [30], header bytes, header_nbits)."""
+    import ctypes
+    from radnet_hip import lib as L
+    hist_ll = np.ascontiguousarray(hist_ll, np.uint32).reshape(-1)
+    hist_d = np.ascontiguousarray(hist_d, np.uint32).reshape(-1)
+    if hist_ll.size != DEFLATE_SYMBOLS or hist_d.size != DEFLATE_DIST_SYMBOLS:
+        raise ValueError("PNG: histograms of %d and %d counts (the alphabets have %d and %d)" % (hist_ll.size, hist_d.size, DEFLATE_SYMBOLS, DEFLATE_DIST_SYMBOLS))
+    code_ll, code_d = np.zeros(DEFLATE_SYMBOLS, DEFLATE_CODE), np.zeros(DEFLATE_DIST_SYMBOLS, DEFLATE_CODE)
+    header = np.zeros(_constant("RADNET_DEFLATE_HEADER_MAX_BITS") // 8, np.uint8)
+    nbits = ctypes.c_int32(0)
+    rc = L.load_library().radnet_deflate_build_codes_lz(hist_ll.ctypes.data, hist_d.ctypes.data, code_ll.ctypes.data, code_d.ctypes.data, header.ctypes.data,
+                                                        header.size, ctypes.byref(nbits))
+    if rc != 0:
+        raise ValueError("PNG: radnet_deflate_build_codes_lz failed (%d)" % rc)
+    return code_ll, code_d, header[:(nbits.value + 7) // 8].tobytes(), nbits.value
+
+
+def stream_bits(hist_ll, code_ll, header_nbits, chunks, hist_d=None, code_d=None, dist_nbits=0):
+    """radnet_deflate_stream_bits: the bits of all headers, tokens and end-of-blocks of `chunks` pieces with these counts and codes;
+    without hist_d and code_d the run-length rule, every match followed by dist_nbits bits."""
+    from radnet_hip import lib as L
+    hist_ll = np.ascontiguousarray(hist_ll, np.uint32)
+    hist_d = None if hist_d is None else np.ascontiguousarray(hist_d, np.uint32)
+    bits = int(L.load_library().radnet_deflate_stream_bits(hist_ll.ctypes.data, None if hist_d is None else hist_d.ctypes.data, code_ll.ctypes.data,
+                                                           None if code_d is None else code_d.ctypes.data, dist_nbits, header_nbits, chunks))
+    if bits < 0:
+        raise ValueError("PNG: radnet_deflate_stream_bits failed (%d)" % bits)
+    return bits
+
+
+def deflate_device_lz(dev, ctx, near=1, crc="host", report=None):
+    """deflate_device with far matches (csrc/deflate_lz.hip, THE LZ TOKEN RULE of include/radnet_hip.h), priced against the
+    run-length rule before anything is emitted: both scans run -- radnet_deflate_rle_scan_u8 and radnet_deflate_lz_scan_u8 with
+    `near`, the pixel stride --, ONE small download brings both sets of counts and the Adler parts, both codes are built and
+    radnet_deflate_stream_bits gives both sizes.  The LZ stream is emitted when bits_lz + 7 * chunks < bits_rle (a piece pads up to
+    7 bits more under one rule than under the other, so the file is then never the longer one); otherwise, ties included, the
+    run-length stream is, and the bytes are deflate_device's.  Returns what deflate_device returns.  A dict passed as `report`
+    receives rule ("lz" or "rle"), bits_lz, bits_rle, matches (the LZ rule's) and far_matches (those at a distance other than 1 and
+    `near`: the distance counts cannot tell more, and tell this only for near <= 4).  The token table takes 4 bytes per stream byte
+    on the device (about 190 MB for a 4000x4000 RGB map) and is allocated before the rules are priced, so also when run-length wins."""
+    import torch
+    _check_crc(crc)
+    from radnet_hip import lib as L
+    n = int(dev.numel())
+    chunks = -(-n // _constant("RADNET_DEFLATE_CHUNK"))
+    ll, dd = DEFLATE_SYMBOLS * 4, DEFLATE_DIST_SYMBOLS * 4
+    at_lz, at_d, at_parts = ll, 2 * ll, (2 * ll + dd + 7) & ~7      # the run-length counts, the LZ counts, the distance counts, the parts
+    scan = torch.zeros(at_parts + chunks * 16, dtype=torch.uint8, device="cuda")
+    tokens = torch.empty(n, dtype=torch.int32, device="cuda")
+    base = scan.data_ptr()
+    ctx.call("radnet_deflate_rle_scan_u8", dev, n, scan, base + at_parts)      # both scans write the same Adler parts, to the same place
+    ctx.call("radnet_deflate_lz_scan_u8", dev, n, int(near), tokens, base + at_lz, base + at_d, base + at_parts)
+    scan_host = torch.empty(scan.numel(), dtype=torch.uint8, pin_memory=True)
+    scan_host.copy_(scan, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    host = scan_host.numpy()
+    hist_rle, hist_ll, hist_d = host[:ll].view(np.uint32), host[at_lz:at_lz + ll].view(np.uint32), host[at_d:at_d + dd].view(np.uint32)
+    adler = adler32_of_parts(host[at_parts:].view(np.uint64), n)
+    hc = huffman_code(hist_rle)
+    code_ll, code_d, header_bytes, header_nbits = huffman_codes_lz(hist_ll, hist_d)
+    bits_rle = stream_bits(hist_rle, hc.code, hc.header_nbits, chunks, dist_nbits=hc.dist_nbits)
+    bits_lz = stream_bits(hist_ll, code_ll, header_nbits, chunks, hist_d, code_d)
+    rule = "lz" if bits_lz + 7 * chunks < bits_rle else "rle"
+    if report is not None:
+        near_symbols = {0} | ({near - 1} if near <= 4 else set())
+        report.update(rule=rule, bits_lz=bits_lz, bits_rle=bits_rle, matches=int(hist_ll[257:].sum()),
+                      far_matches=int(sum(int(c) for s, c in enumerate(hist_d) if s not in near_symbols)))
+    if rule == "rle":
+        return _emit_rle(dev, ctx, hc, hist_rle, adler, crc)
+    piece_cap = int(L.load_library().radnet_deflate_lz_piece_cap(code_ll.ctypes.data, code_d.ctypes.data, header_nbits))
+    if piece_cap < 0:
+        raise ValueError("PNG: radnet_deflate_lz_piece_cap failed (%d)" % piece_cap)
+    header = np.frombuffer(header_bytes, np.uint8)
+    emit = lambda pieces, sizes: ctx.call("radnet_deflate_lz_emit_u8", dev, n, tokens, code_ll.ctypes.data, code_d.ctypes.data, header.ctypes.data,      # noqa: E731
+                                          header_nbits, pieces, piece_cap, sizes)
+    out_cap = (bits_lz + 7) // 8 + chunks * 16     # exact but for each piece's flush and padding
+    return _emit_pack_download(ctx, emit, chunks, piece_cap, out_cap, adler, crc)
+
+
+def _emit_pack_download(ctx, emit, chunks, piece_cap, out_cap, adler, crc):
+    """The second half of deflate_device and deflate_device_lz: emit(pieces, sizes) writes `chunks` pieces of at most piece_cap bytes,
+    radnet_deflate_pack moves them together (out_cap: what they cannot pass), the 8 bytes of the total and then exactly that many
+    bytes come down; crc="device" sums them first.  Returns what deflate_device returns."""
+    import torch
+    pieces = torch.empty(chunks * piece_cap, dtype=torch.uint8, device="cuda")
+    sizes = torch.empty(chunks, dtype=torch.int32, device="cuda")
+    emit(pieces, sizes)
     room = 8 + CRC_SEGMENT.itemsize + 12 if crc == "device" else 0      # behind the packed bytes: padding, one segment, its sum, the result
     out = torch.empty(out_cap + room, dtype=torch.uint8, device="cuda")
     total = torch.empty(1, dtype=torch.int64, device="cuda")
@@ -1717,7 +1816,8 @@ def deflate_device(dev, ctx, huffman="dynamic", crc="host"):
 HOST_DEFLATE_DEFAULTS = dict(level=1, strategy="rle", workers=None, chunk_bytes=1 << 20)
 
 
-def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None, chunk_bytes=1 << 20, ctx=None, deflate="host", huffman="dynamic", crc="host"):
+def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None, chunk_bytes=1 << 20, ctx=None, deflate="host", huffman="dynamic", crc="host",
+                  report=None):
     """The PNG file (bytes) of a contiguous uint8 cuda tensor [H][W][3] (B, G, R; written as 8-bit RGB) or [H][W] (8-bit grey); a
     NumPy array is uploaded first -- there is no CPU filter path, as there is no CPU reconstruction.  filter: "adaptive" (per row
     the type with the smallest sum of |signed residual|, the lowest on a tie), a fixed type 0..4 or its name.  One
@@ -1730,22 +1830,29 @@ def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None,
     workers and chunk_bytes belong to the host deflate: any of them off its default together with deflate="device" is a ValueError.
     crc="device" (opt-in; needs deflate="device", with deflate="host" it is a ValueError): the IDAT chunk's CRC-32 is summed over the
     packed bytes on the device (csrc/crc32.hip) and comes down with them; the host adds the 4 Adler bytes.  The file's bytes are
-    those of crc="host"."""
+    those of crc="host".
+    deflate="device-lz" (opt-in): deflate="device" with far matches (deflate_device_lz; `near` is the pixel stride, 3 or 1): the LZ
+    stream and the run-length stream are priced from their counts and the smaller one is emitted, so the file is never longer than
+    deflate="device"'s and equals it byte for byte when run-length wins.  One dynamic code pair per image: huffman="fixed" is a
+    ValueError beside it, as the host deflate's keywords are; crc="device" is accepted.  A dict passed as `report` receives rule
+    ("lz" or "rle"), bits_lz, bits_rle, matches and far_matches in this mode and is left alone in the others."""
     import torch
     from . import augmentation_device as AD
     mode = _filter_mode(filter)
-    if deflate not in ("host", "device"):
-        raise ValueError("PNG: deflate=%r (\"host\" or \"device\")" % (deflate,))
+    if deflate not in ("host", "device", "device-lz"):
+        raise ValueError("PNG: deflate=%r (\"host\", \"device\" or \"device-lz\")" % (deflate,))
     if huffman not in ("dynamic", "fixed"):
         raise ValueError("PNG: huffman=%r (\"dynamic\" or \"fixed\")" % (huffman,))
     _check_crc(crc)
-    if crc == "device" and deflate != "device":
+    if crc == "device" and deflate == "host":
         raise ValueError("PNG: crc=\"device\" sums the bytes deflate=\"device\" leaves on the device and cannot be set with deflate=\"host\"")
-    if deflate == "device":
+    if deflate != "host":
         given = dict(level=level, strategy=strategy, workers=workers, chunk_bytes=chunk_bytes)
         off = sorted(k for k, v in given.items() if v != HOST_DEFLATE_DEFAULTS[k])
         if off:
-            raise ValueError("PNG: %s belong%s to the host deflate and cannot be set with deflate=\"device\"" % (", ".join(off), "s" if len(off) == 1 else ""))
+            raise ValueError("PNG: %s belong%s to the host deflate and cannot be set with deflate=\"%s\"" % (", ".join(off), "s" if len(off) == 1 else "", deflate))
+    if deflate == "device-lz" and huffman == "fixed":
+        raise ValueError("PNG: deflate=\"device-lz\" builds its two codes from the image and cannot be set with huffman=\"fixed\"")
     h, w, channels = check_writable(img)
     if isinstance(img, np.ndarray):
         img = torch.from_numpy(np.ascontiguousarray(img)).cuda()
@@ -1759,6 +1866,9 @@ def encode_device(img, filter="adaptive", level=1, strategy="rle", workers=None,
             img.record_stream(side)
         dev = torch.empty(n, dtype=torch.uint8, device="cuda")
         ctx.call("radnet_png_filter_rows_u8", img, h, w, channels, w * channels, mode, dev)
+        if deflate == "device-lz":
+            packed, adler, *idat_crc = deflate_device_lz(dev, ctx, near=channels, crc=crc, report=report)
+            return assemble_pieces(packed, adler, w, h, 2 if channels == 3 else 0, idat_crc=idat_crc[0] if idat_crc else None)
         if deflate == "device":
             if crc == "device":
                 packed, adler, idat_crc = deflate_device(dev, ctx, huffman, crc="device")

@@ -177,7 +177,9 @@ class DeviceImageLoader:
 def imwrite(path, img, **kw):
     """cv2.imwrite(path, img) for a PNG map: png.encode_device(img, **kw) written to `path` (a cuda tensor stays where it is; only
     the filtered stream comes down; with deflate="device" only the compressed bytes do, huffman="dynamic" or "fixed": see
-    png.encode_device; crc="device" beside deflate="device" sums the IDAT chunk's CRC-32 there too).  Only the .png suffix is accepted; returns True like cv2.imwrite."""
+    png.encode_device; crc="device" beside deflate="device" sums the IDAT chunk's CRC-32 there too; deflate="device-lz" adds far matches and never
+    writes a longer file than deflate="device", report= a dict that receives which rule ran and both sizes).  Only the .png suffix is accepted; returns
+    True like cv2.imwrite."""
     path = os.fspath(path)
     if os.path.splitext(path)[1].lower() != ".png":
         raise ValueError("imwrite: only PNG files are written, not %r" % (os.path.splitext(path)[1] or path,))

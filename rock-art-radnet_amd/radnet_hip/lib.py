@@ -306,6 +306,11 @@ def load_library():
         "radnet_deflate_piece_cap": (i64, [vp, i32, i32]),
         "radnet_deflate_pack": (C.c_int, [vp, vp, i64, vp, i32, vp, i64, vp]),
         "radnet_deflate_build_code": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32)]),
+        "radnet_deflate_lz_scan_u8": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, vp]),
+        "radnet_deflate_lz_emit_u8": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i32, vp, i64, vp]),
+        "radnet_deflate_build_codes_lz": (C.c_int, [vp, vp, vp, vp, vp, i32, C.POINTER(i32)]),
+        "radnet_deflate_lz_piece_cap": (i64, [vp, vp, i32]),
+        "radnet_deflate_stream_bits": (i64, [vp, vp, vp, vp, i32, i32, i64]),
         "radnet_png_check_crcs": (C.c_int, [vp, i64, vp, vp, i32, i32]),
         "radnet_inflate_find_blocks": (C.c_int, [vp, vp, i64, i64, vp, i32, vp]),
         "radnet_inflate_rle_measure": (C.c_int, [vp, vp, i64, vp, i32]),
